@@ -13,6 +13,7 @@ kernel); `substep_traffic` = the substep on the HBM bytes it really moves (PMC c
 C / OpenMP restatement of the reference's CPU path (oracle/tlab_cpu.c, kind "port") on bounded samples of the same workload on the host
 cores of this box, best of several thread counts.  `--gpus N` without a launcher starts torch.distributed.run itself.  Diagnostics:
 `--loopback P` (P z-slab ranks on one GPU), `--decomp IxK` (x/z pencils), `--grid NX NY NZ`, `--nscal`.
+`--dump-outputs DIR` writes the fields the last timed substep left (q, s), as DIR/<name>.npy: see dump_outputs().
 """
 import argparse
 import json
@@ -45,6 +46,32 @@ def synthetic_fields(targets, nx, ny, nz_total, k0, kmax, seed):
               torch.cos(3 * two_pi * x) * torch.cos(two_pi * y) * torch.sin(two_pi * z)]
     for t, sh in zip(targets, shapes):
         t.copy_(((sh + 0.1 * (2.0 * torch.rand(kmax, ny, nx, dtype=torch.float64, device="cuda", generator=gen) - 1.0)) * wall).reshape(-1))
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: at most this many bytes of samples over all fields of all ranks (64 MB allowed)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(path, names, fields, world):
+    """--dump-outputs: the state a caller of the substep receives (velocities q0..q2, scalars s0..), float64, as path/<name>.npy.  A field larger than
+    its share of DUMP_BYTES is written as a sample: the values at sorted indices drawn by a generator seeded with DUMP_SEED and the field's length, so
+    the same arguments sample the same points in every run and every build.  Returns {name: [points written, field length]}."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = max(1, DUMP_BYTES // (8 * len(fields) * world))
+    out = {}
+    for name, f in zip(names, fields):
+        f = f.reshape(-1)
+        n = f.numel()
+        if n > share:
+            idx = np.unique(np.random.default_rng([DUMP_SEED, n]).integers(0, n, share))
+            v = f.index_select(0, torch.from_numpy(idx).to(f.device))
+        else:
+            v = f
+        a = v.detach().to("cpu", torch.float64).numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        out[name] = [int(a.size), int(n)]
+    return out
 
 
 def substep_traffic(kernels, kernels_substeps, per_launch, ms_per_step, grid, dominant_traffic=None):
@@ -304,6 +331,8 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=256, help="n of the n^3 CPU-baseline sample (0 disables)")
     ap.add_argument("--cpu-sample-large", type=int, default=512, help="second, larger CPU-baseline sample, run only on hosts with at least --cpu-large-min-cores CPUs (0 disables)")
     ap.add_argument("--cpu-large-min-cores", type=int, default=48)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the fields the last timed substep left "
+                    "(q, s) as DIR/<name>.npy, float64; fields larger than their share of 48 MB as a fixed, seeded sample (dump_outputs())")
     args = ap.parse_args()
 
     # --gpus N without a launcher: start the N ranks as a CHILD torch.distributed.run (nothing has touched the GPU yet in this process: no
@@ -357,6 +386,7 @@ def main():
     reduce_dev = "cuda" if (world > 1 and bootstrap == "nccl") else "cpu"      # where the small control reductions live
 
     placement = None
+    field_names = ["q0", "q1", "q2"] + ["s%d" % i for i in range(args.nscal)]      # names of the --dump-outputs files, per rank
     import tlab_amd as T
     from tlab_amd.dns import Dns, RKM_EXP3
     from tlab_amd.lib import load
@@ -395,6 +425,7 @@ def main():
         del full
         for r in pranks:
             state_fields += d.st[r]["q"] + d.st[r]["s"]
+        state_names = ["rank%d_%s" % (r, f) for r in pranks for f in field_names]
 
         def substep(k):
             d.substep_of_cycle(k, dtime)
@@ -419,6 +450,7 @@ def main():
             S = d.st[r]
             synthetic_fields(S["q"] + S["s"], nx, ny, nz, r * d.kmax, d.kmax, r)
             state_fields += S["q"] + S["s"]
+        state_names = ["rank%d_%s" % (r, f) for r in range(args.loopback) for f in field_names]
 
         def substep(k):
             d.substep_of_cycle(k, dtime)
@@ -436,6 +468,7 @@ def main():
             except (T.TlabError, RuntimeError) as e:      # the search failed inside the library (the arrays are the pool in order) or the pool did not fit
                 placement = {"error": str(e)}                # (the driver has its arrays back): the run goes on and says so
         state_fields = d.q + d.s
+        state_names = field_names
 
         def substep(k):
             s = k % d.rkm_endstep
@@ -508,6 +541,7 @@ def main():
         S = d.st[rank]
         synthetic_fields(S["q"] + S["s"], nx, ny, nz, rank * d.kmax, d.kmax, rank)
         state_fields = S["q"] + S["s"]
+        state_names = ["rank%d_%s" % (rank, f) for f in field_names]
 
         def substep(k):
             d.substep_of_cycle(k, dtime)
@@ -559,6 +593,11 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=reduce_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    dumped = None
+    if args.dump_outputs:      # what the last timed substep computed, before anything below steps the fields again
+        torch.cuda.synchronize()
+        dumped = {"dir": os.path.abspath(args.dump_outputs), "seed": DUMP_SEED, "dtype": "float64", "last_timed_substep": args.warmup + args.steps - 1,
+                  "fields": dump_outputs(args.dump_outputs, state_names, state_fields, world)}
     # the host's own cost of issuing a substep: `enqueue` above is throttled by the device once the launch queue is full (the host runs ahead of the GPU
     # until hipLaunchKernel blocks), so one more substep is issued into an EMPTY queue and timed on the host alone
     torch.cuda.synchronize()
@@ -658,6 +697,8 @@ def main():
             "kernels": [{k2: (round(v, 6) if isinstance(v, float) else v) for k2, v in k.items()} for k in kernels],
             "kernels_from": kernels_pass,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         single = world == 1 and args.loopback <= 1 and not args.decomp
         if world == 1 and not single:
             # all ranks on one GPU: the transports' exchanges are device copies (k_copy_blocks; the pencil driver's wire format passes k_trp_copy are

@@ -65,13 +65,11 @@ def has_gpu():
     return torch.cuda.is_available()
 
 
-PARITY_ROUND = "r06"
-
-
 def pytest_sessionfinish(session, exitstatus):
     """Composed-path parity, auditable: every comparison of a device (or CPU-port) error against a scatter-derived bound made in this session goes
-    to profiles/<round>/parity_table.json -- per test the measured error, the oracle's own one-ulp scatter, the bound used and what set it.  Written
-    on GPU sessions only (the -m "not gpu" suite holds two such comparisons); a copy under gpurun_out/ travels back from the GPU box."""
+    to profiles/session/parity_table.json -- per test the measured error, the oracle's own one-ulp scatter, the bound used and what set it.  Written
+    on GPU sessions only (the -m "not gpu" suite holds two such comparisons).  The tables kept as a round's record
+    (profiles/<round>/parity_table.json) are copies of such a file: a test session never rewrites them."""
     try:
         import json
         import subprocess
@@ -119,9 +117,9 @@ def pytest_sessionfinish(session, exitstatus):
         # a run of part of the suite must not replace the table of a whole one
         fname = "parity_table.json" if getattr(session, "testscollected", 0) >= 300 else "parity_table_partial_run.json"
         doc["tests_in_session"] = int(getattr(session, "testscollected", 0))
-        for d in (os.path.join(ROOT, "profiles", PARITY_ROUND), os.path.join(ROOT, "gpurun_out", PARITY_ROUND)):
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, fname), "w") as f:
-                json.dump(doc, f, indent=1)
+        d = os.path.join(ROOT, "profiles", "session")
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, fname), "w") as f:
+            json.dump(doc, f, indent=1)
     except Exception as e:       # noqa: BLE001  (bookkeeping must never fail a test session)
         print("parity table not written:", e)

@@ -1,10 +1,13 @@
 """CPU tests: the numpy oracle (oracle/tlab_oracle.py) is pinned
  (1) against the golden vectors generated from the reference's own Fortran (tests/golden/make_golden.py), and
- (2) against oracle/_ref/libtlab_ref.so directly when it is present (build container, or travelled to the GPU box).
+ (2) against oracle/_ref/libtlab_ref.so: its outputs on seeded 1-D lines stored in tests/golden/ref_lib_1d.npz, and the library itself
+     wherever it is built.
 Agreement is expected to ~1e-15 (observed: bitwise); the asserted bound is 1e-14."""
+import os
+
 import numpy as np
 import pytest
-from conftest import golden_files, rel_err
+from conftest import GOLDEN, golden_files, rel_err
 from oracle import tlab_oracle as O
 from oracle import ref_lib as R
 
@@ -80,9 +83,12 @@ def test_hyper_wall_closure_defect_is_what_the_reference_does():
     assert abs(rhs2[0, 0] / coef3 - O.HYPER_BC1_EXT) < 1e-14
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("n,periodic,stretch", [(16, True, False), (33, False, True), (40, False, False), (64, True, False)])
-def test_oracle_vs_reference_library_1d(n, periodic, stretch):
+REF_1D_CASES = [(16, True, False), (33, False, True), (40, False, False), (64, True, False)]
+REF_1D = os.path.join(GOLDEN, "ref_lib_1d.npz")         # the reference library's outputs on the inputs below (tests/golden/make_golden_ref1d.py)
+
+
+def ref_1d_inputs(n, periodic, stretch):
+    """nodes and the seeded (n, 7) operand of one case of test_oracle_vs_reference_library_1d"""
     rng = np.random.default_rng(n)
     if periodic:
         nodes = np.arange(n) / n * 3.0
@@ -90,18 +96,47 @@ def test_oracle_vs_reference_library_1d(n, periodic, stretch):
         nodes = 0.5 * (1 + np.tanh(1.5 * (2 * np.arange(n) / (n - 1) - 1)) / np.tanh(1.5))
     else:
         nodes = np.arange(n) / (n - 1)
+    return nodes, rng.uniform(-1, 1, (n, 7))
+
+
+def ref_1d_outputs(n, periodic, stretch):
+    """the reference library's first and second derivatives of the case, per boundary condition: {"der1_bc<i>": .., "der2_bc<i>": ..}"""
+    nodes, u = ref_1d_inputs(n, periodic, stretch)
     R.init(n, n, n)
     R.fdm_create(2, nodes, periodic, not stretch)
-    p = O.FdmPlan(nodes, periodic, not stretch)
-    u = rng.uniform(-1, 1, (n, 7))
+    out = {}
     for ibc in ((0,) if periodic else (0, 1, 2, 3)):
-        d1 = O.der1_solve(p.der1, ibc, u)
-        assert rel_err(d1, R.der1_solve(2, ibc, u)) <= TOL
-        assert rel_err(O.der2_solve(p.der2, p.der2.lu, u, d1), R.der2_solve(2, u, d1)) <= TOL
+        d1 = R.der1_solve(2, ibc, u)
+        out["der1_bc%d" % ibc], out["der2_bc%d" % ibc] = d1, R.der2_solve(2, u, d1)
+    return out
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref not built (needs /root/reference)")
+def ref_transpose_input():
+    return np.random.default_rng(3).uniform(-1, 1, (70, 130))           # Fortran a(130, 70): spans the 64x64 blocking of TLab_Transpose
+
+
+@pytest.mark.parametrize("n,periodic,stretch", REF_1D_CASES)
+def test_oracle_vs_reference_library_1d(n, periodic, stretch):
+    """against the reference library's outputs stored in tests/golden/ref_lib_1d.npz, and against the library itself where it is built"""
+    nodes, u = ref_1d_inputs(n, periodic, stretch)
+    g = np.load(REF_1D)
+    tag = "n%d_p%d_s%d_" % (n, periodic, stretch)
+    refs = [{k[len(tag):]: g[k] for k in g.files if k.startswith(tag)}]
+    if R.available():
+        refs.append(ref_1d_outputs(n, periodic, stretch))
+    p = O.FdmPlan(nodes, periodic, not stretch)
+    for ref in refs:
+        assert len(ref) == (2 if periodic else 8)
+        for ibc in ((0,) if periodic else (0, 1, 2, 3)):
+            d1 = O.der1_solve(p.der1, ibc, u)
+            assert rel_err(d1, ref["der1_bc%d" % ibc]) <= TOL
+            assert rel_err(O.der2_solve(p.der2, p.der2.lu, u, d1), ref["der2_bc%d" % ibc]) <= TOL
+
+
 def test_transpose_bit_exact_vs_reference():
-    rng = np.random.default_rng(3)
-    a = rng.uniform(-1, 1, (70, 130))           # Fortran a(130, 70): spans the 64x64 blocking of TLab_Transpose
-    assert np.array_equal(R.transpose(a), np.ascontiguousarray(a.T))
+    a = ref_transpose_input()
+    refs = [np.load(REF_1D)["transpose"]]
+    if R.available():
+        refs.append(R.transpose(a))
+    for t in refs:
+        assert np.array_equal(t, np.ascontiguousarray(a.T))
