@@ -7,11 +7,15 @@ RHS hot path (OPR_Burgers x (12+3 ns), OPR_Partial x 5, OPR_Poisson, pointwise a
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one explicit RK substep (TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT, tools/dns/time.f90:559) on synthetic fields
-already resident in HBM.  Prints ONE JSON line on rank 0.  The `roofline` object is measured live with HIP events placed
-by the library around every kernel launch on its own stream; `targets` = OPR_Partial_{X,Y,Z}(OPR_P1) standalone (the north-star's own
-kernel); `substep_traffic` = the substep on the HBM bytes it really moves (PMC counters, profiles/traffic.json); `cpu_baseline` times the
-C / OpenMP restatement of the reference's CPU path (oracle/tlab_cpu.c, kind "port") on bounded samples of the same workload on the host
-cores of this box, best of several thread counts.  `--gpus N` without a launcher starts torch.distributed.run itself.  Diagnostics:
+already resident in HBM.  Prints ONE JSON line on rank 0.  A plain run sets up (arrays placed by the search of tlab_dns_place_arrays), warms up,
+times the K steps, writes the outputs of --dump-outputs and prints the line: the headline, `config`, `placement` and the `roofline` object,
+measured live with HIP events placed by the library around the dominant kernel's launches in the timed region.
+`--full` adds everything that takes runs of its own, after the timed region: `kernels` = the table of all kernels from a pass with every launch
+timed; `host_issue_empty_queue_ms`; `copy_ceiling(_own)`; `targets` = OPR_Partial_{X,Y,Z}(OPR_P1) standalone (the north-star's own kernel);
+`substep_traffic` = the substep on the HBM bytes it really moves (PMC counters, profiles/traffic.json); the `walls_freeslip`,
+`closure_as_compiled_reference` and `fortran_host` legs; `cpu_baseline` times the C / OpenMP restatement of the reference's CPU path
+(oracle/tlab_cpu.c, kind "port") on bounded samples of the same workload on the host cores of this box, best of several thread counts, and
+`cpu_baseline_reference` the reference's own routines.  `--gpus N` without a launcher starts torch.distributed.run itself.  Diagnostics:
 `--loopback P` (P z-slab ranks on one GPU), `--decomp IxK` (x/z pencils), `--grid NX NY NZ`, `--nscal`.
 `--dump-outputs DIR` writes the fields the last timed substep left (q, s), as DIR/<name>.npy: see dump_outputs().
 """
@@ -325,10 +329,13 @@ def main():
     ap.add_argument("--placement-pool", type=int, default=56, help="candidate allocations of the placement search")
     ap.add_argument("--time-every-launch", action="store_true", help="events around every kernel launch inside the timed region (the kernel table then comes "
                     "from the timed region itself; costs ~0.2 ms per substep at 512^3)")
-    ap.add_argument("--no-fortran-host", action="store_true", help="skip the `fortran_host` leg of the default single-GPU line (the Fortran mini-driver timed at the "
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what takes runs of its own: the table of all kernels, "
+                    "copy ceilings, standalone OPR_Partial targets, HBM traffic of the substep, the free-slip / reference-closure / Fortran-host legs and the "
+                    "CPU baselines (a plain run reports the timed region alone)")
+    ap.add_argument("--no-fortran-host", action="store_true", help="skip the `fortran_host` leg of the --full single-GPU line (the Fortran mini-driver timed at the "
                     "benchmark's size in a child process, after the timed region)")
-    ap.add_argument("--no-freeslip-leg", action="store_true", help="skip the extra `walls_freeslip` timing of the default single-GPU line")
-    ap.add_argument("--cpu-sample", type=int, default=256, help="n of the n^3 CPU-baseline sample (0 disables)")
+    ap.add_argument("--no-freeslip-leg", action="store_true", help="skip the extra `walls_freeslip` and `closure_as_compiled_reference` timings of the --full single-GPU line")
+    ap.add_argument("--cpu-sample", type=int, default=256, help="n of the n^3 CPU-baseline sample of --full (0 disables)")
     ap.add_argument("--cpu-sample-large", type=int, default=512, help="second, larger CPU-baseline sample, run only on hosts with at least --cpu-large-min-cores CPUs (0 disables)")
     ap.add_argument("--cpu-large-min-cores", type=int, default=48)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the fields the last timed substep left "
@@ -566,7 +573,7 @@ def main():
 
     # Every launch of the warm-up is timed by the library's events; the kernel with the largest summed time among the full-field kernels is the
     # dominant one, and in the timed region only ITS launches carry events (two event records per timed launch hold the stream for ~3 us each: with
-    # all ~45 launches of a substep timed, 0.2 ms of the 16).  The table of all kernels comes from a pass of its own after the timed region.
+    # all ~45 launches of a substep timed, 0.2 ms of the 16).  The table of all kernels comes from a pass of its own after the timed region (--full).
     L.tlab_profile_filter(None)
     L.tlab_profile_reset()
     L.tlab_profile_enable(1)
@@ -599,11 +606,13 @@ def main():
         dumped = {"dir": os.path.abspath(args.dump_outputs), "seed": DUMP_SEED, "dtype": "float64", "last_timed_substep": args.warmup + args.steps - 1,
                   "fields": dump_outputs(args.dump_outputs, state_names, state_fields, world)}
     # the host's own cost of issuing a substep: `enqueue` above is throttled by the device once the launch queue is full (the host runs ahead of the GPU
-    # until hipLaunchKernel blocks), so one more substep is issued into an EMPTY queue and timed on the host alone
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    substep(args.warmup + args.steps)
-    issue_empty = time.perf_counter() - t0
+    # until hipLaunchKernel blocks), so one more substep is issued into an EMPTY queue and timed on the host alone (--full)
+    issue_empty = None
+    if args.full:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        substep(args.warmup + args.steps)
+        issue_empty = time.perf_counter() - t0
     torch.cuda.synchronize()
     finite = all(bool(torch.isfinite(t).all()) for t in state_fields)
     # what RCCL itself saw (ncclCommCount / ncclCommCuDevice of the communicator inside libtlab_amd_comm.so), not what this script passed in: the first
@@ -626,7 +635,9 @@ def main():
     dom = next((k for k in timed_rows if k["alg_bytes_per_launch"] > 1e6), None)
     kernels, kernels_pass = timed_rows, "the timed region (every launch timed)"
     kernels_substeps = args.steps          # the number of substeps the table `kernels` covers (its `calls` are sums over them)
-    if dom_tag is not None:      # the table of all kernels: a pass of its own, every launch timed, same fields (every rank takes part in the exchanges)
+    if dom_tag is not None and not args.full:      # the timed region timed the dominant kernel alone: no table of all kernels in a plain run
+        kernels = kernels_pass = None
+    elif dom_tag is not None:      # the table of all kernels: a pass of its own, every launch timed, same fields (every rank takes part in the exchanges)
         npass = min(args.steps, 6)
         L.tlab_profile_filter(None)
         L.tlab_profile_reset()
@@ -673,7 +684,6 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
             "host_issue_ms_per_step": enqueue / args.steps * 1e3,
-            "host_issue_empty_queue_ms": issue_empty * 1e3,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -694,13 +704,16 @@ def main():
                 "frac": dom["alg_GBps"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_meta, "avg_launch_ms": dom["avg_ms"], "launches": dom["calls"],
                 "share_of_step": dom["total_ms"] / (ms_per_step * args.steps)},
             "substep_alg_GBps": (736.0 + 152.0 * args.nscal) * npts / (ms_per_step * 1e-3) / 1e9,
-            "kernels": [{k2: (round(v, 6) if isinstance(v, float) else v) for k2, v in k.items()} for k in kernels],
-            "kernels_from": kernels_pass,
         }
+        if issue_empty is not None:
+            out["host_issue_empty_queue_ms"] = issue_empty * 1e3
+        if kernels is not None:
+            out["kernels"] = [{k2: (round(v, 6) if isinstance(v, float) else v) for k2, v in k.items()} for k in kernels]
+            out["kernels_from"] = kernels_pass
         if dumped is not None:
             out["dump_outputs"] = dumped
         single = world == 1 and args.loopback <= 1 and not args.decomp
-        if world == 1 and not single:
+        if world == 1 and not single and kernels is not None:
             # all ranks on one GPU: the transports' exchanges are device copies (k_copy_blocks; the pencil driver's wire format passes k_trp_copy are
             # packing work that stays on N GPUs) standing in for what xGMI carries on N GPUs.  Their share of the line, so that the work of the ranks
             # can be read without it: summed launch durations of the kernel-table pass per substep
@@ -717,7 +730,7 @@ def main():
             out["placement"] = None if placement is None else placement if "error" in placement else dict(
                 placement, what="tlab_dns_place_arrays before the timed region: ms per substep of the allocations in the order the allocator gave them "
                                 "(ms_first), of the assignment the run uses (ms_best) and of the median / worst assignment tried; --placement-trials 0 skips it")
-        if single:
+        if single and args.full:
             # context for the roofline fraction: what a plain device copy of one field reaches on THIS box (read + write bytes), after the timed
             # region.  The 8 TB/s peak is not reachable by any kernel; the streaming kernels above are to be read against this figure too.
             src, dst = d.hq[0], d.hs[0]
@@ -749,7 +762,7 @@ def main():
                         out["roofline"]["frac_of_own_pattern"] = out["roofline"]["achieved"] / pat
                 except Exception as e:       # noqa: BLE001
                     out["copy_ceiling_own"] = {"error": repr(e)}
-        if single:
+        if single and args.full:
             # the north-star's own target kernel, standalone on this box: OPR_Partial_{X,Y,Z}(OPR_P1) at the benchmark's grid, 16 B per point
             # (SURVEY.md 8d), >= 40 % of the 8 TB/s HBM peak asked for OPR_Partial_X at 512^3
             targets = {}
@@ -778,7 +791,7 @@ def main():
             if tj:
                 out["substep_traffic"] = substep_traffic(kernels, kernels_substeps, tj, ms_per_step, (nx, ny, nz),
                                                          None if out["roofline"] is None else out["roofline"]["traffic"])
-        if single and args.walls == "noslip" and not args.no_freeslip_leg:
+        if single and args.full and args.walls == "noslip" and not args.no_freeslip_leg:
             # the same workload with the reference's DEFAULT walls (VelocityJmin/Jmax = freeslip, Neumann scalars: BOUNDARY_BCS_NEUMANN_Y in the tail
             # of the substep), timed the same way right after the headline: the headline keeps no-slip / Dirichlet walls, this key says what the default costs
             d = None
@@ -814,7 +827,7 @@ def main():
                                      "what": "same box and steps with VelocityJmin/Jmax = freeslip and Neumann scalars (the reference's default walls), arrays placed by the same search"}
             del d2
             torch.cuda.empty_cache()
-        if single and args.walls == "noslip" and not args.no_freeslip_leg:
+        if single and args.full and args.walls == "noslip" and not args.no_freeslip_leg:
             # ... and with the wall closure of the second derivative that the reference AS COMPILED uses (its out-of-bounds read finds 0.1: DESIGN.md section 2,
             # defect 1), which is the closure the parity fixtures made by the reference hold; the headline times the consistent closure 0.0.  Same
             # kernels, same bytes: only two table entries differ.
@@ -847,7 +860,7 @@ def main():
                                                     "what": "same box, steps and kernels with the wall closure 0.1 of the flang-built reference, arrays placed by the same search"}
             del d3
             torch.cuda.empty_cache()
-        if single and not args.no_fortran_host and args.nscal == 1 and not args.ystretch and args.walls == "noslip":
+        if single and args.full and not args.no_fortran_host and args.nscal == 1 and not args.ystretch and args.walls == "noslip":
             # the configuration north_star names: the Fortran RK driver on the device path, at this size, in a child process of its own (its arrays in
             # the host's layout q(isize_field, 3) ...): the UNCHANGED time loop (link-time RHS + the reference's DAXPY / DSCAL, which the library
             # completes to one fused substep: csrc/deferred.cpp) and the six-line patch of time.f90, ms per substep by the driver's own clock
@@ -865,7 +878,7 @@ def main():
                     out["fortran_host"] = {"error": repr(e)}
             else:
                 out["fortran_host"] = {"error": "tlab_amd/fortran/_build_rk/test_rk_driver not built (needs the reference's module files: build container only)"}
-        if args.cpu_sample > 0 and world == 1 and args.loopback <= 1:      # rank 0 at N = 1 only
+        if args.full and args.cpu_sample > 0 and world == 1 and args.loopback <= 1:      # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.nscal)
             # ... and the host used the way the reference uses it (one rank per core): independent instances on disjoint core ranges.  The larger of
             # the two is `cpu_baseline`; the other one stays in the record.

@@ -69,14 +69,14 @@ def test_place_arrays_refuses_a_pool_that_is_too_small(T):
 
 
 def test_bench_line_of_one_gpu_carries_the_placement_report_and_times_the_dominant_kernel_only(T):
-    """bench.py's default single-GPU line at a small box: the placement search ran before the timed region (its report is in the line), the roofline
+    """bench.py --full's single-GPU line at a small box: the placement search ran before the timed region (its report is in the line), the roofline
     object comes from events around the dominant kernel only -- a few launches per timed substep -- and the table of all kernels from its own pass."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--n", "256", "--steps", "6", "--warmup", "3", "--cpu-sample", "0", "--no-freeslip-leg", "--no-fortran-host", "--placement-trials", "4",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--n", "256", "--steps", "6", "--warmup", "3", "--cpu-sample", "0", "--no-freeslip-leg", "--no-fortran-host", "--placement-trials", "4",
            "--placement-pool", "24"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]

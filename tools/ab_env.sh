@@ -7,7 +7,7 @@ mkdir -p "$O"
 K=${KERNELS:-"k_xline<BURGERS> k_htile<BURGERS> k_ptile<BURGERS> k_ode_nn"}
 for r in 1 2; do
   for v in "$@"; do
-    env "$VAR=$v" python bench.py --steps ${STEPS:-15} --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/${VAR}_${v}_$r.json"
+    env "$VAR=$v" python bench.py --full --steps ${STEPS:-15} --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/${VAR}_${v}_$r.json"
     python - "$O/${VAR}_${v}_$r.json" "$VAR=$v run $r" $K <<'PY'
 import json, sys
 r = json.load(open(sys.argv[1]))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Reads bench.py's JSON line on stdin and prints ms_per_step and the per-kernel table (calls per step, average ms, ms per step)."""
+"""Reads the JSON line of bench.py --full on stdin and prints ms_per_step and the per-kernel table (calls per step, average ms, ms per step)."""
 import json
 import sys
 

@@ -19,7 +19,7 @@ one() {
     : > "$O/smi_samples.txt"
     sample &
     SP=$!
-    python3 bench.py --steps 60 --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/bs_run.json"
+    python3 bench.py --full --steps 60 --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/bs_run.json"
     wait $SP
     python3 - "$O/bs_run.json" "$1" "$T0" "$O/smi_samples.txt" >> "$OUT" <<'PY'
 import json, sys, time, re

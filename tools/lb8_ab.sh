@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { python bench.py --loopback 8 --steps 12 --warmup 3 --cpu-sample 0 2>/dev/null | python -c "
+run() { python bench.py --full --loopback 8 --steps 12 --warmup 3 --cpu-sample 0 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

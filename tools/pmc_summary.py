@@ -147,7 +147,7 @@ def clock(d, cname="GRBM_GUI_ACTIVE", kernels=("k_xline<BURGERS>", "k_htile<BURG
 
 
 def timed_window(d, bench_json):
-    """(rows, t0, t1, bench line): the kernel trace of one bench.py run and the bounds of its TIMED REGION.  The trace of the default command also holds the
+    """(rows, t0, t1, bench line): the kernel trace of one bench.py --full run and the bounds of its TIMED REGION.  The trace also holds the
     launches of the placement search (tlab_dns_place_arrays: 4 substeps per trial on assignments the run does not use), the warm-up, the empty-queue
     substep and the pass that fills the kernel table; the timed region is found by COUNT: the dominant kernel (roofline.kernel of the bench line of
     the same run, `lpp` launches per substep) is launched 4 lpp times per trial, then lpp warmup times, then lpp steps times -- the window runs from
@@ -165,7 +165,8 @@ def timed_window(d, bench_json):
     doms = [r for r in rows if tag(r[2]) == dom]
     i0 = lpp * (4 * trials + warmup)
     if len(doms) <= i0 + lpp * steps:
-        sys.exit("timed_window: %d launches of %s in the trace, %d expected before the end of the timed region" % (len(doms), dom, i0 + lpp * steps + 1))
+        sys.exit("timed_window: %d launches of %s in the trace, %d expected before the end of the timed region (a bench.py run without --full "
+                 "launches nothing after it)" % (len(doms), dom, i0 + lpp * steps + 1))
     return rows, doms[i0][0], doms[i0 + lpp * steps][0], b
 
 

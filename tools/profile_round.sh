@@ -13,9 +13,9 @@ mkdir -p "$O"
 export TMPDIR=/tmp
 cd /tmp
 B="$ROOT/bench.py"
-# 1. the default bench line (what the driver runs) and the same command under the kernel trace
-python3 "$B" > "$O/bench_default.json" 2> "$O/bench_default.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/raw_stats" -- python3 "$B" --steps 6 --warmup 2 --cpu-sample 0 --no-freeslip-leg --no-fortran-host > "$O/bench_under_rocprof.json" 2> "$O/rocprof_stats.err"
+# 1. the default bench line with everything --full measures, and the same command under the kernel trace
+python3 "$B" --full > "$O/bench_default.json" 2> "$O/bench_default.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/raw_stats" -- python3 "$B" --full --steps 6 --warmup 2 --cpu-sample 0 --no-freeslip-leg --no-fortran-host > "$O/bench_under_rocprof.json" 2> "$O/rocprof_stats.err"
 python3 "$ROOT/tools/pmc_summary.py" stats "$O/raw_stats" > "$O/rocprofv3_kernel_stats_bench_steps6.csv"
 # (the trace of the default command also holds the launches of the placement search, the warm-up and the kernel-table pass: the timed region by itself)
 python3 "$ROOT/tools/pmc_summary.py" stats_window "$O/raw_stats" "$O/bench_under_rocprof.json" > "$O/rocprofv3_kernel_stats_bench_steps6_timed_region.csv" 2>> "$O/rocprof_stats.err"
@@ -39,7 +39,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$O/raw_ops_wri
 python3 "$ROOT/tools/pmc_summary.py" pmc "$O/raw_ops_fetch" "$O/raw_ops_write" > "$O/pmc_hbm_traffic_opr_partial_p1.txt"
 python3 "$OPS" --types P1,BURGERS --iters 20 > "$O/ops_standalone.txt" 2>&1
 # 4. the other lines profiles/README.md quotes, same binaries, same session (outside the profiler)
-Q="--cpu-sample 0 --no-freeslip-leg --no-fortran-host"
+Q="--full --cpu-sample 0 --no-freeslip-leg --no-fortran-host"
 python3 "$B" --loopback 8 --steps 20 --warmup 5 $Q > "$O/bench_loopback8_native.json" 2> /dev/null
 TLAB_SLAB_FUSED_X=0 python3 "$B" --loopback 8 --steps 20 --warmup 5 $Q > "$O/bench_loopback8_native_unfused.json" 2> /dev/null
 python3 "$B" --loopback 8 --walls freeslip --steps 20 --warmup 5 $Q > "$O/bench_loopback8_native_freeslip.json" 2> /dev/null

@@ -9,7 +9,7 @@ OUT=$O/sustained_probe.txt
 : > "$OUT"
 T0=$(date +%s.%N)
 one() {
-    python3 bench.py --steps "$1" --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/sp_run.json"
+    python3 bench.py --full --steps "$1" --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/sp_run.json"
     python3 - "$O/sp_run.json" "$2" "$T0" >> "$OUT" <<'PY'
 import json, sys, time
 r = json.load(open(sys.argv[1]))

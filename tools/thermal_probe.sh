@@ -12,7 +12,7 @@ smi() {
 T0=$(date +%s.%N)
 for i in $(seq 1 "$N"); do
     S=$(smi)
-    python3 bench.py --steps 15 --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/thermal_run.json"
+    python3 bench.py --full --steps 15 --warmup 3 --cpu-sample 0 --no-freeslip-leg 2>/dev/null | grep '^{' > "$O/thermal_run.json"
     python3 - "$O/thermal_run.json" "$i" "$T0" "$S" >> "$OUT" <<'PY'
 import json, sys, time
 r = json.load(open(sys.argv[1]))
