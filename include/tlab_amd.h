@@ -321,6 +321,12 @@ int tlab_dns_destroy(tlab_dns_t d);
 /* on (default): the pointwise sums of the RHS are folded into the operator kernels (same summation order as the reference);
  * off: the reference's literal sequence of temporaries + pointwise loops.  Both give the same result to round-off. */
 int tlab_dns_set_fusion(tlab_dns_t d, int on);
+/* Scalar bounds limiting, [Control] ScalLimit = yes with MinScalar / MaxScalar (DNS_BOUNDS_LIMIT, tools/dns/dns_local.f90:67-90, called after the update
+ * of every substep, time.f90:248-250): after s += dte hs, every active scalar becomes min(max(s, lo), hi) at every point, wall planes included; hs is
+ * not touched.  n entries (n <= nscal; scalars beyond n are not limited) of active (!= 0: limited), lo, hi.  active == NULL switches limiting off: the
+ * kernels of a run without bounds, the results bit for bit.  TLAB_EINVAL: n > nscal, a NaN bound, lo > hi.  tlab_time_substep_incompressible_explicit
+ * applies the bounds (in the epilogue of the kernel that finishes each scalar); tlab_rhs_global_incompressible_1 does not update s and does not. */
+int tlab_dns_set_scalar_bounds(tlab_dns_t d, int n, const int *active, const double *lo, const double *hi);
 /* Start of a Runge-Kutta step: TIME_RUNGEKUTTA sets hq = 0, hs = 0 there (tools/dns/time.f90:212-216).  Instead of filling the arrays,
  * tell the driver: the next tlab_rhs_global_incompressible_1 / tlab_time_substep_incompressible_explicit treats them as zero (its first
  * operator launch overwrites instead of accumulating), whatever they contain. */
@@ -344,8 +350,19 @@ int tlab_deferred_axpy(long long n, double a, const double *x, double *y);      
 int tlab_deferred_scal(long long n, double a, double *x);                       /* DSCAL with unit stride:  x *= a   */
 int tlab_deferred_zero(double *a, long long n);                                 /* a(1:n) = 0                        */
 int tlab_deferred_flush(void);
+/* DNS_BOUNDS_LIMIT of an unchanged host (time.f90:248-250, dns_local.f90:67-90, through tlab_amd/fortran/dns_local_device.sed): x = min(max(x, lo), hi).
+ * Recorded like the BLAS calls: the sequence RHS, DAXPY x (3 + ns), one clip per limited s, [DSCAL x (3 + ns)] runs as ONE fused substep with those
+ * bounds (tlab_deferred_stats counts[0]; tlab_deferred_clip_stats counts[0]).  A clip of another array, before the DAXPY of its field, a second clip of one field, or bounds of a driver that has
+ * its own (tlab_*_set_scalar_bounds) make the record run literally, in the order of the calls.  Off: tlab_pw_clip. */
+int tlab_deferred_clip(long long n, double lo, double hi, double *x);
 /* counts[6]: fused substeps run, sequences executed literally, begin_steps taken from zero fills, eager axpy, eager scal, eager zero fills */
 int tlab_deferred_stats(long long *counts);
+/* counts[2]: fused substeps that carried recorded clips (of counts[0] above), clips executed on their own (tlab_pw_clip) */
+int tlab_deferred_clip_stats(long long *counts);
+/* 1: p points into device memory, 0: host memory, < 0: error.  tlab_deferred_axpy / tlab_deferred_scal use it as a guard, so that a BLAS-1 call of the
+ * host on host arrays (the DAXPY / DSCAL of tlab_amd_dns.f90 are global symbols) never reaches a kernel: host + host runs as a host loop at once,
+ * device + device as before, mixed pointers are refused (TLAB_EINVAL).  The ranges seen last are cached. */
+int tlab_pointer_on_device(const void *p);
 /* Which device allocations should play q, s, hq, hs, txc?  The rate of a kernel that streams many arrays at once depends on the SET of allocations
  * it streams (not on any one of them): 4.8 .. 5.9 TB/s for one 13-stream kernel over sets of 1-GiB hipMalloc allocations, 16.0 .. 17.2 ms per substep
  * of the 512^3 box from process to process (profiles/r05/placement_*.txt).  No rule predicts it, so it is searched: given a pool
@@ -497,6 +514,8 @@ int tlab_pencil_dns_destroy(tlab_pencil_dns_t d);
 int tlab_pencil_dns_bind(tlab_pencil_dns_t d, int l, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc);
 long long tlab_pencil_dns_info(tlab_pencil_dns_t d, int what);   /* 0 imax, 1 kmax, 2 kmax / npro_i, 3 doubles of a txc array, 4 nlocal, 5 first local rank */
 int tlab_pencil_dns_set_bcs(tlab_pencil_dns_t d, const int *flow_jmin, const int *flow_jmax, const int *scal_jmin, const int *scal_jmax);
+/* scalar bounds limiting, as tlab_dns_set_scalar_bounds: applied by tlab_pencil_dns_substep in the update pass of each limited scalar */
+int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi);
 int tlab_pencil_dns_begin_step(tlab_pencil_dns_t d);
 int tlab_pencil_dns_rhs(tlab_pencil_dns_t d, double dte);                                    /* RHS_GLOBAL_INCOMPRESSIBLE_1 */
 /* The transpositions are started AHEAD of independent launches (the reference's analogue: tools/dns/rhs_global_incompressible_nbc.f90:135-382): while one
@@ -538,6 +557,8 @@ int tlab_slab_dns_begin_step(tlab_slab_dns_t d);                 /* as tlab_dns_
 int tlab_deferred_slab_rhs(tlab_slab_dns_t d, double dte);
 int tlab_deferred_pencil_rhs(tlab_pencil_dns_t d, double dte);
 int tlab_slab_dns_set_remove_divergence(tlab_slab_dns_t d, int on);
+/* scalar bounds limiting, as tlab_dns_set_scalar_bounds: applied by tlab_slab_dns_substep, one pass per limited scalar after the substep */
+int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi);
 /* as tlab_dns_set_surface_bcs: the dynamic surface model of the scalars on z-slabs.  The plane average of BOUNDARY_BCS_SURFACE_Y (AVG1V2D,
  * boundary_bcs.f90:520,535) is an all-reduce: the transport's allreduce is called with op = 2 (MPI_SUM) on the ranks' plane averages. */
 int tlab_slab_dns_set_surface_bcs(tlab_slab_dns_t d, const int *sfc_jmin, const int *sfc_jmax, const double *cpl_jmin, const double *cpl_jmax);      /* as tlab_dns_set_remove_divergence ([Main] TermDivergence) */
@@ -559,6 +580,7 @@ int tlab_pw_sum3(double *a, const double *b, const double *c, long long n);     
 int tlab_pw_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n); /* h -= .., x3 */
 int tlab_pw_rk_update(double *q, double *h, double dte, double kco, int scale, long long n);             /* q += dte h; h *= kco */
 int tlab_pw_fill(double *a, double value, long long n);      /* a = value   (hq = 0.0_wp at the start of a Runge-Kutta step, time.f90:212-216) */
+int tlab_pw_clip(double *a, double lo, double hi, long long n);         /* a = min(max(a, lo), hi)  (DNS_BOUNDS_LIMIT, dns_local.f90:67-90) */
 int tlab_pw_scale(double *a, double alpha, long long n);     /* a = alpha a (hq = kco hq between substeps, time.f90:272-297)                    */
 /* fused tail of a substep for one field: h -= g (g may be NULL); wall planes of h = pb / pt (NULL = zeros); q += dte h; h *= kco if scale
  * (rhs_global_incompressible_1.f90:348-352, :373-375; time.f90:645-664, :272-297) */

@@ -663,6 +663,8 @@ struct OpExtra {
     int fscale = 0, fnx = 1, fny = 1;
     const double *fpb = nullptr, *fpt = nullptr;      // ... with given wall tendencies (Neumann walls) instead of zero
     int ffin[4] = {0, 0, 0, 0};
+    int fclip[4] = {0, 0, 0, 0};      // k_xline finishing epilogue: scalar bounds (XLineArgs::fclip)
+    double flo[4] = {0, 0, 0, 0}, fhi[4] = {0, 0, 0, 0};
     double *fdiv = nullptr;
     double fidte = 0.0;
     unsigned fresh_mask = 0;        // k_htile MODE_BURGERS: fields that overwrite their tendency in an accumulating launch
@@ -862,7 +864,8 @@ void run_xline(tlab_fdm_plan_t g, const LineGeom &geom, int mode, int ibc, const
     a.in0b = ex.in0b; a.in0b_scale = ex.scale; a.acc = ex.sub ? 2 : (ex.acc ? 1 : 0);
     a.fq = ex.fq; a.fdte = ex.fdte; a.fkco = ex.fkco; a.fscale = ex.fscale; a.fnx = ex.fnx; a.fny = ex.fny; a.fpb = ex.fpb; a.fpt = ex.fpt;
     a.nf = ex.nf > 0 ? ex.nf : 1;
-    for (int f = 0; f < 4; ++f) { a.fs[f] = ex.nf > 0 ? ex.fs[f] : in0; a.fo[f] = ex.nf > 0 ? ex.fo[f] : out0; a.fnu[f] = ex.nf > 0 ? ex.fnu[f] : nu; a.ffin[f] = ex.ffin[f]; }
+    for (int f = 0; f < 4; ++f) { a.fs[f] = ex.nf > 0 ? ex.fs[f] : in0; a.fo[f] = ex.nf > 0 ? ex.fo[f] : out0; a.fnu[f] = ex.nf > 0 ? ex.fnu[f] : nu; a.ffin[f] = ex.ffin[f];
+                              a.fclip[f] = ex.fclip[f]; a.flo[f] = ex.flo[f]; a.fhi[f] = ex.fhi[f]; }
     a.fdiv = ex.fdiv; a.fidte = ex.fidte;
     a.ari = ex.ari; a.ari_ny = ex.ari_ny;
     a.s1 = g->stencil(1, ibc);
@@ -1052,7 +1055,8 @@ bool tlab_internal_burgers_can_div(int dir, tlab_fdm_plan_t g, int nx, int ny, i
 
 bool tlab_internal_burgers_acc_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, int nf, const double *nu, const double *const *s,
                                  const double *vel, double *const *result, bool overwrite, const int *finish, double dte, double kco,
-                                 int scale, double *divx, double idte, unsigned fresh_mask, const double *ari) {
+                                 int scale, double *divx, double idte, unsigned fresh_mask, const double *ari, const int *clip, const double *clip_lo,
+                                 const double *clip_hi) {
     check_common(dir, g, nx, ny, nz, ibc);
     if (nf < 1 || nf > 4) throw Invalid("1 to 4 fields per call");
     if (tlab_internal_anelastic() && !ari) return false;      // the operator state says anelastic: the plain fused kernels would drop the density weight
@@ -1072,6 +1076,12 @@ bool tlab_internal_burgers_acc_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int
         if (!tlab_internal_burgers_can_finish(dir, g, nx, ny, nz)) throw Invalid("internal: this Burgers launch cannot finish a field");
         for (int f = 0; f < nf; ++f) ex.ffin[f] = finish[f];
         ex.fdte = dte; ex.fkco = kco; ex.fscale = scale; ex.fny = ny;
+        if (clip)      // scalar bounds of the finished fields (mode 1: every line, 2: interior lines only)
+            for (int f = 0; f < nf; ++f)
+                if (finish[f] && clip[f]) { ex.fclip[f] = clip[f]; ex.flo[f] = clip_lo[f]; ex.fhi[f] = clip_hi[f]; }
+    } else if (clip) {
+        for (int f = 0; f < nf; ++f)
+            if (clip[f]) throw Invalid("internal: bounds without a finishing launch");
     }
     if (divx) {      // divx: the launch also writes (x) / adds (y, z) d/dx (h + idte vel) of the field that is the velocity itself (a term of the pressure forcing)
         if (!(dir == 1 ? tlab_internal_burgers_can_finish(dir, g, nx, ny, nz) : tlab_internal_burgers_can_div(dir, g, nx, ny, nz)))
@@ -1133,7 +1143,7 @@ int tlab_opr_burgers_add_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, i
         for (int f = 0; f < nf; ++f)
             if (!s[f] || !result[f] || result[f] == s[f] || result[f] == vel) throw Invalid("tlab_opr_burgers_add_n: null or aliased arrays");
         if (!tlab_internal_anelastic() &&
-            tlab_internal_burgers_acc_n(dir, g, nx, ny, nz, ibc, nf, nu, s, vel, result, overwrite != 0, nullptr, 0.0, 1.0, 0, nullptr, 0.0, 0u, nullptr)) return;
+            tlab_internal_burgers_acc_n(dir, g, nx, ny, nz, ibc, nf, nu, s, vel, result, overwrite != 0, nullptr, 0.0, 1.0, 0, nullptr, 0.0, 0u, nullptr, nullptr, nullptr, nullptr)) return;
         for (int f = 0; f < nf; ++f) {
             if (overwrite) hip_check(hipMemsetAsync(result[f], 0, (size_t)nx * ny * nz * sizeof(double), g_stream), "memset");
             const int rc = tlab_opr_burgers_add(dir, g, nx, ny, nz, ibc, nu[f], s[f], vel, result[f], tmp1, tmp2);

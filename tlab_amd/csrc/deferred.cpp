@@ -12,11 +12,15 @@
 // scale) that the patched host of INTEGRATION.md section 3b would have made.  Same kernels, same arguments: the fields are those of the fused
 // route to the bit.  A sequence that does not match (other vectors, other factors, another order) is executed literally, in the order it came.
 //
+// The host's DNS_BOUNDS_LIMIT (time.f90:248-250; tlab_amd/fortran/dns_local_device.sed turns its loop into tlab_deferred_clip) sits between the DAXPYs
+// and the DSCALs: a clip of a recorded s after its DAXPY is recorded too and becomes the driver's bounds for the one fused call.
+//
 // What makes it safe: every launch of the library fetches its stream through tlab_current_stream(), which flushes first; tlab_sync, the copies and
 // tlab_free flush as well.  What it cannot see: a host statement that reads a device array directly (hipMalloc memory is host-addressable on
 // MI355X): such a host calls tlab_deferred_flush() or tlab_sync() first, or keeps the layer off (the default).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
@@ -30,6 +34,13 @@ int tlab_internal_dns_nscal(tlab_dns_t d);
 // the arrays a decomposed driver is bound to (one local rank: a Fortran / MPI host), slab.cpp / pencil.cpp; false: not bound, or several local ranks
 bool tlab_internal_slab_bound(tlab_slab_dns_t d, double *const **q, double *const **s, double *const **hq, double *const **hs, int *nscal, long long *n);
 bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, double *const **q, double *const **s, double *const **hq, double *const **hs, int *nscal, long long *n);
+// the drivers' own scalar bounds (tlab_*_set_scalar_bounds): rhs.cpp, slab.cpp, pencil.cpp
+bool tlab_internal_dns_has_bounds(tlab_dns_t d);
+bool tlab_internal_slab_has_bounds(tlab_slab_dns_t d);
+bool tlab_internal_pencil_has_bounds(tlab_pencil_dns_t d);
+void tlab_internal_dns_swap_bounds(tlab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
+void tlab_internal_slab_swap_bounds(tlab_slab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
+void tlab_internal_pencil_swap_bounds(tlab_pencil_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
 
 namespace {
 struct Range { double *p; long long n; };
@@ -46,17 +57,32 @@ struct Pending {
     std::vector<double *> x, y;                   // per field: tendency, state
     std::vector<char> upd, scl;
     int nupd = 0, nscl = 0;
+    std::vector<char> clp;                        // per scalar: clipped after its DAXPY (DNS_BOUNDS_LIMIT), with clo / chi
+    std::vector<double> clo, chi;
+    int nclp = 0;
     std::vector<Range> zeros;                     // `hq = 0` of the start of a step, not yet executed
 };
 Pending g_p;
 bool g_on = false, g_busy = false;
 long long g_stat[6] = {0, 0, 0, 0, 0, 0};        // fused substeps, literal flushes, begin_steps, eager axpy, eager scal, eager zero
+long long g_clip_stat[2] = {0, 0};                // fused substeps that carried recorded clips, clips executed on their own
 
 struct Busy {
     bool was;
     Busy() : was(g_busy) { g_busy = true; }
     ~Busy() { g_busy = was; }
 };
+
+// the BLAS guard of tlab_deferred_axpy / _scal: 1 both on the device, 0 both on the host, -2 mixed (refused), -1 the query failed
+int classify(const char *who, const void *x, const void *y) {
+    const int a = tlab_pointer_on_device(x), b = y ? tlab_pointer_on_device(y) : a;
+    if (a < 0 || b < 0) return -1;
+    if (a != b) {
+        tlab_set_error(std::string(who) + ": one array in host memory and one in device memory");
+        return -2;
+    }
+    return a;
+}
 
 int run_zeros_eagerly() {
     std::vector<Range> z;
@@ -87,11 +113,28 @@ bool zeros_are_the_tendencies(const Pending &p) {
 int run_begin(const Pending &p) {
     return p.kind == 0 ? tlab_dns_begin_step(p.d) : p.kind == 1 ? tlab_slab_dns_begin_step(p.slab) : tlab_pencil_dns_begin_step(p.pencil);
 }
+void swap_bounds(Pending &p, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
+    if (p.kind == 1) tlab_internal_slab_swap_bounds(p.slab, on, lo, hi);
+    else if (p.kind == 2) tlab_internal_pencil_swap_bounds(p.pencil, on, lo, hi);
+    else tlab_internal_dns_swap_bounds(p.d, on, lo, hi);
+}
+bool driver_has_bounds(const Pending &p) {
+    return p.kind == 1 ? tlab_internal_slab_has_bounds(p.slab) : p.kind == 2 ? tlab_internal_pencil_has_bounds(p.pencil) : tlab_internal_dns_has_bounds(p.d);
+}
+// the substep the record describes: its bounds are the recorded clips and nothing else (a driver's own bounds do not belong to RHS + DAXPY), put in
+// place for this one call and taken back
 int run_substep(Pending &p, double kco, int scale) {
-    if (p.kind == 1) return tlab_slab_dns_substep(p.slab, p.dte, kco, scale);
-    if (p.kind == 2) return tlab_pencil_dns_substep(p.pencil, p.dte, kco, scale);
-    return tlab_time_substep_incompressible_explicit(p.d, p.dte, kco, scale, p.q.data(), p.s.empty() ? nullptr : p.s.data(), p.hq.data(),
-                                                     p.hs.empty() ? nullptr : p.hs.data(), p.txc.data());
+    std::vector<char> on;
+    std::vector<double> lo, hi;
+    if (p.nclp) { on = p.clp; lo = p.clo; hi = p.chi; }
+    swap_bounds(p, on, lo, hi);
+    int rc;
+    if (p.kind == 1) rc = tlab_slab_dns_substep(p.slab, p.dte, kco, scale);
+    else if (p.kind == 2) rc = tlab_pencil_dns_substep(p.pencil, p.dte, kco, scale);
+    else rc = tlab_time_substep_incompressible_explicit(p.d, p.dte, kco, scale, p.q.data(), p.s.empty() ? nullptr : p.s.data(), p.hq.data(),
+                                                        p.hs.empty() ? nullptr : p.hs.data(), p.txc.data());
+    swap_bounds(p, on, lo, hi);
+    return rc;
 }
 int run_rhs(Pending &p) {
     if (p.kind == 1) return tlab_slab_dns_rhs(p.slab, p.dte);
@@ -119,10 +162,11 @@ int flush_impl() {
     if (rc != TLAB_OK) return rc;
     if (p.nupd == p.nf && (p.nscl == 0 || p.nscl == p.nf)) {      // the whole substep, as the patched host would have called it
         ++g_stat[0];
+        if (p.nclp) ++g_clip_stat[0];
         return run_substep(p, p.nscl ? p.kco : 1.0, p.nscl ? 1 : 0);
     }
     ++g_stat[1];
-    if (p.nupd == p.nf) {                                           // all updated, some scaled: the substep without scaling, then those
+    if (p.nupd == p.nf) {                                           // all updated, some scaled: the substep without scaling (+ clips), then those
         rc = run_substep(p, 1.0, 0);
         for (int f = 0; f < p.nf && rc == TLAB_OK; ++f)
             if (p.scl[f]) rc = tlab_pw_scale(p.x[f], p.kco, p.n);
@@ -131,6 +175,8 @@ int flush_impl() {
     rc = run_rhs(p);
     for (int f = 0; f < p.nf && rc == TLAB_OK; ++f)
         if (p.upd[f]) rc = tlab_pw_rk_update(p.y[f], p.x[f], p.dte, 1.0, 0, p.n);
+    for (int is = 0; is + 3 < p.nf && rc == TLAB_OK; ++is)          // (a clip was recorded after the DAXPY of its field only)
+        if (p.clp[is]) { ++g_clip_stat[1]; rc = tlab_pw_clip(p.y[3 + is], p.clo[is], p.chi[is], p.n); }
     return rc;
 }
 }      // namespace
@@ -172,6 +218,13 @@ int tlab_deferred_stats(long long *counts) {
     return TLAB_OK;
 }
 
+int tlab_deferred_clip_stats(long long *counts) {
+    if (!counts) return TLAB_EINVAL;
+    counts[0] = g_clip_stat[0];
+    counts[1] = g_clip_stat[1];
+    return TLAB_OK;
+}
+
 int tlab_deferred_zero(double *a, long long n) {
     if (!a || n < 0) { tlab_set_error("tlab_deferred_zero: bad arguments"); return TLAB_EINVAL; }
     if (!g_on) { ++g_stat[5]; return tlab_pw_fill(a, 0.0, n); }
@@ -206,6 +259,8 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
     for (int i = 0; i < ns; ++i) { p.x.push_back(hs[i]); p.y.push_back(s[i]); }
     p.upd.assign(p.nf, 0); p.scl.assign(p.nf, 0);
     p.nupd = p.nscl = 0;
+    p.clp.assign(p.nf - 3, 0); p.clo.assign(p.nf - 3, 0.0); p.chi.assign(p.nf - 3, 0.0);
+    p.nclp = 0;
     return TLAB_OK;
 }
 
@@ -234,6 +289,8 @@ static int deferred_decomposed(int kind, tlab_slab_dns_t slab, tlab_pencil_dns_t
     for (int i = 0; i < ns; ++i) { p.x.push_back(hs[i]); p.y.push_back(s[i]); }
     p.upd.assign(p.nf, 0); p.scl.assign(p.nf, 0);
     p.nupd = p.nscl = 0;
+    p.clp.assign(p.nf - 3, 0); p.clo.assign(p.nf - 3, 0.0); p.chi.assign(p.nf - 3, 0.0);
+    p.nclp = 0;
     return TLAB_OK;
 }
 int tlab_deferred_slab_rhs(tlab_slab_dns_t d, double dte) {
@@ -247,6 +304,12 @@ int tlab_deferred_pencil_rhs(tlab_pencil_dns_t d, double dte) {
 
 int tlab_deferred_axpy(long long n, double a, const double *x, double *y) {
     if (!x || !y || n < 0) { tlab_set_error("tlab_deferred_axpy: bad arguments"); return TLAB_EINVAL; }
+    const int where = classify("tlab_deferred_axpy", x, y);
+    if (where < 0) return where == -2 ? TLAB_EINVAL : TLAB_EHIP;
+    if (where == 0) {                    // host arrays: the BLAS-1 call of the host itself, at once (a recorded substep is not touched)
+        for (long long i = 0; i < n; ++i) y[i] += a * x[i];
+        return TLAB_OK;
+    }
     if (g_on && g_p.rhs && g_p.nscl == 0 && n == g_p.n && a == g_p.dte) {
         for (int f = 0; f < g_p.nf; ++f)
             if (!g_p.upd[f] && g_p.x[f] == x && g_p.y[f] == y) { g_p.upd[f] = 1; ++g_p.nupd; return TLAB_OK; }
@@ -261,6 +324,12 @@ int tlab_deferred_axpy(long long n, double a, const double *x, double *y) {
 
 int tlab_deferred_scal(long long n, double a, double *x) {
     if (!x || n < 0) { tlab_set_error("tlab_deferred_scal: bad arguments"); return TLAB_EINVAL; }
+    const int where = classify("tlab_deferred_scal", x, nullptr);
+    if (where < 0) return where == -2 ? TLAB_EINVAL : TLAB_EHIP;
+    if (where == 0) {
+        for (long long i = 0; i < n; ++i) x[i] *= a;
+        return TLAB_OK;
+    }
     if (g_on && g_p.rhs && g_p.nupd == g_p.nf && n == g_p.n && (g_p.nscl == 0 || a == g_p.kco)) {
         for (int f = 0; f < g_p.nf; ++f)
             if (!g_p.scl[f] && g_p.x[f] == x) {
@@ -274,6 +343,67 @@ int tlab_deferred_scal(long long n, double a, double *x) {
     }
     ++g_stat[4];
     return tlab_pw_scale(x, a, n);
+}
+
+int tlab_deferred_clip(long long n, double lo, double hi, double *x) {
+    if (!x || n < 0 || std::isnan(lo) || std::isnan(hi) || lo > hi) {
+        tlab_set_error("tlab_deferred_clip: null array, n < 0, NaN bounds or lo > hi");
+        return TLAB_EINVAL;
+    }
+    if (g_on && g_p.rhs && g_p.nscl == 0 && n == g_p.n && !driver_has_bounds(g_p)) {
+        for (int is = 0; is + 3 < g_p.nf; ++is)
+            if (g_p.y[3 + is] == x) {
+                if (!g_p.upd[3 + is] || g_p.clp[is]) break;       // before its DAXPY, or a second clip: literal
+                g_p.clp[is] = 1; g_p.clo[is] = lo; g_p.chi[is] = hi; ++g_p.nclp;
+                return TLAB_OK;
+            }
+    }
+    if (g_on) {
+        const int rc = flush_impl();
+        if (rc != TLAB_OK) return rc;
+    }
+    ++g_clip_stat[1];
+    return tlab_pw_clip(x, lo, hi, n);
+}
+
+// 1: device memory, 0: host memory, < 0: error.  The allocation ranges of the device pointers seen last are kept (hipMemGetAddressRange), and the host
+// pointers seen last: a time loop hands the same arrays over and over, and hipPointerGetAttributes costs a runtime call.
+int tlab_pointer_on_device(const void *p) {
+    if (!p) { tlab_set_error("tlab_pointer_on_device: null pointer"); return TLAB_EINVAL; }
+    struct DevRange { const char *b = nullptr; size_t n = 0; };
+    static DevRange dev[16];
+    static const void *host[16] = {nullptr};
+    static int next_dev = 0, next_host = 0;
+    const char *c = static_cast<const char *>(p);
+    for (const DevRange &r : dev)
+        if (r.b && c >= r.b && c < r.b + r.n) return 1;
+    for (const void *h : host)
+        if (h == p) return 0;
+    hipPointerAttribute_t at;
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e == hipErrorInvalidValue) {      // memory the runtime does not know: host memory; the query leaves a sticky error behind
+        (void)hipGetLastError();
+        host[next_host] = p; next_host = (next_host + 1) % 16;
+        return 0;
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        tlab_set_error(std::string("tlab_pointer_on_device: hipPointerGetAttributes: ") + hipGetErrorString(e));
+        return TLAB_EHIP;
+    }
+    if (at.type == hipMemoryTypeUnregistered || at.type == hipMemoryTypeHost) {
+        host[next_host] = p; next_host = (next_host + 1) % 16;
+        return 0;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess && base && size) {
+        dev[next_dev].b = static_cast<const char *>(base); dev[next_dev].n = size;
+        next_dev = (next_dev + 1) % 16;
+    } else {
+        (void)hipGetLastError();
+    }
+    return 1;
 }
 
 }      // extern "C"

@@ -304,7 +304,9 @@ __device__ __forceinline__ void xstore(double *__restrict__ p, const double (&u)
 // LV / LV2: table form of the first- / second-derivative system (see xcoef)
 // OCC = 2: two workgroups per CU (two waves per SIMD) asked of the compiler, and the lane-variant tables re-read from LDS where they are used instead of
 // being kept in ~140 registers across the loop over lines and fields (512-point lines: 256 VGPRs + 102 AGPRs = one wave per SIMD otherwise)
-template <int M, int MODE, int LV, int WPL, int LV2 = LV, int TPB = 256, bool CL = false, bool PER = false, int OCC = 1>
+// CLIP: the finishing epilogue also applies the scalar bounds (XLineArgs::fclip); a separate instantiation, so that the kernels of runs without bounds
+// are those of before
+template <int M, int MODE, int LV, int WPL, int LV2 = LV, int TPB = 256, bool CL = false, bool PER = false, int OCC = 1, bool CLIP = false>
 __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline(XLineArgs a) {
     // (CL with one wave per line: stage_red leaves the rows of the two-level reduction empty)
     extern __shared__ double xlds[];
@@ -464,6 +466,13 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
                             const double hv = wall ? 0.0 : x2[p];
                             u[p] = u[p] + a.fdte * hv;
                             x2[p] = a.fscale ? a.fkco * hv : hv;
+                        }
+                        if constexpr (CLIP) {
+                            if (a.fclip[f] == 1 || (a.fclip[f] == 2 && !wall)) {
+                                const double lo = a.flo[f], hi = a.fhi[f];
+#pragma unroll
+                                for (int p = 0; p < M; ++p) u[p] = fmin(fmax(u[p], lo), hi);
+                            }
                         }
                         if (live) xstore<M>(const_cast<double *>(src) + off, u);
                     }
@@ -1001,7 +1010,21 @@ static hipError_t launch_xline_m(int mode, const XLineArgs &a_in, hipStream_t st
     case MODE_P1: hipLaunchKernelGGL((k_xline<M, MODE_P1, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a); break;
     case MODE_P2: hipLaunchKernelGGL((k_xline<M, MODE_P2, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a); break;
     case MODE_P2_P1: hipLaunchKernelGGL((k_xline<M, MODE_P2_P1, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a); break;
-    case MODE_BURGERS: hipLaunchKernelGGL((k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a); break;
+    case MODE_BURGERS:
+        if constexpr (M <= 8) {      // (the finishing epilogue exists in the 8-rows-per-lane forms only)
+            if (a.fclip[0] || a.fclip[1] || a.fclip[2] || a.fclip[3]) {
+                static bool cattr = false;
+                if (!cattr) {
+                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC, true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                    cattr = true;
+                }
+                hipLaunchKernelGGL((k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC, true>), dim3(grid), dim3(TPB), lds, st, a);
+                break;
+            }
+        }
+        hipLaunchKernelGGL((k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a);
+        break;
     }
     return hipGetLastError();
 }

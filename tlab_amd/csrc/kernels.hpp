@@ -36,6 +36,10 @@ struct XLineArgs {          // k_xline: derivative along the contiguous index, n
     // of this launch, which must be the LAST one that adds to its tendency:  h = fo[f] (+ this term) ; h = 0 on the wall planes ;
     // fs[f] += fdte h ; fo[f] = fscale ? fkco h : h     (time.f90:645-664, :272-297; Dirichlet walls)
     int ffin[4];
+    // ... and (k_xline<.., CLIP = true> only) fclip[f] != 0: scalar bounds limiting of the updated field, fs[f] = min(max(fs[f], flo[f]), fhi[f])
+    // (DNS_BOUNDS_LIMIT, dns_local.f90:67-90): 1 on every line, 2 on interior lines only (the wall planes are finished and clipped by k_wall_fix)
+    int fclip[4];
+    double flo[4], fhi[4];
     // ... and fdiv != NULL: for the field whose operand is the advecting velocity itself (u along x) the launch also writes the x term of the
     // pressure forcing, d/dx (h + fidte u) with the finished tendency h (rhs_global_incompressible_1.f90:197-230), into fdiv
     double *fdiv;
@@ -172,16 +176,19 @@ hipError_t launch_add1(double *h, const double *a, long long n, hipStream_t st);
 hipError_t launch_axpy1(double *o, const double *a, const double *b, double s, long long n, hipStream_t st);
 hipError_t launch_sum3(double *a, const double *b, const double *c, long long n, hipStream_t st);
 hipError_t launch_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n, hipStream_t st);
-hipError_t launch_rk_update(double *q, double *h, double dte, double kco, int scale, long long n, hipStream_t st);
+
 hipError_t launch_get_wall_planes(const double *f, double *hb, double *ht, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_fill_wall_planes(double *f, double vb, double vt, int nx, int ny, int nz, hipStream_t st);
+struct ClipBounds { double lo, hi; };      // scalar bounds limiting (DNS_BOUNDS_LIMIT): s = min(max(s, lo), hi) after the update; NULL: none
 hipError_t launch_final_update(double *q, double *h, const double *g, const double *pb, const double *pt, double dte, double kco, int scale,
-                               int nx, int ny, int nz, hipStream_t st, const double *gw = nullptr);
+                               int nx, int ny, int nz, hipStream_t st, const double *gw = nullptr, const ClipBounds *clip = nullptr);
+hipError_t launch_clip(double *a, double lo, double hi, long long n, hipStream_t st);
+hipError_t launch_rk_update(double *q, double *h, double dte, double kco, int scale, long long n, hipStream_t st, const ClipBounds *clip = nullptr);
 hipError_t launch_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,
-                           hipStream_t stream);
+                           hipStream_t stream, const ClipBounds *clip = nullptr);
 hipError_t launch_sub2(double *o, const double *a, const double *b, long long n, hipStream_t st);
 hipError_t launch_copy_blocks(int n, const double *const *src, double *const *dst, const long long *cnt, hipStream_t st);      // n device copies, batched launches
 hipError_t launch_neumann_planes(const double *u, const double *du, const double *cb, const double *ct, int do_b, int do_t, double *hb,

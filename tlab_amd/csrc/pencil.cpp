@@ -28,6 +28,7 @@ extern hipStream_t tlab_current_stream();
 int tlab_internal_deferred_flush();      // deferred.cpp
 extern void tlab_set_error(const std::string &s);
 extern bool tlab_device_ready();
+int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi);      // rhs.cpp
 extern "C" bool tlab_internal_anelastic();
 extern "C" bool tlab_internal_dealiasing();
 
@@ -119,6 +120,9 @@ struct Rank {
 
 }  // namespace
 
+bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
+                                std::vector<double> &blo, std::vector<double> &bhi);      // rhs.cpp
+
 struct tlab_pencil_dns {
     tlab_pencil_transport tr{};
     tlab_fdm_plan_t g[3] = {nullptr, nullptr, nullptr};
@@ -131,6 +135,8 @@ struct tlab_pencil_dns {
     int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
     std::vector<int> scal_jmin, scal_jmax;
     bool fresh = false;
+    std::vector<char> clip_on;                    // [Control] ScalLimit: DNS_BOUNDS_LIMIT after the update of every substep (empty: no scalar limited)
+    std::vector<double> clip_lo, clip_hi;
     bool overlap = true;              // rhs_overlapped (exchanges started ahead of independent launches) instead of the literal sequence; TLAB_PENCIL_OVERLAP=0
     // tlab_pencil_dns_substep: the velocities are finished by ONE pass each behind the pressure gradient (h -= dp/dx_i, zero wall planes, q += dte h,
     // h *= kco: k_final_update, the arithmetic of k_sub3 + k_set_wall_planes + k_rk_update in the same order) where all their walls are Dirichlet;
@@ -839,9 +845,23 @@ int tlab_pencil_dns_substep(tlab_pencil_dns_t d, double dte, double kco, int sca
         if (d->overlap) rhs_overlapped(d, dte); else rhs(d, dte);
         for (Rank &R : d->rk) {      // time.f90:645-664, :272-297
             for (int i = 0; i < 3 && !d->fin.done; ++i) ok(tlab_pw_rk_update(R.q[i], R.hq[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
-            for (int i = 0; i < d->nscal; ++i) ok(tlab_pw_rk_update(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
+            for (int i = 0; i < d->nscal; ++i) {      // (+ DNS_BOUNDS_LIMIT, dns_local.f90:67-90, in the same pass where the scalar is limited)
+                if (!d->clip_on.empty() && d->clip_on[i])
+                    ok(tlab_internal_pw_rk_update_clip(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n, d->clip_lo[i], d->clip_hi[i]), "tlab_pw_rk_update (bounds)");
+                else ok(tlab_pw_rk_update(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
+            }
         }
     });
+}
+
+int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi) {
+    (void)tlab_internal_deferred_flush();
+    if (!d) { tlab_set_error("tlab_pencil_dns_set_scalar_bounds: null handle"); return TLAB_EINVAL; }
+    std::vector<char> on;
+    std::vector<double> blo, bhi;
+    if (!tlab_internal_check_bounds("tlab_pencil_dns_set_scalar_bounds", d->nscal, n, active, lo, hi, on, blo, bhi)) return TLAB_EINVAL;
+    d->clip_on.swap(on); d->clip_lo.swap(blo); d->clip_hi.swap(bhi);
+    return TLAB_OK;
 }
 
 }  // extern "C"
@@ -852,4 +872,9 @@ bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, double *const **q, double *
     *q = d->rk[0].q.data(); *s = d->rk[0].s.data(); *hq = d->rk[0].hq.data(); *hs = d->rk[0].hs.data();
     *nscal = d->nscal; *n = d->n;
     return true;
+}
+// deferred.cpp: does the driver limit scalars of its own?  And the bounds of a recorded substep, put in place for the one fused call and taken back
+bool tlab_internal_pencil_has_bounds(tlab_pencil_dns_t d) { return d && !d->clip_on.empty(); }
+void tlab_internal_pencil_swap_bounds(tlab_pencil_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
+    d->clip_on.swap(on); d->clip_lo.swap(lo); d->clip_hi.swap(hi);
 }

@@ -82,13 +82,18 @@ __global__ void __launch_bounds__(256) k_sub3(double *__restrict__ h1, double *_
 }
 
 // q = q + dte*h  and then  h = kco*h  (time.f90:645-664 and :272-297; kco == 1 leaves h untouched as after the last substep)
+template <bool CLIP>
 __global__ void __launch_bounds__(256) k_rk_update(double *__restrict__ q, double *__restrict__ h, double dte, double kco, int scale,
-                                                   long long n) {
+                                                   long long n, double lo, double hi) {
     const long long n2 = n >> 1, stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
         double2 qv = reinterpret_cast<double2 *>(q)[i], hv = reinterpret_cast<double2 *>(h)[i];
         qv.x = qv.x + dte * hv.x;
         qv.y = qv.y + dte * hv.y;
+        if constexpr (CLIP) {      // scalar bounds (DNS_BOUNDS_LIMIT) on the updated field
+            qv.x = fmin(fmax(qv.x, lo), hi);
+            qv.y = fmin(fmax(qv.y, lo), hi);
+        }
         reinterpret_cast<double2 *>(q)[i] = qv;
         if (scale) {
             hv.x = kco * hv.x;
@@ -98,6 +103,7 @@ __global__ void __launch_bounds__(256) k_rk_update(double *__restrict__ q, doubl
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         q[n - 1] = q[n - 1] + dte * h[n - 1];
+        if constexpr (CLIP) q[n - 1] = fmin(fmax(q[n - 1], lo), hi);
         if (scale) h[n - 1] = kco * h[n - 1];
     }
 }
@@ -156,16 +162,19 @@ __global__ void __launch_bounds__(256) k_neumann_planes(const double *__restrict
 // fused tail of the substep for one velocity component (rhs_global_incompressible_1.f90:348-352, :373-375; time.f90:645-664, :272-297):
 //   h = h - g (pressure gradient); h = 0 on the wall planes j = 1, ny; q = q + dte*h; h = kco*h (if scale)
 // gw != NULL: h = h - g gw(j), the anelastic form (Thermo_Anelastic_WEIGHT_SUBTRACT with ribackground, :326-329)
+template <bool CLIP>
 __global__ void __launch_bounds__(256) k_final_update(double *__restrict__ q, double *__restrict__ h, const double *__restrict__ g,
                                                       const double *__restrict__ pb, const double *__restrict__ pt, double dte,
-                                                      double kco, int scale, int nx, int ny, long long n, const double *__restrict__ gw) {
+                                                      double kco, int scale, int nx, int ny, long long n, const double *__restrict__ gw,
+                                                      double lo, double hi) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int j = (int)((i / nx) % ny);
         double hv = g ? (gw ? h[i] - g[i] * gw[j] : h[i] - g[i]) : h[i];
         if (j == 0) hv = pb ? pb[(i % nx) + (long long)nx * (i / ((long long)nx * ny))] : 0.0;
         else if (j == ny - 1) hv = pt ? pt[(i % nx) + (long long)nx * (i / ((long long)nx * ny))] : 0.0;
-        q[i] = q[i] + dte * hv;
+        if constexpr (CLIP) q[i] = fmin(fmax(q[i] + dte * hv, lo), hi);      // DNS_BOUNDS_LIMIT (dns_local.f90:67-90) on the updated scalar
+        else q[i] = q[i] + dte * hv;
         h[i] = scale ? kco * hv : hv;
     }
 }
@@ -380,10 +389,29 @@ hipError_t launch_axpy1(double *o, const double *a, const double *b, double s, l
 }
 
 hipError_t launch_final_update(double *q, double *h, const double *g, const double *pb, const double *pt, double dte, double kco, int scale,
-                               int nx, int ny, int nz, hipStream_t st, const double *gw) {
+                               int nx, int ny, int nz, hipStream_t st, const double *gw, const ClipBounds *clip) {
     const long long n = (long long)nx * ny * nz;
     ProfScope ps("k_final_update", st, (double)n * (g ? 40 : 32));
-    hipLaunchKernelGGL(k_final_update, dim3(pw_grid(n)), dim3(256), 0, st, q, h, g, pb, pt, dte, kco, scale, nx, ny, n, gw);
+    if (clip) hipLaunchKernelGGL(k_final_update<true>, dim3(pw_grid(n)), dim3(256), 0, st, q, h, g, pb, pt, dte, kco, scale, nx, ny, n, gw, clip->lo, clip->hi);
+    else hipLaunchKernelGGL(k_final_update<false>, dim3(pw_grid(n)), dim3(256), 0, st, q, h, g, pb, pt, dte, kco, scale, nx, ny, n, gw, 0.0, 0.0);
+    return CHECK_LAUNCH();
+}
+
+// a = min(max(a, lo), hi)   (DNS_BOUNDS_LIMIT, dns_local.f90:67-90, as a pass of its own: tlab_pw_clip and the routes whose last kernel cannot carry it)
+__global__ void __launch_bounds__(256) k_clip(double *__restrict__ a, double lo, double hi, long long n) {
+    const long long n2 = n >> 1, stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += stride) {
+        double2 v = reinterpret_cast<double2 *>(a)[i];
+        v.x = fmin(fmax(v.x, lo), hi);
+        v.y = fmin(fmax(v.y, lo), hi);
+        reinterpret_cast<double2 *>(a)[i] = v;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) a[n - 1] = fmin(fmax(a[n - 1], lo), hi);
+}
+hipError_t launch_clip(double *a, double lo, double hi, long long n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    ProfScope ps("k_clip", st, (double)n * 16);
+    hipLaunchKernelGGL(k_clip, dim3(pw_grid(n / 2 + 1)), dim3(256), 0, st, a, lo, hi, n);
     return CHECK_LAUNCH();
 }
 
@@ -414,9 +442,10 @@ hipError_t launch_sub3(double *h1, double *h2, double *h3, const double *a, cons
     hipLaunchKernelGGL(k_sub3, dim3(pw_grid(n)), dim3(256), 0, st, h1, h2, h3, a, b, c, n);
     return CHECK_LAUNCH();
 }
-hipError_t launch_rk_update(double *q, double *h, double dte, double kco, int scale, long long n, hipStream_t st) {
+hipError_t launch_rk_update(double *q, double *h, double dte, double kco, int scale, long long n, hipStream_t st, const ClipBounds *clip) {
     ProfScope ps("k_rk_update", st, (double)n * (scale ? 32 : 24));
-    hipLaunchKernelGGL(k_rk_update, dim3(pw_grid(n / 2)), dim3(256), 0, st, q, h, dte, kco, scale, n);
+    if (clip) hipLaunchKernelGGL(k_rk_update<true>, dim3(pw_grid(n / 2)), dim3(256), 0, st, q, h, dte, kco, scale, n, clip->lo, clip->hi);
+    else hipLaunchKernelGGL(k_rk_update<false>, dim3(pw_grid(n / 2)), dim3(256), 0, st, q, h, dte, kco, scale, n, 0.0, 0.0);
     return CHECK_LAUNCH();
 }
 hipError_t launch_get_wall_planes(const double *f, double *hb, double *ht, int nx, int ny, int nz, hipStream_t st) {
@@ -463,8 +492,12 @@ hipError_t launch_wall_weighted(const double *a1, const double *a2, const double
 // Wall planes of a field whose interior was finished with zero wall tendencies (the Burgers epilogue's Dirichlet treatment) although its walls are
 // Neumann ones: sb / st = the weighted sums of k_wall_weighted over the STORED tendencies, i.e. kco times the wall tendency when the tendencies were
 // scaled (the functional is linear) -- h(wall) = s, q(wall) += dte s / kco (or dte s unscaled)
+// CLIP: the scalar's bounds on both wall planes afterwards (the interior was clipped by the epilogue that finished it; a plane without a Neumann
+// value keeps its value and is clipped again, which changes nothing)
+template <bool CLIP>
 __global__ void __launch_bounds__(256) k_wall_fix(double *__restrict__ q, double *__restrict__ h, const double *__restrict__ sb,
-                                                  const double *__restrict__ st, double dte, double kco, int scale, int nx, int ny, int nz) {
+                                                  const double *__restrict__ st, double dte, double kco, int scale, int nx, int ny, int nz,
+                                                  double clo, double chi) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)nx * nz) return;
     const int ix = (int)((unsigned long long)i % (unsigned)nx);
@@ -472,10 +505,16 @@ __global__ void __launch_bounds__(256) k_wall_fix(double *__restrict__ q, double
     const long long lo = ix + (long long)nx * ny * k, hi = lo + (long long)nx * (ny - 1);
     if (sb) { const double s = sb[i]; h[lo] = s; q[lo] = q[lo] + dte * (scale ? s / kco : s); }
     if (st) { const double s = st[i]; h[hi] = s; q[hi] = q[hi] + dte * (scale ? s / kco : s); }
+    if constexpr (CLIP) {
+        q[lo] = fmin(fmax(q[lo], clo), chi);
+        q[hi] = fmin(fmax(q[hi], clo), chi);
+    }
 }
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,
-                           hipStream_t stream) {
-    hipLaunchKernelGGL(k_wall_fix, dim3((unsigned)(((long long)nx * nz + 255) / 256)), dim3(256), 0, stream, q, h, sb, st, dte, kco, scale, nx, ny, nz);
+                           hipStream_t stream, const ClipBounds *clip) {
+    const dim3 grid((unsigned)(((long long)nx * nz + 255) / 256));
+    if (clip) hipLaunchKernelGGL(k_wall_fix<true>, grid, dim3(256), 0, stream, q, h, sb, st, dte, kco, scale, nx, ny, nz, clip->lo, clip->hi);
+    else hipLaunchKernelGGL(k_wall_fix<false>, grid, dim3(256), 0, stream, q, h, sb, st, dte, kco, scale, nx, ny, nz, 0.0, 0.0);
     return CHECK_LAUNCH();
 }
 // o = a - b (planes)

@@ -39,7 +39,8 @@ void tlab_internal_poisson_arm_v_final(tlab_poisson_plan_t P, double *q, double 
 bool tlab_internal_burgers_can_finish(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
 bool tlab_internal_burgers_acc_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, int nf, const double *nu, const double *const *s,
                                  const double *vel, double *const *result, bool overwrite, const int *finish, double dte, double kco, int scale,
-                                 double *divx, double idte, unsigned fresh_mask = 0, const double *ari = nullptr);
+                                 double *divx, double idte, unsigned fresh_mask = 0, const double *ari = nullptr, const int *clip = nullptr,
+                                 const double *clip_lo = nullptr, const double *clip_hi = nullptr);
 bool tlab_internal_burgers_fusable_anelastic(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
 bool tlab_internal_burgers_can_div(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
 bool tlab_internal_partial_p1_sub(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, const double *u, double *result);
@@ -62,6 +63,9 @@ struct tlab_dns {
     int flow_jmin[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};   // BcsFlowJmin%type
     int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
     std::vector<int> scal_jmin, scal_jmax;         // BcsScalJmin%type, BcsScalJmax%type
+    // [Control] ScalLimit: DNS_BOUNDS_LIMIT (dns_local.f90:67-90) after the update of every substep, s = min(max(s, lo), hi) for the active scalars
+    std::vector<char> clip_on;                     // empty: no scalar is limited (the kernels of before)
+    std::vector<tlab::ClipBounds> clip_b;
     // dynamic surface model of the scalars (BcsScalJmin/Jmax%SfcType = DNS_SFC_LINEAR, %cpl; boundary_bcs.f90:29-31, 49-50, 478-546)
     std::vector<int> sfc_jmin, sfc_jmax;
     std::vector<double> cpl_jmin, cpl_jmax;
@@ -284,6 +288,9 @@ static void burgers_into(tlab_dns_t d, int dir, double nu, const double *s, cons
     pending_add = true;
 }
 
+// bounds of scalar is, or NULL when it is not limited
+static const tlab::ClipBounds *clip_of(tlab_dns_t d, int is) { return !d->clip_on.empty() && d->clip_on[is] ? &d->clip_b[is] : nullptr; }
+
 static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs,
                      double *const *txc, bool tail_update, double kco, int scale_tendencies) {
     const int nx = d->nx, ny = d->ny, nz = d->nz;
@@ -369,6 +376,15 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     for (int is = 0; is < d->nscal && !scal_neumann_planes; ++is)
         finish_scal = finish_scal && d->scal_jmin[is] == TLAB_DNS_BCS_DIRICHLET && d->scal_jmax[is] == TLAB_DNS_BCS_DIRICHLET;
     finish_scal = finish_scal && !any_surface;      // the wall planes of a scalar with a surface model are not zero
+    // scalar bounds in the epilogue that finishes scalar is: on every line, or -- Neumann walls on the wall-plane route -- on the interior lines, k_wall_fix
+    // clipping the wall planes once they are set
+    auto clip_into = [&](int is, int &mode, double &lo, double &hi) {
+        const tlab::ClipBounds *c = clip_of(d, is);
+        if (!c) return;
+        const bool neu = d->scal_jmin[is] == TLAB_DNS_BCS_NEUMANN || d->scal_jmax[is] == TLAB_DNS_BCS_NEUMANN;
+        mode = (scal_neumann_planes && neu) ? 2 : 1;
+        lo = c->lo; hi = c->hi;
+    };
     // Likewise the x term of the pressure forcing, d/dx (hq1 + u/dte) (:197-230): when the x Burgers launch runs last it holds the finished
     // tendency of u in registers, line by line, and differentiates it on the spot instead of a separate launch re-reading hq1 and u.
     const double idte = d->remove_divergence ? 1.0 / dte : 0.0;      // hq + 0 q is hq bit for bit: the same kernels serve the else-branch (:234-250)
@@ -389,23 +405,27 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             for (size_t e0 = 0; e0 < L.eq.size(); e0 += 4) {
                 const int nf = (int)std::min<size_t>(4, L.eq.size() - e0);
                 const double *sp[4]; double *rp[4]; double nup[4];
-                int fin[4] = {0, 0, 0, 0};
+                int fin[4] = {0, 0, 0, 0}, clip[4] = {0, 0, 0, 0};
+                double clo[4] = {0, 0, 0, 0}, chi[4] = {0, 0, 0, 0};
                 unsigned fresh_mask = 0;
                 bool all_fresh = fresh, any_fresh = false;
                 for (int f = 0; f < nf; ++f) {
                     const int e = L.eq[e0 + f];
                     sp[f] = eqs[e].fld; rp[f] = eqs[e].dst; nup[f] = eqs[e].nu;
                     fin[f] = (finish_scal && L.last_x && e >= 3) ? 1 : 0;        // equations 3.. are the scalars
+                    if (fin[f]) clip_into(e - 3, clip[f], clo[f], chi[f]);
                     const bool fr = fresh && !touched[e];
                     if (fr) { fresh_mask |= 1u << f; any_fresh = true; } else all_fresh = false;
                     touched[e] = true;
                 }
                 const bool any_fin = fin[0] || fin[1] || fin[2] || fin[3];
+                const bool any_clip = clip[0] || clip[1] || clip[2] || clip[3];
                 const bool over = all_fresh && any_fresh;                   // every field of the launch starts its tendency here
                 double *divp = nullptr;
                 if (L.divf >= 0 && (L.dir != 1 || e0 == 0)) divp = tmp1;  // x: batch 0 holds u; y, z: the one-field launches
                 if (!tlab_internal_burgers_acc_n(L.dir, d->g[L.dir - 1], nx, ny, nz, 0, nf, nup, sp, vel[L.dir - 1], rp, over,
-                                                 any_fin ? fin : nullptr, dte, kco, scale_tendencies ? 1 : 0, divp, idte, over ? 0u : fresh_mask))
+                                                 any_fin ? fin : nullptr, dte, kco, scale_tendencies ? 1 : 0, divp, idte, over ? 0u : fresh_mask, nullptr,
+                                                 any_clip ? clip : nullptr, clo, chi))
                     throw Fail(TLAB_EINVAL, "internal: inconsistent fused Burgers path");
             }
         }
@@ -417,15 +437,19 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             for (size_t e0 = 0; e0 < eqs.size(); e0 += 4) {
                 const int nf = (int)std::min<size_t>(4, eqs.size() - e0);
                 const double *sp[4]; double *rp[4]; double nup[4];
-                int fin[4] = {0, 0, 0, 0};
+                int fin[4] = {0, 0, 0, 0}, clip[4] = {0, 0, 0, 0};
+                double clo[4] = {0, 0, 0, 0}, chi[4] = {0, 0, 0, 0};
                 for (int f = 0; f < nf; ++f) {
                     sp[f] = eqs[e0 + f].fld; rp[f] = eqs[e0 + f].dst; nup[f] = eqs[e0 + f].nu;
                     fin[f] = (finish_scal && k == 2 && e0 + f >= 3) ? 1 : 0;        // equations 3.. are the scalars
+                    if (fin[f]) clip_into((int)(e0 + f) - 3, clip[f], clo[f], chi[f]);
                 }
                 const bool any_fin = fin[0] || fin[1] || fin[2] || fin[3];
+                const bool any_clip = clip[0] || clip[1] || clip[2] || clip[3];
                 double *divx = (div_in_burgers && dir == 1 && e0 == 0) ? tmp1 : nullptr;       // batch 0 holds u
                 if (!tlab_internal_burgers_acc_n(dir, d->g[dir - 1], nx, ny, nz, 0, nf, nup, sp, vel[dir - 1], rp, fresh && k == 0,
-                                                 any_fin ? fin : nullptr, dte, kco, scale_tendencies ? 1 : 0, divx, idte, 0u, anel ? d->rib : nullptr))
+                                                 any_fin ? fin : nullptr, dte, kco, scale_tendencies ? 1 : 0, divx, idte, 0u, anel ? d->rib : nullptr,
+                                                 any_clip ? clip : nullptr, clo, chi))
                     throw Fail(TLAB_EINVAL, "internal: inconsistent fused Burgers path");
             }
         }
@@ -554,9 +578,12 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         }
         for (int is = 0; is < d->nscal && !finish_scal; ++is) {
             const int ibc = ibc_y(d->scal_jmin[is], d->scal_jmax[is]);
-            if (ibc == 0) hk(launch_final_update(s[is], hs[is], nullptr, nullptr, nullptr, dte, kco, scale_tendencies, nx, ny, nz, st), "final update");
+            if (ibc == 0) hk(launch_final_update(s[is], hs[is], nullptr, nullptr, nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)),
+                             "final update");
             else if (!tlab_internal_neumann_final(gy, nx, ny, nz, ibc, hs[is], s[is], dte, kco, scale_tendencies))
                 throw Fail(TLAB_EINVAL, "internal: inconsistent fused Neumann tail");
+            else if (const tlab::ClipBounds *c = clip_of(d, is))      // (the y-line tail kernel has no bounds epilogue: a pass of its own)
+                hk(launch_clip(s[is], c->lo, c->hi, n, st), "clip");
         }
         for (int is = 0; is < d->nscal && finish_scal && scal_neumann_planes; ++is) {      // finished by the x Burgers launch but for their wall planes
             const int ibc = ibc_y(d->scal_jmin[is], d->scal_jmax[is]);
@@ -566,7 +593,8 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             if (!d->wall_planes) hk(hipMalloc((void **)&d->wall_planes, 6 * np * sizeof(double)), "hipMalloc");
             double *Sb = d->wall_planes, *St = Sb + np;
             hk(launch_wall_weighted(hs[is], nullptr, W.w, W.w + W.K, W.K, Sb, St, nullptr, nullptr, nx, ny, nz, st), "wall planes");
-            hk(launch_wall_fix(s[is], hs[is], (ibc & 1) ? Sb : nullptr, (ibc & 2) ? St : nullptr, dte, kco, scale_tendencies, nx, ny, nz, st), "wall planes");
+            hk(launch_wall_fix(s[is], hs[is], (ibc & 1) ? Sb : nullptr, (ibc & 2) ? St : nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, clip_of(d, is)),
+               "wall planes");
         }
         return;
     }
@@ -664,7 +692,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         }
         for (int is = 0; is < d->nscal && !finish_scal; ++is) {      // (finish_scal: done in the epilogue of the x Burgers launch)
             scal_planes(is, pb, pt);
-            hk(launch_final_update(s[is], hs[is], nullptr, pb, pt, dte, kco, scale_tendencies, nx, ny, nz, st), "final update");
+            hk(launch_final_update(s[is], hs[is], nullptr, pb, pt, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)), "final update");
         }
     } else {
         if (!anel && !grad_sub) hk(launch_sub3(hq[0], hq[1], hq[2], tmp2, tmp3, tmp4, n, st), "sub3");
@@ -1114,6 +1142,60 @@ int tlab_dns_place_blocks(tlab_dns_t d, int ncand, double *const *cand_q, double
     }
 }
 
+extern "C++" {
+// shared by the three drivers: n entries (<= nscal) of active / lo / hi checked, the bounds of the active ones returned (on[is] = 0 otherwise)
+bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
+                                std::vector<double> &blo, std::vector<double> &bhi) {
+    on.clear(); blo.clear(); bhi.clear();
+    if (!active) return true;
+    if (n < 0 || n > nscal || !lo || !hi) {
+        tlab_set_error(std::string(who) + ": " + std::to_string(n) + " bounds for " + std::to_string(nscal) + " scalars, or NULL lo / hi");
+        return false;
+    }
+    on.assign((size_t)nscal, 0);
+    blo.assign((size_t)nscal, 0.0);
+    bhi.assign((size_t)nscal, 0.0);
+    bool any = false;
+    for (int is = 0; is < n; ++is) {
+        if (!active[is]) continue;
+        if (std::isnan(lo[is]) || std::isnan(hi[is]) || lo[is] > hi[is]) {
+            tlab_set_error(std::string(who) + ": scalar " + std::to_string(is + 1) + " has bounds [" + std::to_string(lo[is]) + ", " + std::to_string(hi[is]) +
+                           "] (NaN, or min > max)");
+            on.clear(); blo.clear(); bhi.clear();
+            return false;
+        }
+        on[is] = 1; blo[is] = lo[is]; bhi[is] = hi[is];
+        any = true;
+    }
+    if (!any) { on.clear(); blo.clear(); bhi.clear(); }      // nothing active: the kernels of a run without bounds
+    return true;
+}
+
+void tlab_internal_dns_swap_bounds(tlab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
+}      // extern "C++"
+
+int tlab_dns_set_scalar_bounds(tlab_dns_t d, int n, const int *active, const double *lo, const double *hi) {
+    (void)tlab_internal_deferred_flush();
+    if (!d) { tlab_set_error("tlab_dns_set_scalar_bounds: null handle"); return TLAB_EINVAL; }
+    std::vector<char> on;
+    std::vector<double> blo, bhi;
+    if (!tlab_internal_check_bounds("tlab_dns_set_scalar_bounds", d->nscal, n, active, lo, hi, on, blo, bhi)) return TLAB_EINVAL;
+    tlab_internal_dns_swap_bounds(d, on, blo, bhi);
+    return TLAB_OK;
+}
+extern "C++" {
+// deferred.cpp: does the driver limit scalars of its own?  And the bounds of a recorded substep, put in place for the one fused call and taken back
+bool tlab_internal_dns_has_bounds(tlab_dns_t d) { return d && !d->clip_on.empty(); }
+void tlab_internal_dns_swap_bounds(tlab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
+    std::vector<double> olo(d->clip_on.size()), ohi(d->clip_on.size());
+    for (size_t i = 0; i < d->clip_b.size(); ++i) { olo[i] = d->clip_b[i].lo; ohi[i] = d->clip_b[i].hi; }
+    std::vector<tlab::ClipBounds> b(on.size());
+    for (size_t i = 0; i < on.size(); ++i) b[i] = {lo[i], hi[i]};
+    d->clip_on.swap(on); d->clip_b.swap(b);
+    lo.swap(olo); hi.swap(ohi);
+}
+}      // extern "C++"
+
 int tlab_dns_set_fusion(tlab_dns_t d, int on) {
     (void)tlab_internal_deferred_flush();
     if (!d) return TLAB_EINVAL;
@@ -1137,6 +1219,17 @@ int tlab_pw_axpy3(double *o1, double *o2, double *o3, const double *h1, const do
 int tlab_pw_sum3(double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_sum3(a, b, c, n, tlab_current_stream())) }
 int tlab_pw_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_sub3(h1, h2, h3, a, b, c, n, tlab_current_stream())) }
 int tlab_pw_rk_update(double *q, double *h, double dte, double kco, int scale, long long n) { PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream())) }
+extern "C++" {
+// q += dte h, q = min(max(q, lo), hi), h *= kco: the scalar update of the decomposed drivers with their bounds (pencil.cpp)
+int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi) {
+    const tlab::ClipBounds c{lo, hi};
+    PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream(), &c))
+}
+}      // extern "C++"
+int tlab_pw_clip(double *a, double lo, double hi, long long n) {
+    if (!a || n < 0 || std::isnan(lo) || std::isnan(hi) || lo > hi) { tlab_set_error("tlab_pw_clip: null array, n < 0, NaN bounds or lo > hi"); return TLAB_EINVAL; }
+    PW_GUARD(launch_clip(a, lo, hi, n, tlab_current_stream()))
+}
 int tlab_pw_fill(double *a, double value, long long n) { PW_GUARD(launch_fill(a, value, n, tlab_current_stream())) }
 int tlab_pw_scale(double *a, double alpha, long long n) { PW_GUARD(launch_scale(a, alpha, n, tlab_current_stream())) }
 int tlab_pw_final_update(double *q, double *h, const double *g, const double *pb, const double *pt, double dte, double kco, int scale, int nx, int ny,

@@ -48,8 +48,9 @@ extern "C" int tlab_internal_dns_neumann_weights(tlab_dns_t d, int ibc, const do
 namespace tlab {
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);                                      // pointwise.hip
+struct ClipBounds;
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,
-                           hipStream_t stream);
+                           hipStream_t stream, const ClipBounds *clip = nullptr);
 hipError_t launch_copy_blocks(int n, const double *const *src, double *const *dst, const long long *cnt, hipStream_t st);      // pointwise.hip
 hipError_t launch_plane_avg(const double *t, int j, int nx, int ny, int nz, double *avg, hipStream_t st);
 hipError_t launch_surface_flux_avg(double *ref, const double *t, int j, double sign, double diff, double cpl, double avg, int nx, int ny, int nz,
@@ -152,6 +153,9 @@ struct Rank {
 
 }  // namespace
 
+bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
+                                std::vector<double> &blo, std::vector<double> &bhi);      // rhs.cpp
+
 struct tlab_slab_dns {
     tlab_slab_transport tr{};
     tlab_fdm_plan_t g[3] = {nullptr, nullptr, nullptr}, gy_elliptic = nullptr;
@@ -173,6 +177,8 @@ struct tlab_slab_dns {
     int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
     std::vector<int> scal_jmin, scal_jmax;
     bool fresh = false;
+    std::vector<char> clip_on;                    // [Control] ScalLimit: DNS_BOUNDS_LIMIT after the update of every substep (empty: no scalar limited)
+    std::vector<double> clip_lo, clip_hi;
     std::vector<int> sfc_jmin, sfc_jmax;          // BcsScalJmin / Jmax%SfcType (0 static, 1 linear) and %cpl per scalar
     std::vector<double> cpl_jmin, cpl_jmax;
     bool remove_divergence = true;     // [Main] TermDivergence: forcing div(hq + q/dte) (rhs_global_incompressible_1.f90:177-232); false: div(hq) (:234-250)
@@ -871,6 +877,10 @@ int tlab_slab_dns_substep(tlab_slab_dns_t d, double dte, double kco, int scale_t
     return guarded([&] {
         if (!d || !(dte > 0.0)) throw Fail(TLAB_EINVAL, "tlab_slab_dns_substep: bad arguments");
         rhs_halo(d, dte, true, dte, kco, scale_tendencies);
+        // DNS_BOUNDS_LIMIT (dns_local.f90:67-90) on the updated scalars: a pass of its own per field (the z pass that finishes them has no bounds epilogue)
+        for (int i = 0; i < (int)d->clip_on.size(); ++i)
+            if (d->clip_on[i])
+                for (Rank &R : d->rk) ok(tlab_pw_clip(R.s[i], d->clip_lo[i], d->clip_hi[i], d->n), "tlab_pw_clip");
     });
 }
 
@@ -915,6 +925,16 @@ int tlab_slab_dns_dilatation_bounds(tlab_slab_dns_t d, double *dil_min, double *
     });
 }
 
+int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi) {
+    (void)tlab_internal_deferred_flush();
+    if (!d) { tlab_set_error("tlab_slab_dns_set_scalar_bounds: null handle"); return TLAB_EINVAL; }
+    std::vector<char> on;
+    std::vector<double> blo, bhi;
+    if (!tlab_internal_check_bounds("tlab_slab_dns_set_scalar_bounds", d->nscal, n, active, lo, hi, on, blo, bhi)) return TLAB_EINVAL;
+    d->clip_on.swap(on); d->clip_lo.swap(blo); d->clip_hi.swap(bhi);
+    return TLAB_OK;
+}
+
 }  // extern "C"
 
 // deferred.cpp: the arrays of the ONE local rank of a Fortran / MPI host (several local ranks -- loopback runs -- have no single DAXPY partner)
@@ -923,4 +943,9 @@ bool tlab_internal_slab_bound(tlab_slab_dns_t d, double *const **q, double *cons
     *q = d->rk[0].q.data(); *s = d->rk[0].s.data(); *hq = d->rk[0].hq.data(); *hs = d->rk[0].hs.data();
     *nscal = d->nscal; *n = d->n;
     return true;
+}
+// deferred.cpp: does the driver limit scalars of its own?  And the bounds of a recorded substep, put in place for the one fused call and taken back
+bool tlab_internal_slab_has_bounds(tlab_slab_dns_t d) { return d && !d->clip_on.empty(); }
+void tlab_internal_slab_swap_bounds(tlab_slab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
+    d->clip_on.swap(on); d->clip_lo.swap(lo); d->clip_hi.swap(hi);
 }

@@ -41,6 +41,22 @@ def _bcs_arrays(nscal, velocity_jmin, velocity_jmax, scalar_jmin, scalar_jmax):
     return fj0, fj1, sj0, sj1
 
 
+def _bounds_arrays(lo, hi, active):
+    """ctypes arrays of the scalar bounds (lo = None: off).  Lists may be shorter than nscal (the scalars beyond them are not limited); the
+    library refuses more entries than nscal, NaN bounds and lo > hi."""
+    if lo is None and hi is None:
+        return 0, None, None, None
+    if lo is None or hi is None:
+        raise ValueError("set_scalar_bounds: give both lo and hi, or neither (off)")
+    lo, hi = [float(v) for v in np.atleast_1d(lo)], [float(v) for v in np.atleast_1d(hi)]
+    act = [1] * len(lo) if active is None else [int(bool(a)) for a in np.atleast_1d(active)]
+    if not (len(lo) == len(hi) == len(act)):
+        raise ValueError("set_scalar_bounds: lo, hi and active differ in length")
+    n = len(lo)
+    m = max(n, 1)
+    return n, (ctypes.c_int * m)(*act), (ctypes.c_double * m)(*lo), (ctypes.c_double * m)(*hi)
+
+
 def rk_coefficients(mode):
     """TIME_INITIALIZE, tools/dns/time.f90:86-108."""
     if mode == RKM_EXP3:   # Williamson 1980
@@ -125,6 +141,12 @@ class Dns:
         if rb.shape != (self.ny,) or ri.shape != (self.ny,):
             raise TlabError("anelastic profiles: ny values each")
         check(load().tlab_dns_set_anelastic(self._h, rb.ctypes.data_as(dp), ri.ctypes.data_as(dp)), "tlab_dns_set_anelastic")
+
+    def set_scalar_bounds(self, lo=None, hi=None, active=None):
+        """[Control] ScalLimit = yes, MinScalar / MaxScalar (DNS_BOUNDS_LIMIT, dns_local.f90:67-90): after the update of every substep each active
+        scalar becomes min(max(s, lo), hi).  lo, hi, active: one entry per scalar (active defaults to all); None switches limiting off."""
+        n, act, l, h = _bounds_arrays(lo, hi, active)
+        check(load().tlab_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_dns_set_scalar_bounds")
 
     def set_fusion(self, on):
         """on (default): pointwise sums folded into the operator kernels; off: the reference's literal sequence."""

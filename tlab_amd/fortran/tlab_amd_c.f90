@@ -251,6 +251,43 @@ module TLab_AMD_C
             import :: c_int, c_long_long
             integer(c_long_long), intent(out) :: counts(6)
         end function
+        ! DNS_BOUNDS_LIMIT of an unchanged host (dns_local_device.sed, TLab_AMD_Bounds_Limit): x = min(max(x, lo), hi), recorded like the BLAS calls
+        integer(c_int) function tlab_deferred_clip(n, lo, hi, x) bind(C, name='tlab_deferred_clip')
+            import :: c_int, c_ptr, c_double, c_long_long
+            integer(c_long_long), value :: n
+            real(c_double), value :: lo, hi
+            type(c_ptr), value :: x
+        end function
+        integer(c_int) function tlab_deferred_clip_stats(counts) bind(C, name='tlab_deferred_clip_stats')
+            import :: c_int, c_long_long
+            integer(c_long_long), intent(out) :: counts(2)
+        end function
+        integer(c_int) function tlab_pointer_on_device(p) bind(C, name='tlab_pointer_on_device')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: p
+        end function
+        integer(c_int) function tlab_pw_clip(a, lo, hi, n) bind(C, name='tlab_pw_clip')
+            import :: c_int, c_ptr, c_double, c_long_long
+            type(c_ptr), value :: a
+            real(c_double), value :: lo, hi
+            integer(c_long_long), value :: n
+        end function
+        ! [Control] ScalLimit of a patched host: the driver applies the bounds inside its substep (n <= nscal entries; active = c_null_ptr: off)
+        integer(c_int) function tlab_dns_set_scalar_bounds(dns, n, active, lo, hi) bind(C, name='tlab_dns_set_scalar_bounds')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, active, lo, hi
+            integer(c_int), value :: n
+        end function
+        integer(c_int) function tlab_slab_dns_set_scalar_bounds(slab, n, active, lo, hi) bind(C, name='tlab_slab_dns_set_scalar_bounds')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: slab, active, lo, hi
+            integer(c_int), value :: n
+        end function
+        integer(c_int) function tlab_pencil_dns_set_scalar_bounds(pencil, n, active, lo, hi) bind(C, name='tlab_pencil_dns_set_scalar_bounds')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: pencil, active, lo, hi
+            integer(c_int), value :: n
+        end function
         integer(c_int) function tlab_rhs_global_incompressible_1(dns, dte, q, s, hq, hs, txc) bind(C, name='tlab_rhs_global_incompressible_1')
             import :: c_int, c_ptr, c_double
             type(c_ptr), value :: dns

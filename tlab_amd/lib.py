@@ -70,6 +70,13 @@ SIGNATURES = {
     "tlab_dns_create": (c_int, [ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_dbl, _dp]),
     "tlab_dns_destroy": (c_int, [c_vp]),
     "tlab_dns_set_fusion": (c_int, [c_vp, c_int]),
+    "tlab_dns_set_scalar_bounds": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), _dp, _dp]),
+    "tlab_slab_dns_set_scalar_bounds": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), _dp, _dp]),
+    "tlab_pencil_dns_set_scalar_bounds": (c_int, [c_vp, c_int, ctypes.POINTER(c_int), _dp, _dp]),
+    "tlab_pw_clip": (c_int, [c_vp, c_dbl, c_dbl, ctypes.c_longlong]),
+    "tlab_deferred_clip": (c_int, [ctypes.c_longlong, c_dbl, c_dbl, c_vp]),
+    "tlab_deferred_clip_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
+    "tlab_pointer_on_device": (c_int, [c_vp]),
     "tlab_dns_begin_step": (c_int, [c_vp]),
     "tlab_deferred_enable": (c_int, [c_int]),
     "tlab_deferred_rhs": (c_int, [c_vp, c_dbl, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),

@@ -28,7 +28,7 @@ import numpy as np
 
 from .lib import load, check, TlabError, c_vp
 from .operators import FdmPlan, _use_torch_stream, _ptr
-from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, DNS_BCS_NEUMANN, _bcs_arrays
+from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, DNS_BCS_NEUMANN, _bcs_arrays, _bounds_arrays
 from .parallel import LoopbackComm, DistComm, trp_k_forward, trp_k_backward, trp_i_forward, trp_i_backward
 
 
@@ -454,6 +454,11 @@ class NativePencilDns:
         fj0, fj1, sj0, sj1 = _bcs_arrays(self.nscal, velocity_jmin, velocity_jmax, scalar_jmin, scalar_jmax)
         ia = lambda v, m: (ctypes.c_int * max(m, 1))(*list(v)[:m])       # noqa: E731
         check(load().tlab_pencil_dns_set_bcs(self._h, ia(fj0, 3), ia(fj1, 3), ia(sj0, self.nscal), ia(sj1, self.nscal)), "tlab_pencil_dns_set_bcs")
+
+    def set_scalar_bounds(self, lo=None, hi=None, active=None):
+        """Scalar bounds limiting after the update of every substep, as Dns.set_scalar_bounds (None: off)."""
+        n, act, l, h = _bounds_arrays(lo, hi, active)
+        check(load().tlab_pencil_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_pencil_dns_set_scalar_bounds")
 
     def RHS_GLOBAL_INCOMPRESSIBLE_1(self, dte):
         _use_torch_stream()

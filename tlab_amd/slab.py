@@ -17,7 +17,7 @@ import numpy as np
 
 from .lib import load, check, TlabError, c_vp, c_int
 from .operators import FdmPlan, _use_torch_stream
-from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, _bcs_arrays
+from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, _bcs_arrays, _bounds_arrays
 
 _pp = ctypes.POINTER(c_vp)
 _pll = ctypes.POINTER(ctypes.c_longlong)
@@ -221,6 +221,11 @@ class NativeSlabDns:
         c0 = (ctypes.c_double * ns)(*[float(v) for v in (coupling_jmin or [0.0] * ns)][:ns])
         c1 = (ctypes.c_double * ns)(*[float(v) for v in (coupling_jmax or [0.0] * ns)][:ns])
         check(load().tlab_slab_dns_set_surface_bcs(self._h, s0, s1, c0, c1), "tlab_slab_dns_set_surface_bcs")
+
+    def set_scalar_bounds(self, lo=None, hi=None, active=None):
+        """Scalar bounds limiting after the update of every substep, as Dns.set_scalar_bounds (None: off)."""
+        n, act, l, h = _bounds_arrays(lo, hi, active)
+        check(load().tlab_slab_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_slab_dns_set_scalar_bounds")
 
     def set_remove_divergence(self, on):
         """dns.ini [Main] TermDivergence (as Dns.set_remove_divergence): off = the forcing of the pressure equation is div(hq) alone."""
