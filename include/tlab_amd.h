@@ -430,6 +430,17 @@ int tlab_dns_set_slab(tlab_dns_t d, int koffset);
 int tlab_time_courant(tlab_dns_t d, double *const *q, double cfla, double cfld, double *pmax, double *dtime);
 int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *tmp1);
 int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *amn, double *amx);
+/* DNS_BOUNDS_CONTROL with the location of its failure branch (tools/dns/dns_local.f90:157-230, incompressible / anelastic):
+ *   dil_min, dil_max = min / max of div(q) (= -FI_INVARIANT_P, logs_data(10:11)); loc_min, loc_max (int[3] each; NULL = not wanted) = the 1-based
+ *   (i, j, k) of the first occurrence in column-major order (Fortran minloc / maxloc), k offset by tlab_dns_set_slab.  q[3], txc[9]: HOST arrays
+ *   of DEVICE pointers; txc[0], txc[5], txc[6] are destroyed (and txc[2..4], which take rbackground * q, in anelastic runs, :160-162).  Staggered
+ *   runs (FI_INVARIANT_P_STAG): TLAB_EUNSUPPORTED.  Synchronises the stream.
+ * tlab_device_minmax: the local part of MINMAX (utils/minmax.f90:6) on any DEVICE array of n doubles (no driver). */
+int tlab_dns_dilatation_extremes(tlab_dns_t d, double *const *q, double *const *txc, double *dil_min, double *dil_max, int *loc_min, int *loc_max);
+int tlab_device_minmax(const double *a, long long n, double *amn, double *amx);
+/* tlab_minmax_any: the same for an array of either kind, classified by tlab_pointer_on_device: device memory -> the kernel, host memory (or no
+ * tlab_init) -> a host loop.  A host array never reaches a kernel. */
+int tlab_minmax_any(const double *a, long long n, double *amn, double *amx);
 
 /* RHS_GLOBAL_INCOMPRESSIBLE_1()   tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
  * it works on the module arrays q, s, hq, hs, txc and on dte).  q[3] = u,v,w; s[nscal]; hq[3], hs[nscal] are
@@ -525,6 +536,14 @@ int tlab_pencil_dns_rhs(tlab_pencil_dns_t d, double dte);                       
  * forward i" / "wait backward i"); the text of the last RHS is copied into buf (size bytes). */
 int tlab_pencil_dns_trace(tlab_pencil_dns_t d, int on, char *buf, int size);
 int tlab_pencil_dns_substep(tlab_pencil_dns_t d, double dte, double kco, int scale_tendencies);   /* + the update loops of time.f90:645-664, :272-297 */
+/* the monitors, as the slab forms below: TIME_COURANT (pmax, dtime equal on every rank; ds(1) indexed at i + ims_offset_i, ds(3) at k + ims_offset_k),
+ * DNS_BOUNDS_CONTROL's DilMin / DilMax and the extremes with their global location (as tlab_dns_dilatation_extremes; all ranks return the same
+ * values).  The x / z derivatives go through the I- / K-transpositions where those directions are split; txc[0], txc[1], txc[6], txc[7] are
+ * destroyed.  *_courant_local: pmax over the local ranks only, for a host whose own MPI_ALLREDUCE follows (time.f90:522). */
+int tlab_pencil_dns_time_courant(tlab_pencil_dns_t d, double cfla, double cfld, double *pmax, double *dtime);
+int tlab_pencil_dns_courant_local(tlab_pencil_dns_t d, double *pmax);
+int tlab_pencil_dns_dilatation_bounds(tlab_pencil_dns_t d, double *dil_min, double *dil_max);
+int tlab_pencil_dns_dilatation_extremes(tlab_pencil_dns_t d, double *dil_min, double *dil_max, int *loc_min, int *loc_max);
 
 typedef struct tlab_slab_dns *tlab_slab_dns_t;
 /* gx, gy: the local plans; gz: the plan of the GLOBAL z direction (nz_total nodes).  kmax = nz_total / nranks planes per rank; returns
@@ -570,6 +589,11 @@ int tlab_slab_dns_substep(tlab_slab_dns_t d, double dte, double kco, int scale_t
 int tlab_slab_dns_time_courant(tlab_slab_dns_t d, double cfla, double cfld, double *pmax, double *dtime);
 /* DNS_BOUNDS_CONTROL (tools/dns/dns_local.f90:157-187): extremes of div(q) over the whole box; destroys txc[0], txc[1] */
 int tlab_slab_dns_dilatation_bounds(tlab_slab_dns_t d, double *dil_min, double *dil_max);
+/* ... and with the global 1-based (i, j, k) of the first occurrence of each (as tlab_dns_dilatation_extremes; loc_* may be NULL): the value is
+ * all-reduced first, then the smallest global column-major index among the ranks that hold it.  Destroys txc[0], txc[6], txc[7]. */
+int tlab_slab_dns_dilatation_extremes(tlab_slab_dns_t d, double *dil_min, double *dil_max, int *loc_min, int *loc_max);
+/* TIME_COURANT's pmax[2] over the local ranks only, for a host whose own MPI_ALLREDUCE follows (time.f90:522) */
+int tlab_slab_dns_courant_local(tlab_slab_dns_t d, double *pmax);
 
 /* The pointwise loops of the RHS / RK update as separate calls (rhs_global_incompressible_1.f90:106-112, :197-201, :257-259,
  * :348-352, :279-280, :373-375; time.f90:645-664 + :272-297), for drivers that interleave communication. */

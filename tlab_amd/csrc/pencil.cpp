@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/tlab_amd.h"
+#include "monitor.hpp"
 
 extern hipStream_t tlab_current_stream();
 int tlab_internal_deferred_flush();      // deferred.cpp
@@ -31,6 +32,8 @@ extern bool tlab_device_ready();
 int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi);      // rhs.cpp
 extern "C" bool tlab_internal_anelastic();
 extern "C" bool tlab_internal_dealiasing();
+extern "C" int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff,
+                                         double *pmax);      // rhs.cpp
 
 namespace tlab {
 hipError_t launch_copy_blocks(int n, const double *const *src, double *const *dst, const long long *cnt, hipStream_t st);      // pointwise.hip
@@ -116,6 +119,7 @@ struct Rank {
     double *pen[3] = {nullptr, nullptr, nullptr}, *pack[2] = {nullptr, nullptr};
     std::vector<double *> q, s, hq, hs, txc;
     bool bound = false;
+    tlab_dns_t dns = nullptr;         // the tables of TIME_COURANT (ds(ig)%one_ov_ds1 of the global directions), made on first use
 };
 
 }  // namespace
@@ -148,6 +152,7 @@ struct tlab_pencil_dns {
     std::vector<Rank> rk;
     ~tlab_pencil_dns() {
         for (Rank &R : rk) {
+            if (R.dns) (void)tlab_dns_destroy(R.dns);
             if (R.poisson) (void)tlab_poisson_plan_destroy(R.poisson);
             for (double *p : {R.hb, R.ht, R.rt, R.u_t, R.w_t, R.ta, R.tb, R.wire, R.pen[0], R.pen[1], R.pen[2], R.pack[0], R.pack[1], R.rt2, R.wire2, R.wireb[0], R.wireb[1], R.tx})
                 if (p) (void)hipFree(p);
@@ -683,6 +688,78 @@ void rhs_overlapped(D *d, double dte) {
     finish_velocities(d);
 }
 
+// ---- monitors (TIME_COURANT, DNS_BOUNDS_CONTROL) ----
+tlab_dns_t dns_handle(D *d, Rank &R) {
+    if (!R.dns) {
+        const double one = 1.0;
+        ok(tlab_dns_create(&R.dns, d->g[0], d->g[1], d->g[2], R.poisson, d->imax, d->ny, d->kmax, d->nscal, d->visc, d->nscal ? d->schmidt.data() : &one),
+           "tlab_dns_create");
+    }
+    return R.dns;
+}
+// pmax over the local ranks; ds(1) and ds(3) are indexed at the global i, k (time.f90:402-410)
+void courant_local(D *d, double *pmax) {
+    need_bound(d);
+    pmax[0] = pmax[1] = 0.0;
+    for (Rank &R : d->rk) {
+        double v[2];
+        ok(tlab_internal_dns_courant(dns_handle(d, R), R.q[0], R.q[1], R.q[2], d->imax, d->ny, d->kmax, R.pi * d->imax, R.pk * d->kmax, v), "TIME_COURANT");
+        pmax[0] = std::max(pmax[0], v[0]);
+        pmax[1] = std::max(pmax[1], v[1]);
+    }
+}
+// div(q) = txc[0] (+ txc[1] where z is split: the K-transposition brings dw/dz back into a buffer of its own; the reduction adds the two);
+// returns whether txc[1] holds that second operand.  The accumulating forms of OPR_Partial put the y (and unsplit x, z) terms on txc[0].
+bool divergence(D *d) {
+    need_bound(d);
+    if (tlab_internal_anelastic() || tlab_internal_dealiasing())
+        throw Fail(TLAB_EUNSUPPORTED, "pencil monitors: the anelastic formulation / dealiasing filters are not built into the decomposed drivers");
+    const int nx = d->imax, ny = d->ny, kmax = d->kmax;
+    auto padd = [&](Rank &R, int dir, const double *u, int acc) {
+        ok(tlab_opr_partial_add(dir, d->g[dir - 1], nx, ny, kmax, 0, u, nullptr, 0.0, R.txc[0], acc, R.txc[6], R.txc[7]), "tlab_opr_partial_add");
+    };
+    if (d->npi == 1) {
+        for (Rank &R : d->rk) padd(R, 1, R.q[0], 0);
+    } else {      // opr_partial.f90:117-136
+        trp_i_forward(d, [](Rank &R) { return R.q[0]; }, [](Rank &R) { return R.ta; });
+        for (Rank &R : d->rk) partial(d, 1, d->nx, (int)d->nlx, 1, R.ta, R.rt);
+        trp_i_backward(d, [](Rank &R) { return R.rt; }, [](Rank &R) { return R.txc[0]; });
+    }
+    for (Rank &R : d->rk) padd(R, 2, R.q[1], 1);
+    if (d->npk == 1) {
+        for (Rank &R : d->rk) padd(R, 3, R.q[2], 1);
+        return false;
+    }
+    trp_k_forward(d, [](Rank &R) { return R.q[2]; }, [](Rank &R) { return R.ta; });      // opr_partial.f90:185-195
+    for (Rank &R : d->rk) partial(d, 3, (int)d->nlz, 1, d->nzt, R.ta, R.rt);
+    trp_k_backward(d, [](Rank &R) { return R.rt; }, [](Rank &R) { return R.txc[1]; });
+    return true;
+}
+// min / max of div(q) over all ranks and, if loc_* != NULL, the global 1-based (i, j, k) of their first occurrence
+void extremes(D *d, double *dil_min, double *dil_max, int *loc_min, int *loc_max) {
+    const bool two = divergence(d);
+    const int L = (int)d->rk.size();
+    std::vector<double> mn((size_t)L), mx((size_t)L), imn((size_t)L), imx((size_t)L);
+    for (int l = 0; l < L; ++l) {
+        Rank &R = d->rk[l];
+        long long a = 0, b = 0;
+        hk(tlab::monitor_extremes(R.txc[0], two ? R.txc[1] : nullptr, d->n, &mn[l], &mx[l], &a, &b, tlab_current_stream()), "k_extremes");
+        auto global = [&](long long e) {      // local (i, j, k) of the block -> global column-major index
+            const long long i = e % d->imax + (long long)R.pi * d->imax, j = (e / d->imax) % d->ny, k = e / ((long long)d->imax * d->ny) + (long long)R.pk * d->kmax;
+            return (double)(i + (long long)d->nx * (j + (long long)d->ny * k));
+        };
+        imn[l] = global(a);
+        imx[l] = global(b);
+    }
+    auto ar = [&](double *v, int n, int op) { return d->tr.allreduce(d->tr.ctx, v, n, op); };
+    tck(tlab::monitor_allreduce_extreme(ar, 1, mn, imn), "allreduce");
+    tck(tlab::monitor_allreduce_extreme(ar, 0, mx, imx), "allreduce");
+    *dil_min = mn[0];
+    *dil_max = mx[0];
+    tlab::monitor_ijk(imn[0], d->nx, d->ny, loc_min);
+    tlab::monitor_ijk(imx[0], d->nx, d->ny, loc_max);
+}
+
 template <class F>
 int guarded(F f) {
     try {
@@ -851,6 +928,48 @@ int tlab_pencil_dns_substep(tlab_pencil_dns_t d, double dte, double kco, int sca
                 else ok(tlab_pw_rk_update(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
             }
         }
+    });
+}
+
+int tlab_pencil_dns_courant_local(tlab_pencil_dns_t d, double *pmax) {
+    return guarded([&] {
+        if (!d || !pmax) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_courant_local: bad arguments");
+        courant_local(d, pmax);
+    });
+}
+
+// TIME_COURANT with the MPI_MAX of time.f90:522, as tlab_slab_dns_time_courant
+int tlab_pencil_dns_time_courant(tlab_pencil_dns_t d, double cfla, double cfld, double *pmax, double *dtime) {
+    return guarded([&] {
+        if (!d || !pmax) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_time_courant: bad arguments");
+        need_bound(d);
+        const int L = (int)d->rk.size();
+        std::vector<double> v((size_t)2 * L);
+        for (int l = 0; l < L; ++l) {
+            Rank &R = d->rk[l];
+            ok(tlab_internal_dns_courant(dns_handle(d, R), R.q[0], R.q[1], R.q[2], d->imax, d->ny, d->kmax, R.pi * d->imax, R.pk * d->kmax, &v[(size_t)2 * l]),
+               "TIME_COURANT");
+        }
+        tck(d->tr.allreduce(d->tr.ctx, v.data(), 2, 0), "allreduce");
+        pmax[0] = v[0]; pmax[1] = v[1];
+        if (dtime) {
+            const double dtc = pmax[0] > 0.0 ? cfla / pmax[0] : 1.0e300, dtd = pmax[1] > 0.0 ? cfld / pmax[1] : 1.0e300;
+            *dtime = cfla > 0.0 ? std::min(dtc, dtd) : 0.0;
+        }
+    });
+}
+
+int tlab_pencil_dns_dilatation_bounds(tlab_pencil_dns_t d, double *dil_min, double *dil_max) {
+    return guarded([&] {
+        if (!d || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_dilatation_bounds: bad arguments");
+        extremes(d, dil_min, dil_max, nullptr, nullptr);
+    });
+}
+
+int tlab_pencil_dns_dilatation_extremes(tlab_pencil_dns_t d, double *dil_min, double *dil_max, int *loc_min, int *loc_max) {
+    return guarded([&] {
+        if (!d || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_dilatation_extremes: bad arguments");
+        extremes(d, dil_min, dil_max, loc_min, loc_max);
     });
 }
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "monitor.hpp"
 #include "plan.hpp"
 
 using namespace tlab;
@@ -907,6 +908,79 @@ int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *a
         tlab_set_error(f.what());
         return f.code;
     }
+}
+
+// DNS_BOUNDS_CONTROL (dns_local.f90:157-230), incompressible and anelastic: div(q) accumulated into txc[0] by the three P1 derivatives, then one
+// reduction for min, max and their first locations.  Anelastic runs weight the velocities by rbackground first (:160-162, into txc[2..4]).
+int tlab_dns_dilatation_extremes(tlab_dns_t d, double *const *q, double *const *txc, double *dil_min, double *dil_max, int *loc_min, int *loc_max) {
+    try {
+        if (!d || !q || !txc || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_dns_dilatation_extremes: bad arguments");
+        if (d->stagger) throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_dilatation_extremes: FI_INVARIANT_P_STAG (staggered pressure) is not built on the device");
+        hipStream_t st = tlab_current_stream();      // (a recorded substep runs first: q is read below)
+        follow_anelastic(d);
+        const int nx = d->nx, ny = d->ny, nz = d->nz;
+        const long long n = (long long)nx * ny * nz;
+        const double *u = q[0], *v = q[1], *w = q[2];
+        if (d->rb) {      // Thermo_Anelastic_WEIGHT_OUTPLACE(.., rbackground, q(1, i), txc(1, 2 + i))
+            for (int i = 0; i < 3; ++i) hk(launch_weight_y(txc[2 + i], q[i], d->rb, nx, ny, n, 0, st), "k_weight_y");
+            u = txc[2]; v = txc[3]; w = txc[4];
+        }
+        ok(tlab_opr_partial_add(1, d->g[0], nx, ny, nz, 0, u, nullptr, 0.0, txc[0], 0, txc[5], txc[6]), "OPR_Partial_X");
+        ok(tlab_opr_partial_add(2, d->g[1], nx, ny, nz, 0, v, nullptr, 0.0, txc[0], 1, txc[5], txc[6]), "OPR_Partial_Y");
+        ok(tlab_opr_partial_add(3, d->g[2], nx, ny, nz, 0, w, nullptr, 0.0, txc[0], 1, txc[5], txc[6]), "OPR_Partial_Z");
+        long long imn = 0, imx = 0;
+        hk(monitor_extremes(txc[0], nullptr, n, dil_min, dil_max, &imn, &imx, st), "k_extremes");
+        auto loc = [&](long long e, int *ijk) {      // 1-based, k global (tlab_dns_set_slab)
+            if (!ijk) return;
+            ijk[0] = (int)(e % nx) + 1; ijk[1] = (int)((e / nx) % ny) + 1; ijk[2] = (int)(e / ((long long)nx * ny)) + 1 + d->koffset;
+        };
+        loc(imn, loc_min);
+        loc(imx, loc_max);
+        return TLAB_OK;
+    } catch (const Fail &f) {
+        tlab_set_error(f.what());
+        return f.code;
+    }
+}
+
+// the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
+int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff, double *pmax) {
+    try {
+        if (d->dx2i < 0.0) throw Fail(TLAB_EINVAL, "TIME_COURANT: the plans carry no Jacobian (tlab_fdm_plan_set_aux)");
+        hipStream_t st = tlab_current_stream();
+        hk(monitor_courant_max(u, v, w, d->od[0], d->od[1], d->od[2], nx, ny, nz, ioff, koff, d->nz_total > 1 ? 1 : 0, &pmax[0], st), "k_courant");
+        pmax[1] = d->schmidtfactor * d->dx2i;
+        return TLAB_OK;
+    } catch (const Fail &f) {
+        tlab_set_error(f.what());
+        return f.code;
+    }
+}
+
+// MINMAX (utils/minmax.f90:6), local part, of any device array: no driver needed
+int tlab_device_minmax(const double *a, long long n, double *amn, double *amx) {
+    try {
+        if (!a || n < 1 || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_device_minmax: bad arguments");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
+        hk(monitor_extremes(a, nullptr, n, amn, amx, nullptr, nullptr, tlab_current_stream()), "k_extremes");
+        return TLAB_OK;
+    } catch (const Fail &f) {
+        tlab_set_error(f.what());
+        return f.code;
+    }
+}
+
+// ... of an array of either kind (the drop-in MINMAX): device memory takes the kernel, host memory the host loop of minmax.f90 -- a host array
+// never reaches a kernel, a device array is never read by the host.  Without tlab_init no array is the library's: the host loop.
+int tlab_minmax_any(const double *a, long long n, double *amn, double *amx) {
+    if (!a || n < 1 || !amn || !amx) { tlab_set_error("tlab_minmax_any: bad arguments"); return TLAB_EINVAL; }
+    const int on = tlab_device_ready() ? tlab_pointer_on_device(a) : 0;
+    if (on < 0) return on;
+    if (on) return tlab_device_minmax(a, n, amn, amx);
+    double mn = a[0], mx = a[0];
+    for (long long i = 1; i < n; ++i) { mn = std::min(mn, a[i]); mx = std::max(mx, a[i]); }
+    *amn = mn; *amx = mx;
+    return TLAB_OK;
 }
 
 int tlab_dns_begin_step(tlab_dns_t d) {

@@ -13,6 +13,7 @@
 // The exchanges go through a tlab_slab_transport (include/tlab_amd.h): RCCL (comm.hip), the single-process loopback below, or the caller's own.
 // This file holds host logic only; every kernel is reached through the C ABI of the operator library, as a Fortran host would reach it.
 #include "../../include/tlab_amd.h"
+#include "monitor.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -900,22 +901,71 @@ int tlab_slab_dns_time_courant(tlab_slab_dns_t d, double cfla, double cfld, doub
     });
 }
 
+}  // extern "C"
+
+namespace {
+// div(q) into txc[0] of every local rank, the z-derivative by the slab route of the RHS (FI_INVARIANT_P = -div, fi_vectorcalculus.f90:111-141)
+void divergence(D *d) {
+    const int nx = d->nx, ny = d->ny, kmax = d->kmax;
+    int w = halo_start(d, 1, [&](Rank &R, int) { return Slot{R.q[2], 2}; });
+    for (Rank &R : d->rk) {
+        ok(tlab_opr_partial(1, d->g[0], TLAB_OPR_P1, nx, ny, kmax, 0, R.q[0], R.txc[0], nullptr), "tlab_opr_partial");
+        padd(d, R, 2, R.q[1], nullptr, 0.0, R.txc[0], 1);
+    }
+    twait(d, w);
+    for (Rank &R : d->rk) zpartial(d, R, 1, R.q[2], 2, nullptr, 0, 0.0, nullptr, 0);
+    w = msg_start(d, 1);
+    twait(d, w);
+    for (Rank &R : d->rk) zpartial(d, R, 2, R.q[2], 2, nullptr, 0, 0.0, R.txc[0], 1);
+}
+}  // namespace
+
+extern "C" {
+
+int tlab_slab_dns_dilatation_extremes(tlab_slab_dns_t d, double *dil_min, double *dil_max, int *loc_min, int *loc_max) {
+    return guarded([&] {
+        if (!d || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_slab_dns_dilatation_extremes: bad arguments");
+        need_bound(d);
+        refuse_unsupported_state("tlab_slab_dns_dilatation_extremes");
+        divergence(d);
+        const int L = (int)d->rk.size();
+        std::vector<double> mn((size_t)L), mx((size_t)L), imn((size_t)L), imx((size_t)L);
+        for (int l = 0; l < L; ++l) {
+            long long a = 0, b = 0;
+            hk(tlab::monitor_extremes(d->rk[l].txc[0], nullptr, d->n, &mn[l], &mx[l], &a, &b, tlab_current_stream()), "k_extremes");
+            imn[l] = (double)(a + d->rk[l].r * d->n);      // a slab is a contiguous range of the global column-major order
+            imx[l] = (double)(b + d->rk[l].r * d->n);
+        }
+        auto ar = [&](double *v, int n, int op) { return d->tr.allreduce(d->tr.ctx, v, n, op); };
+        tck(tlab::monitor_allreduce_extreme(ar, 1, mn, imn), "allreduce");
+        tck(tlab::monitor_allreduce_extreme(ar, 0, mx, imx), "allreduce");
+        *dil_min = mn[0];
+        *dil_max = mx[0];
+        tlab::monitor_ijk(imn[0], d->nx, d->ny, loc_min);
+        tlab::monitor_ijk(imx[0], d->nx, d->ny, loc_max);
+    });
+}
+
+int tlab_slab_dns_courant_local(tlab_slab_dns_t d, double *pmax) {
+    return guarded([&] {
+        if (!d || !pmax) throw Fail(TLAB_EINVAL, "tlab_slab_dns_courant_local: bad arguments");
+        need_bound(d);
+        pmax[0] = pmax[1] = 0.0;
+        for (Rank &R : d->rk) {
+            double v[2];
+            ok(tlab_time_courant(dns_handle(d, R), R.q.data(), 0.0, 0.0, v, nullptr), "tlab_time_courant");
+            pmax[0] = std::max(pmax[0], v[0]);
+            pmax[1] = std::max(pmax[1], v[1]);
+        }
+    });
+}
+
 int tlab_slab_dns_dilatation_bounds(tlab_slab_dns_t d, double *dil_min, double *dil_max) {
     return guarded([&] {
         if (!d || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_slab_dns_dilatation_bounds: bad arguments");
         need_bound(d);
         const int nx = d->nx, ny = d->ny, kmax = d->kmax, L = (int)d->rk.size();
-        // div(q) with the z-derivative by the slab route of the RHS (FI_INVARIANT_P = -div, fi_vectorcalculus.f90:111-141)
-        int w = halo_start(d, 1, [&](Rank &R, int) { return Slot{R.q[2], 2}; });
-        for (Rank &R : d->rk) {
-            ok(tlab_opr_partial(1, d->g[0], TLAB_OPR_P1, nx, ny, kmax, 0, R.q[0], R.txc[0], nullptr), "tlab_opr_partial");
-            padd(d, R, 2, R.q[1], nullptr, 0.0, R.txc[0], 1);
-        }
-        twait(d, w);
-        for (Rank &R : d->rk) zpartial(d, R, 1, R.q[2], 2, nullptr, 0, 0.0, nullptr, 0);
-        w = msg_start(d, 1);
-        twait(d, w);
-        for (Rank &R : d->rk) zpartial(d, R, 2, R.q[2], 2, nullptr, 0, 0.0, R.txc[0], 1);
+        divergence(d);
         std::vector<double> mn((size_t)L), mx((size_t)L);
         for (int l = 0; l < L; ++l) ok(tlab_minmax(dns_handle(d, d->rk[l]), d->rk[l].txc[0], nx, ny, kmax, &mn[l], &mx[l]), "tlab_minmax");
         tck(d->tr.allreduce(d->tr.ctx, mn.data(), 1, 1), "allreduce");

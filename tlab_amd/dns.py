@@ -57,6 +57,21 @@ def _bounds_arrays(lo, hi, active):
     return n, (ctypes.c_int * m)(*act), (ctypes.c_double * m)(*lo), (ctypes.c_double * m)(*hi)
 
 
+def _extremes(mn, mx, lmin, lmax, locations):
+    """(DilMin, DilMax[, (i, j, k) of the minimum, (i, j, k) of the maximum]) of the dilatation_extremes methods"""
+    if not locations:
+        return mn.value, mx.value
+    return mn.value, mx.value, tuple(lmin), tuple(lmax)
+
+
+def device_minmax(a):
+    """MINMAX's local part (utils/minmax.f90) of a contiguous float64 device tensor: (min, max)."""
+    _use_torch_stream()
+    mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    check(load().tlab_device_minmax(c_vp(a.data_ptr()), a.numel(), ctypes.byref(mn), ctypes.byref(mx)), "tlab_device_minmax")
+    return mn.value, mx.value
+
+
 def rk_coefficients(mode):
     """TIME_INITIALIZE, tools/dns/time.f90:86-108."""
     if mode == RKM_EXP3:   # Williamson 1980
@@ -215,6 +230,18 @@ class Dns:
         mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
         check(load().tlab_minmax(self._h, self.txc[0].data_ptr(), self.nx, self.ny, self.nz, ctypes.byref(mn), ctypes.byref(mx)), "tlab_minmax")
         return -mx.value, -mn.value
+
+    def dilatation_extremes(self, locations=True):
+        """DNS_BOUNDS_CONTROL with the location of its failure branch (dns_local.f90:157-230): (DilMin, DilMax) = min / max of div(q), and with
+        locations also the 1-based (i, j, k) of the first occurrence of each in Fortran order (minloc / maxloc).  Destroys txc[0], txc[5], txc[6]
+        (and txc[2..4] in anelastic runs, which weight q by rbackground first)."""
+        _use_torch_stream()
+        q, _, _, _, txc = self._arrays()
+        mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        lmin, lmax = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+        check(load().tlab_dns_dilatation_extremes(self._h, q, txc, ctypes.byref(mn), ctypes.byref(mx), lmin if locations else None,
+                                                   lmax if locations else None), "tlab_dns_dilatation_extremes")
+        return _extremes(mn, mx, lmin, lmax, locations)
 
     def begin_step(self):
         """hq = hs = 0 of TIME_RUNGEKUTTA (time.f90:212-216) without touching the arrays: the next substep overwrites them."""

@@ -204,6 +204,7 @@ program test_rk_driver
     use TLabMPI_VARS
     use TLabMPI_Transpose
     use TLab_AMD_C, only: tlab_sync, tlab_memcpy_d2h, TLab_AMD_Check, tlab_time_courant, tlab_deferred_stats
+    use TLab_AMD_Monitors, only: TLab_AMD_Courant, TLab_AMD_Dilatation
     use, intrinsic :: iso_c_binding
     implicit none
 
@@ -231,6 +232,12 @@ program test_rk_driver
     integer timing_stat
     integer(c_long_long) dstat(6)
     character(len=16) timing_env
+    ! TLAB_AMD_MONITORS=1: TIME_COURANT's pmax and DNS_BOUNDS_CONTROL's dilatation after every iteration (dns_main.f90:268, :273), one log line each,
+    ! and MINMAX once on a device and on a host copy of u at the end
+    logical monitors
+    integer mon_stat, dil_imn(3), dil_imx(3)
+    character(len=16) mon_env
+    real(wp) mon_pmax(2), dil_min, dil_max, mm(4)
 
     ! ###################################################################
     call TLab_Start()                                                          ! dns_main.f90:62
@@ -351,6 +358,8 @@ program test_rk_driver
     call get_environment_variable('TLAB_AMD_TIMING', timing_env, status=timing_stat)
     if (timing_stat == 0) read (timing_env, *, iostat=timing_stat) warm_iters
     if (timing_stat /= 0) warm_iters = -1
+    call get_environment_variable('TLAB_AMD_MONITORS', mon_env, status=mon_stat)
+    monitors = mon_stat == 0 .and. trim(mon_env) == '1'
     do while (itime < nitera_last)                                             ! :246-250
         if (warm_iters >= 0 .and. itime == nitera_first + warm_iters) then
             call TLab_AMD_Check(tlab_sync(), 'tlab_sync')
@@ -366,7 +375,24 @@ program test_rk_driver
         call TIME_RUNGEKUTTA()
         itime = itime + 1
         rtime = rtime + dtime
+        if (monitors) then
+            call TLab_AMD_Courant(mon_pmax)
+            call TLab_AMD_Dilatation(dil_min, dil_max, dil_imn, dil_imx)
+            write (sRes, '(a,i0,4(a,es23.16),a,6(1x,i0))') 'MONITORS: itime ', itime, ' CFL# ', dtime*mon_pmax(1), ' D# ', dtime*mon_pmax(2), &
+                ' DilMin ', dil_min, ' DilMax ', dil_max, ' at', dil_imn, dil_imx
+            call TLab_Write_ASCII(lfile, trim(sRes))
+        end if
     end do
+    if (monitors) then
+        call MINMAX(imax, jmax, kmax, q(1, 1), mm(1), mm(2))                    ! device memory: the kernel
+        allocate (h1(isize_field))
+        call TLab_AMD_Check(tlab_sync(), 'tlab_sync')
+        call TLab_AMD_Check(tlab_memcpy_d2h(c_loc(h1), c_loc(q(1, 1)), int(isize_field, c_size_t)*8_c_size_t), 'd2h')
+        call MINMAX(imax, jmax, kmax, h1, mm(3), mm(4))                        ! host memory: the host loop
+        deallocate (h1)
+        write (sRes, '(a,4(1x,es23.16))') 'MINMAX: device host', mm
+        call TLab_Write_ASCII(lfile, trim(sRes))
+    end if
     if (warm_iters >= 0 .and. nitera_last > nitera_first + warm_iters) then
         call TLab_AMD_Check(tlab_sync(), 'tlab_sync')
         call system_clock(clock1)

@@ -461,6 +461,42 @@ module TLab_AMD_C
             type(c_ptr), value :: d
             real(c_double), intent(out) :: dil_min, dil_max
         end function
+        ! the monitors of the main loop (TIME_COURANT, DNS_BOUNDS_CONTROL; module TLab_AMD_Monitors)
+        integer(c_int) function tlab_slab_dns_courant_local(d, pmax) bind(C, name='tlab_slab_dns_courant_local')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: d
+            real(c_double), intent(out) :: pmax(2)
+        end function
+        integer(c_int) function tlab_pencil_dns_courant_local(d, pmax) bind(C, name='tlab_pencil_dns_courant_local')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: d
+            real(c_double), intent(out) :: pmax(2)
+        end function
+        integer(c_int) function tlab_dns_dilatation_extremes(d, q, txc, dil_min, dil_max, loc_min, loc_max) bind(C, name='tlab_dns_dilatation_extremes')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: d
+            type(c_ptr), intent(in) :: q(*), txc(*)
+            real(c_double), intent(out) :: dil_min, dil_max
+            integer(c_int), intent(out) :: loc_min(3), loc_max(3)
+        end function
+        integer(c_int) function tlab_slab_dns_dilatation_extremes(d, dil_min, dil_max, loc_min, loc_max) bind(C, name='tlab_slab_dns_dilatation_extremes')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: d
+            real(c_double), intent(out) :: dil_min, dil_max
+            integer(c_int), intent(out) :: loc_min(3), loc_max(3)
+        end function
+        integer(c_int) function tlab_pencil_dns_dilatation_extremes(d, dil_min, dil_max, loc_min, loc_max) bind(C, name='tlab_pencil_dns_dilatation_extremes')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: d
+            real(c_double), intent(out) :: dil_min, dil_max
+            integer(c_int), intent(out) :: loc_min(3), loc_max(3)
+        end function
+        integer(c_int) function tlab_minmax_any(a, n, amn, amx) bind(C, name='tlab_minmax_any')
+            import :: c_int, c_ptr, c_double, c_long_long
+            type(c_ptr), value :: a
+            integer(c_long_long), value :: n
+            real(c_double), intent(out) :: amn, amx
+        end function
         integer(c_int) function tlab_boundary_bcs_neumann_y(plan, ibc, nx, ny, nz, u, bcs_hb, bcs_ht, tmp1) bind(C, name='tlab_boundary_bcs_neumann_y')
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, u, bcs_hb, bcs_ht, tmp1

@@ -104,6 +104,9 @@ SIGNATURES = {
     "tlab_time_courant": (c_int, [c_vp, ctypes.POINTER(c_vp), c_dbl, c_dbl, _dp, _dp]),
     "tlab_fi_invariant_p": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tlab_minmax": (c_int, [c_vp, c_vp, c_int, c_int, c_int, _dp, _dp]),
+    "tlab_dns_dilatation_extremes": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), _dp, _dp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tlab_device_minmax": (c_int, [c_vp, ctypes.c_longlong, _dp, _dp]),
+    "tlab_minmax_any": (c_int, [c_vp, ctypes.c_longlong, _dp, _dp]),
     "tlab_opr_burgers_add": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tlab_opr_burgers_add_n": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_int, _dp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_int]),
     "tlab_opr_partial_add": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_int, c_vp, c_vp]),
@@ -142,6 +145,12 @@ SIGNATURES = {
     "tlab_slab_dns_substep": (c_int, [c_vp, c_dbl, c_dbl, c_int]),
     "tlab_slab_dns_time_courant": (c_int, [c_vp, c_dbl, c_dbl, _dp, _dp]),
     "tlab_slab_dns_dilatation_bounds": (c_int, [c_vp, _dp, _dp]),
+    "tlab_slab_dns_dilatation_extremes": (c_int, [c_vp, _dp, _dp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "tlab_slab_dns_courant_local": (c_int, [c_vp, _dp]),
+    "tlab_pencil_dns_time_courant": (c_int, [c_vp, c_dbl, c_dbl, _dp, _dp]),
+    "tlab_pencil_dns_courant_local": (c_int, [c_vp, _dp]),
+    "tlab_pencil_dns_dilatation_bounds": (c_int, [c_vp, _dp, _dp]),
+    "tlab_pencil_dns_dilatation_extremes": (c_int, [c_vp, _dp, _dp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tlab_transpose": (c_int, [c_vp, c_int, c_int, c_vp]),
     "tlab_last_kernel_path": (c_int, []),
     "tlab_force_kernel_path": (c_int, [c_int]),

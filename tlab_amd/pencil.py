@@ -28,7 +28,7 @@ import numpy as np
 
 from .lib import load, check, TlabError, c_vp
 from .operators import FdmPlan, _use_torch_stream, _ptr
-from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, DNS_BCS_NEUMANN, _bcs_arrays, _bounds_arrays
+from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, DNS_BCS_NEUMANN, _bcs_arrays, _bounds_arrays, _extremes
 from .parallel import LoopbackComm, DistComm, trp_k_forward, trp_k_backward, trp_i_forward, trp_i_backward
 
 
@@ -475,6 +475,28 @@ class NativePencilDns:
             check(load().tlab_pencil_dns_begin_step(self._h), "tlab_pencil_dns_begin_step")
         last = s == self.rkm_endstep - 1
         self.TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT(dtime * self.kdt[s], 1.0 if last else self.kco[s], not last)
+
+    def TIME_COURANT(self, cfla, cfld):
+        """As NativeSlabDns.TIME_COURANT: ((pmax1, pmax2), dtime), the same on every rank."""
+        _use_torch_stream()
+        pmax, dt = (ctypes.c_double * 2)(), ctypes.c_double(0.0)
+        check(load().tlab_pencil_dns_time_courant(self._h, float(cfla), float(cfld), pmax, ctypes.byref(dt)), "tlab_pencil_dns_time_courant")
+        return (pmax[0], pmax[1]), dt.value
+
+    def dilatation_bounds(self):
+        _use_torch_stream()
+        mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(load().tlab_pencil_dns_dilatation_bounds(self._h, ctypes.byref(mn), ctypes.byref(mx)), "tlab_pencil_dns_dilatation_bounds")
+        return mn.value, mx.value
+
+    def dilatation_extremes(self, locations=True):
+        """As Dns.dilatation_extremes over all ranks; the (i, j, k) are global (i + ims_offset_i, k + ims_offset_k)."""
+        _use_torch_stream()
+        mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        lmin, lmax = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+        check(load().tlab_pencil_dns_dilatation_extremes(self._h, ctypes.byref(mn), ctypes.byref(mx), lmin if locations else None,
+                                                          lmax if locations else None), "tlab_pencil_dns_dilatation_extremes")
+        return _extremes(mn, mx, lmin, lmax, locations)
 
     def block_of(self, r, global_field):
         pi, pk = self.pro(r)

@@ -17,7 +17,7 @@ import numpy as np
 
 from .lib import load, check, TlabError, c_vp, c_int
 from .operators import FdmPlan, _use_torch_stream
-from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, _bcs_arrays, _bounds_arrays
+from .dns import rk_coefficients, RKM_EXP3, DNS_BCS_DIRICHLET, _bcs_arrays, _bounds_arrays, _extremes
 
 _pp = ctypes.POINTER(c_vp)
 _pll = ctypes.POINTER(ctypes.c_longlong)
@@ -258,6 +258,15 @@ class NativeSlabDns:
         mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
         check(load().tlab_slab_dns_dilatation_bounds(self._h, ctypes.byref(mn), ctypes.byref(mx)), "tlab_slab_dns_dilatation_bounds")
         return mn.value, mx.value
+
+    def dilatation_extremes(self, locations=True):
+        """As Dns.dilatation_extremes over all ranks; the (i, j, k) are global (k + ims_offset_k)."""
+        _use_torch_stream()
+        mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        lmin, lmax = (ctypes.c_int * 3)(), (ctypes.c_int * 3)()
+        check(load().tlab_slab_dns_dilatation_extremes(self._h, ctypes.byref(mn), ctypes.byref(mx), lmin if locations else None,
+                                                        lmax if locations else None), "tlab_slab_dns_dilatation_extremes")
+        return _extremes(mn, mx, lmin, lmax, locations)
 
     def scatter(self, name, idx, global_field):
         """global_field: flat tensor nx*ny*nz_total (x fastest); every local rank takes its planes."""
