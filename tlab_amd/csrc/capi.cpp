@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "internal.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -79,11 +80,7 @@ double *workspace(size_t n) {
 
 }  // namespace
 
-void tlab_internal_filter_1d(int dir, tlab_filter_t f, int nx, int ny, int nz, const double *u, double *result, hipStream_t st);      // filter.hip
-
-// hooks for the other translation units (poisson.hip, rhs.hip)
-int tlab_internal_deferred_flush();      // deferred.cpp: a recorded Runge-Kutta tail runs before anything else is enqueued (no-op unless tlab_deferred_enable)
-int tlab_internal_deferred_take_error();
+// hooks for the other translation units (internal.hpp)
 hipStream_t tlab_current_stream() {
     (void)tlab_internal_deferred_flush();
     return g_stream;
@@ -997,8 +994,6 @@ bool tlab_internal_gradient_final(int dir, tlab_fdm_plan_t g, int nx, int ny, in
     g_last_path = path;
     return true;
 }
-extern "C" bool tlab_internal_anelastic();      // (defined inside the extern "C" block below)
-extern "C" bool tlab_internal_dealiasing();
 // result += nu d2s - vel ds   (only when the fully fused Burgers kernels apply)
 bool tlab_internal_burgers_acc(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, double nu, const double *s, const double *vel,
                                double *result) {

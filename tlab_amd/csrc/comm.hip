@@ -20,10 +20,8 @@
 
 #include "../../include/tlab_amd.h"
 #include "../../include/tlab_amd_comm.h"
+#include "internal.hpp"      // tlab_current_stream, tlab_set_error, tlab_device_ready of libtlab_amd.so
 
-extern hipStream_t tlab_current_stream();
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
 
 namespace {
 

@@ -23,37 +23,30 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <vector>
 
-#include "../../include/tlab_amd.h"
+#include "driver_common.hpp"
 
-extern void tlab_set_error(const std::string &s);
-long long tlab_internal_dns_points(tlab_dns_t d);      // rhs.cpp
-int tlab_internal_dns_nscal(tlab_dns_t d);
-// the arrays a decomposed driver is bound to (one local rank: a Fortran / MPI host), slab.cpp / pencil.cpp; false: not bound, or several local ranks
-bool tlab_internal_slab_bound(tlab_slab_dns_t d, double *const **q, double *const **s, double *const **hq, double *const **hs, int *nscal, long long *n);
-bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, double *const **q, double *const **s, double *const **hq, double *const **hs, int *nscal, long long *n);
-// the drivers' own scalar bounds (tlab_*_set_scalar_bounds): rhs.cpp, slab.cpp, pencil.cpp
-bool tlab_internal_dns_has_bounds(tlab_dns_t d);
-bool tlab_internal_slab_has_bounds(tlab_slab_dns_t d);
-bool tlab_internal_pencil_has_bounds(tlab_pencil_dns_t d);
-void tlab_internal_dns_swap_bounds(tlab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
-void tlab_internal_slab_swap_bounds(tlab_slab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
-void tlab_internal_pencil_swap_bounds(tlab_pencil_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
+using tlab::ScalarBounds;
 
 namespace {
 struct Range { double *p; long long n; };
+// the driver behind a recorded RHS -- tlab_dns (one domain), tlab_slab_dns or tlab_pencil_dns, the same tail behind each of them: its three entry
+// points on its handle (and, one domain, on the arrays handed to the RHS) and its own scalar bounds
+struct Driver {
+    std::function<int()> begin_step;
+    std::function<int(double dte)> rhs;
+    std::function<int(double dte, double kco, int scale)> substep;
+    ScalarBounds *bounds = nullptr;
+};
 struct Pending {
     bool rhs = false;
-    int kind = 0;                                 // 0: tlab_dns (one domain), 1: tlab_slab_dns, 2: tlab_pencil_dns -- the same tail behind each of them
-    tlab_dns_t d = nullptr;
-    tlab_slab_dns_t slab = nullptr;
-    tlab_pencil_dns_t pencil = nullptr;
+    Driver drv;
     double dte = 0.0, kco = 1.0;
     int nf = 0;                                   // 3 + nscal
     long long n = 0;
-    std::vector<double *> q, s, hq, hs, txc;      // as handed to the RHS
     std::vector<double *> x, y;                   // per field: tendency, state
     std::vector<char> upd, scl;
     int nupd = 0, nscl = 0;
@@ -110,37 +103,31 @@ bool zeros_are_the_tendencies(const Pending &p) {
     return true;
 }
 
-int run_begin(const Pending &p) {
-    return p.kind == 0 ? tlab_dns_begin_step(p.d) : p.kind == 1 ? tlab_slab_dns_begin_step(p.slab) : tlab_pencil_dns_begin_step(p.pencil);
-}
-void swap_bounds(Pending &p, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
-    if (p.kind == 1) tlab_internal_slab_swap_bounds(p.slab, on, lo, hi);
-    else if (p.kind == 2) tlab_internal_pencil_swap_bounds(p.pencil, on, lo, hi);
-    else tlab_internal_dns_swap_bounds(p.d, on, lo, hi);
-}
-bool driver_has_bounds(const Pending &p) {
-    return p.kind == 1 ? tlab_internal_slab_has_bounds(p.slab) : p.kind == 2 ? tlab_internal_pencil_has_bounds(p.pencil) : tlab_internal_dns_has_bounds(p.d);
-}
 // the substep the record describes: its bounds are the recorded clips and nothing else (a driver's own bounds do not belong to RHS + DAXPY), put in
 // place for this one call and taken back
 int run_substep(Pending &p, double kco, int scale) {
-    std::vector<char> on;
-    std::vector<double> lo, hi;
-    if (p.nclp) { on = p.clp; lo = p.clo; hi = p.chi; }
-    swap_bounds(p, on, lo, hi);
-    int rc;
-    if (p.kind == 1) rc = tlab_slab_dns_substep(p.slab, p.dte, kco, scale);
-    else if (p.kind == 2) rc = tlab_pencil_dns_substep(p.pencil, p.dte, kco, scale);
-    else rc = tlab_time_substep_incompressible_explicit(p.d, p.dte, kco, scale, p.q.data(), p.s.empty() ? nullptr : p.s.data(), p.hq.data(),
-                                                        p.hs.empty() ? nullptr : p.hs.data(), p.txc.data());
-    swap_bounds(p, on, lo, hi);
+    ScalarBounds b;
+    if (p.nclp) { b.on = p.clp; b.lo = p.clo; b.hi = p.chi; }
+    p.drv.bounds->swap(b);
+    const int rc = p.drv.substep(p.dte, kco, scale);
+    p.drv.bounds->swap(b);
     return rc;
 }
-int run_rhs(Pending &p) {
-    if (p.kind == 1) return tlab_slab_dns_rhs(p.slab, p.dte);
-    if (p.kind == 2) return tlab_pencil_dns_rhs(p.pencil, p.dte);
-    return tlab_rhs_global_incompressible_1(p.d, p.dte, p.q.data(), p.s.empty() ? nullptr : p.s.data(), p.hq.data(), p.hs.empty() ? nullptr : p.hs.data(),
-                                            p.txc.data());
+
+// a new record: driver, step and the fields (tendency, state) the BLAS calls that follow are matched against; the zero fills recorded so far stay
+void record(Driver drv, double dte, int ns, long long n, double *const *q, double *const *s, double *const *hq, double *const *hs) {
+    Pending &p = g_p;
+    p.rhs = true;
+    p.drv = std::move(drv);
+    p.dte = dte; p.kco = 1.0;
+    p.nf = 3 + ns; p.n = n;
+    p.x.clear(); p.y.clear();
+    for (int i = 0; i < 3; ++i) { p.x.push_back(hq[i]); p.y.push_back(q[i]); }
+    for (int i = 0; i < ns; ++i) { p.x.push_back(hs[i]); p.y.push_back(s[i]); }
+    p.upd.assign(p.nf, 0); p.scl.assign(p.nf, 0);
+    p.nupd = p.nscl = 0;
+    p.clp.assign(ns, 0); p.clo.assign(ns, 0.0); p.chi.assign(ns, 0.0);
+    p.nclp = 0;
 }
 
 int flush_impl() {
@@ -152,7 +139,7 @@ int flush_impl() {
     int rc = TLAB_OK;
     if (zeros_are_the_tendencies(p)) {
         ++g_stat[2];
-        rc = run_begin(p);
+        rc = p.drv.begin_step();
     } else {
         for (const Range &r : p.zeros) {
             ++g_stat[5];
@@ -172,7 +159,7 @@ int flush_impl() {
             if (p.scl[f]) rc = tlab_pw_scale(p.x[f], p.kco, p.n);
         return rc;
     }
-    rc = run_rhs(p);
+    rc = p.drv.rhs(p.dte);
     for (int f = 0; f < p.nf && rc == TLAB_OK; ++f)
         if (p.upd[f]) rc = tlab_pw_rk_update(p.y[f], p.x[f], p.dte, 1.0, 0, p.n);
     for (int is = 0; is + 3 < p.nf && rc == TLAB_OK; ++is)          // (a clip was recorded after the DAXPY of its field only)
@@ -245,61 +232,50 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }
-    Pending &p = g_p;                    // (keeps the zero fills recorded so far)
-    p.rhs = true;
-    p.kind = 0; p.d = d; p.slab = nullptr; p.pencil = nullptr;
-    p.dte = dte; p.kco = 1.0;
-    p.nf = 3 + ns; p.n = tlab_internal_dns_points(d);
-    p.q.assign(q, q + 3); p.hq.assign(hq, hq + 3);
-    p.s.clear(); p.hs.clear();
-    if (ns > 0) { p.s.assign(s, s + ns); p.hs.assign(hs, hs + ns); }
-    p.txc.assign(txc, txc + 9);
-    p.x.clear(); p.y.clear();
-    for (int i = 0; i < 3; ++i) { p.x.push_back(hq[i]); p.y.push_back(q[i]); }
-    for (int i = 0; i < ns; ++i) { p.x.push_back(hs[i]); p.y.push_back(s[i]); }
-    p.upd.assign(p.nf, 0); p.scl.assign(p.nf, 0);
-    p.nupd = p.nscl = 0;
-    p.clp.assign(p.nf - 3, 0); p.clo.assign(p.nf - 3, 0.0); p.chi.assign(p.nf - 3, 0.0);
-    p.nclp = 0;
+    // the arrays stay with the record: this driver takes them with every call
+    const std::vector<double *> Q(q, q + 3), S(s, s + ns), HQ(hq, hq + 3), HS(hs, hs + ns), T(txc, txc + 9);
+    Driver drv;
+    drv.begin_step = [d] { return tlab_dns_begin_step(d); };
+    drv.rhs = [=](double dte_) {
+        return tlab_rhs_global_incompressible_1(d, dte_, Q.data(), ns ? S.data() : nullptr, HQ.data(), ns ? HS.data() : nullptr, T.data());
+    };
+    drv.substep = [=](double dte_, double kco, int scale) {
+        return tlab_time_substep_incompressible_explicit(d, dte_, kco, scale, Q.data(), ns ? S.data() : nullptr, HQ.data(), ns ? HS.data() : nullptr,
+                                                         T.data());
+    };
+    drv.bounds = tlab_internal_dns_bounds(d);
+    record(std::move(drv), dte, ns, tlab_internal_dns_points(d), q, s, hq, hs);
     return TLAB_OK;
 }
 
-// the same for the decomposed drivers: their arrays are bound (tlab_slab_dns_bind / tlab_pencil_dns_bind), so the call carries the handle and dte only
-static int deferred_decomposed(int kind, tlab_slab_dns_t slab, tlab_pencil_dns_t pencil, double dte) {
-    double *const *q = nullptr, *const *s = nullptr, *const *hq = nullptr, *const *hs = nullptr;
-    int ns = 0;
-    long long n = 0;
-    const bool okb = kind == 1 ? tlab_internal_slab_bound(slab, &q, &s, &hq, &hs, &ns, &n) : tlab_internal_pencil_bound(pencil, &q, &s, &hq, &hs, &ns, &n);
-    if (!g_on || !okb || !(dte > 0.0)) {      // off, or nothing to match the BLAS calls against (several local ranks): at once
+// the same for the decomposed drivers: their arrays are bound (tlab_slab_dns_bind / tlab_pencil_dns_bind), so the call carries the handle and dte only;
+// bound: tlab_internal_{slab,pencil}_bound found the arrays of the one local rank (b)
+static int deferred_decomposed(Driver drv, bool bound, const tlab_bound_fields &b, double dte) {
+    if (!g_on || !bound || !(dte > 0.0)) {      // off, or nothing to match the BLAS calls against (several local ranks): at once
         if (g_on) { const int rc = flush_impl(); if (rc != TLAB_OK) return rc; }
-        return kind == 1 ? tlab_slab_dns_rhs(slab, dte) : tlab_pencil_dns_rhs(pencil, dte);
+        return drv.rhs(dte);
     }
     if (g_p.rhs) {
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }
-    Pending &p = g_p;
-    p.rhs = true;
-    p.kind = kind; p.d = nullptr; p.slab = slab; p.pencil = pencil;
-    p.dte = dte; p.kco = 1.0;
-    p.nf = 3 + ns; p.n = n;
-    p.q.clear(); p.s.clear(); p.hq.clear(); p.hs.clear(); p.txc.clear();
-    p.x.clear(); p.y.clear();
-    for (int i = 0; i < 3; ++i) { p.x.push_back(hq[i]); p.y.push_back(q[i]); }
-    for (int i = 0; i < ns; ++i) { p.x.push_back(hs[i]); p.y.push_back(s[i]); }
-    p.upd.assign(p.nf, 0); p.scl.assign(p.nf, 0);
-    p.nupd = p.nscl = 0;
-    p.clp.assign(p.nf - 3, 0); p.clo.assign(p.nf - 3, 0.0); p.chi.assign(p.nf - 3, 0.0);
-    p.nclp = 0;
+    drv.bounds = b.bounds;
+    record(std::move(drv), dte, b.nscal, b.n, b.q, b.s, b.hq, b.hs);
     return TLAB_OK;
 }
 int tlab_deferred_slab_rhs(tlab_slab_dns_t d, double dte) {
     if (!d) { tlab_set_error("tlab_deferred_slab_rhs: null handle"); return TLAB_EINVAL; }
-    return deferred_decomposed(1, d, nullptr, dte);
+    tlab_bound_fields b{};
+    const bool bound = tlab_internal_slab_bound(d, &b);
+    return deferred_decomposed({[d] { return tlab_slab_dns_begin_step(d); }, [d](double dte_) { return tlab_slab_dns_rhs(d, dte_); },
+                                [d](double dte_, double kco, int scale) { return tlab_slab_dns_substep(d, dte_, kco, scale); }}, bound, b, dte);
 }
 int tlab_deferred_pencil_rhs(tlab_pencil_dns_t d, double dte) {
     if (!d) { tlab_set_error("tlab_deferred_pencil_rhs: null handle"); return TLAB_EINVAL; }
-    return deferred_decomposed(2, nullptr, d, dte);
+    tlab_bound_fields b{};
+    const bool bound = tlab_internal_pencil_bound(d, &b);
+    return deferred_decomposed({[d] { return tlab_pencil_dns_begin_step(d); }, [d](double dte_) { return tlab_pencil_dns_rhs(d, dte_); },
+                                [d](double dte_, double kco, int scale) { return tlab_pencil_dns_substep(d, dte_, kco, scale); }}, bound, b, dte);
 }
 
 int tlab_deferred_axpy(long long n, double a, const double *x, double *y) {
@@ -350,7 +326,7 @@ int tlab_deferred_clip(long long n, double lo, double hi, double *x) {
         tlab_set_error("tlab_deferred_clip: null array, n < 0, NaN bounds or lo > hi");
         return TLAB_EINVAL;
     }
-    if (g_on && g_p.rhs && g_p.nscl == 0 && n == g_p.n && !driver_has_bounds(g_p)) {
+    if (g_on && g_p.rhs && g_p.nscl == 0 && n == g_p.n && !g_p.drv.bounds->any()) {
         for (int is = 0; is + 3 < g_p.nf; ++is)
             if (g_p.y[3 + is] == x) {
                 if (!g_p.upd[3 + is] || g_p.clp[is]) break;       // before its DAXPY, or a second clip: literal

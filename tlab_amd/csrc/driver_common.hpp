@@ -1,0 +1,134 @@
+// What the three drivers (rhs.cpp: one domain, slab.cpp: z-slabs, pencil.cpp: x/z pencils) and zslab.hip share around their physics: the error
+// type and the guards of their entry points, and the state and argument checks that do not depend on the decomposition.  Header-only, host code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "internal.hpp"
+
+namespace tlab {
+
+struct Fail : std::runtime_error {
+    int code;
+    Fail(int c, const std::string &s) : std::runtime_error(s), code(c) {}
+};
+inline void ok(int rc, const char *what) {
+    if (rc != TLAB_OK) throw Fail(rc, std::string(what) + ": " + tlab_last_error());
+}
+inline void hk(hipError_t e, const char *what) {
+    if (e != hipSuccess) throw Fail(TLAB_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The body of an entry point: a Fail becomes its code, with its text in tlab_last_error().  Any other std::exception becomes `other`; with
+// TLAB_OK it is not caught (the entry points whose bodies throw nothing but Fail).
+template <class F>
+int catch_fail(F f, int other = TLAB_OK) {
+    try {
+        f();
+        return TLAB_OK;
+    } catch (const Fail &e) {
+        tlab_set_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        if (other == TLAB_OK) throw;
+        tlab_set_error(e.what());
+        return other;
+    }
+}
+// ... of an entry point that is refused before tlab_init
+template <class F>
+int guarded(F f) {
+    return catch_fail([&] {
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
+        f();
+    }, TLAB_EINVAL);
+}
+
+// n doubles (at least one) of device memory, zeroed by a blocking hipMemset or -- on_stream -- by hipMemsetAsync on the library's current stream
+inline double *dalloc(size_t n, bool on_stream) {
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(double);
+    double *p = nullptr;
+    hk(hipMalloc((void **)&p, bytes), "hipMalloc");
+    hk(on_stream ? hipMemsetAsync(p, 0, bytes, tlab_current_stream()) : hipMemset(p, 0, bytes), "hipMemset");
+    return p;
+}
+
+// [Control] ScalLimit: DNS_BOUNDS_LIMIT (dns_local.f90:67-90) after the update of every substep, s = min(max(s, lo), hi) for the active scalars
+struct ScalarBounds {
+    std::vector<char> on;      // per scalar; empty: no scalar is limited (the kernels of a run without bounds)
+    std::vector<double> lo, hi;
+    bool any() const { return !on.empty(); }
+    bool active(int is) const { return !on.empty() && on[is]; }
+    void swap(ScalarBounds &o) { on.swap(o.on); lo.swap(o.lo); hi.swap(o.hi); }
+    // false (nothing changed, the reason in tlab_last_error()): see tlab_internal_check_bounds
+    bool set(const char *who, int nscal, int n, const int *active_, const double *lo_, const double *hi_) {
+        ScalarBounds b;
+        if (!tlab_internal_check_bounds(who, nscal, n, active_, lo_, hi_, b.on, b.lo, b.hi)) return false;
+        swap(b);
+        return true;
+    }
+};
+// tlab_*_set_scalar_bounds of a driver D with members nscal and bounds
+template <class D>
+int set_scalar_bounds(const char *who, D *d, int n, const int *active, const double *lo, const double *hi) {
+    (void)tlab_internal_deferred_flush();
+    if (!d) { tlab_set_error(std::string(who) + ": null handle"); return TLAB_EINVAL; }
+    return d->bounds.set(who, d->nscal, n, active, lo, hi) ? TLAB_OK : TLAB_EINVAL;
+}
+
+// BcsFlowJmin/Jmax%type of u, v, w and BcsScalJmin/Jmax%type of the scalars (TLAB_DNS_BCS_*)
+struct WallBcs {
+    int flow_jmin[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
+    int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
+    std::vector<int> scal_jmin, scal_jmax;
+    void all_dirichlet(int nscal) {
+        scal_jmin.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
+        scal_jmax.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
+    }
+    // tlab_*_set_bcs (who = the entry point): throws, and leaves the types as they were, unless every type is valid
+    void set(const std::string &who, int nscal, const int *fmin, const int *fmax, const int *smin, const int *smax) {
+        if (!fmin || !fmax || (nscal > 0 && (!smin || !smax))) throw Fail(TLAB_EINVAL, who + ": bad arguments");
+        auto valid = [](int t) { return t == TLAB_DNS_BCS_DIRICHLET || t == TLAB_DNS_BCS_NEUMANN; };
+        for (int i = 0; i < 3; ++i)
+            if (!valid(fmin[i]) || !valid(fmax[i])) throw Fail(TLAB_EINVAL, who + ": type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN");
+        for (int i = 0; i < nscal; ++i)
+            if (!valid(smin[i]) || !valid(smax[i])) throw Fail(TLAB_EINVAL, who + ": type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN");
+        if (fmin[1] != TLAB_DNS_BCS_DIRICHLET || fmax[1] != TLAB_DNS_BCS_DIRICHLET)
+            throw Fail(TLAB_EUNSUPPORTED, who + ": the wall-normal velocity must be Dirichlet (impermeable walls; the pressure BCs assume v = 0)");
+        for (int i = 0; i < 3; ++i) { flow_jmin[i] = fmin[i]; flow_jmax[i] = fmax[i]; }
+        for (int i = 0; i < nscal; ++i) { scal_jmin[i] = smin[i]; scal_jmax[i] = smax[i]; }
+    }
+};
+
+// tlab_*_bind of the decomposed drivers: the module arrays of one local rank R (members q, s, hq, hs, txc, bound); no entry may be null (the
+// first kernel would dereference it)
+template <class R>
+void bind_arrays(const std::string &who, int nscal, R &rank, double *const *q, double *const *s, double *const *hq, double *const *hs,
+                 double *const *txc) {
+    if (!q || !hq || !txc || (nscal > 0 && (!s || !hs))) throw Fail(TLAB_EINVAL, who + ": bad arguments");
+    rank.q.assign(q, q + 3); rank.hq.assign(hq, hq + 3); rank.txc.assign(txc, txc + 9);
+    rank.s.assign(s, s + nscal); rank.hs.assign(hs, hs + nscal);
+    for (const std::vector<double *> *v : {&rank.q, &rank.s, &rank.hq, &rank.hs, &rank.txc})
+        for (double *p : *v)
+            if (!p) throw Fail(TLAB_EINVAL, who + ": null array");
+    rank.bound = true;
+}
+// tlab_internal_{slab,pencil}_bound of a driver D with members rk (its local ranks), nscal, n and bounds
+template <class D>
+bool bound_fields(D *d, tlab_bound_fields *out) {
+    if (!d || d->rk.size() != 1 || !d->rk[0].bound) return false;
+    *out = {d->rk[0].q.data(), d->rk[0].s.data(), d->rk[0].hq.data(), d->rk[0].hs.data(), d->nscal, d->n, &d->bounds};
+    return true;
+}
+
+// time.f90:523-538, explicit RK: the smaller of the advective and the diffusive limit of pmax (TIME_COURANT); 0 without a CFL number
+inline double courant_dtime(double cfla, double cfld, const double *pmax) {
+    const double dtc = pmax[0] > 0.0 ? cfla / pmax[0] : 1.0e300, dtd = pmax[1] > 0.0 ? cfld / pmax[1] : 1.0e300;
+    return cfla > 0.0 ? std::min(dtc, dtd) : 0.0;
+}
+
+}  // namespace tlab

@@ -13,14 +13,11 @@
 #include <vector>
 
 #include "../../include/tlab_amd.h"
+#include "internal.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "profile.hpp"
 
-extern "C" void tlab_internal_dealiasing_forget(tlab_filter_t f);      // capi.cpp
-extern hipStream_t tlab_current_stream();
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
 
 using namespace tlab;
 

@@ -191,6 +191,10 @@ hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double 
                            hipStream_t stream, const ClipBounds *clip = nullptr);
 hipError_t launch_sub2(double *o, const double *a, const double *b, long long n, hipStream_t st);
 hipError_t launch_copy_blocks(int n, const double *const *src, double *const *dst, const long long *cnt, hipStream_t st);      // n device copies, batched launches
+hipError_t launch_plane_avg(const double *t, int j, int nx, int ny, int nz, double *avg, hipStream_t st);
+hipError_t launch_surface_flux_avg(double *ref, const double *t, int j, double sign, double diff, double cpl, double avg, int nx, int ny, int nz,
+                                   hipStream_t st);
+hipError_t launch_trp_copy(double *S, double *W, long long m, int P, long long c, int to_wire, hipStream_t st);
 hipError_t launch_neumann_planes(const double *u, const double *du, const double *cb, const double *ct, int do_b, int do_t, double *hb,
                                  double *ht, int nx, int ny, int nz, hipStream_t st);
 

@@ -18,46 +18,18 @@
 #include <cstring>
 #include <functional>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "../../include/tlab_amd.h"
+#include "driver_common.hpp"
+#include "kernels.hpp"
 #include "monitor.hpp"
 
-extern hipStream_t tlab_current_stream();
-int tlab_internal_deferred_flush();      // deferred.cpp
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
-int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi);      // rhs.cpp
-extern "C" bool tlab_internal_anelastic();
-extern "C" bool tlab_internal_dealiasing();
-extern "C" int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff,
-                                         double *pmax);      // rhs.cpp
-
-namespace tlab {
-hipError_t launch_copy_blocks(int n, const double *const *src, double *const *dst, const long long *cnt, hipStream_t st);      // pointwise.hip
-hipError_t launch_trp_copy(double *S, double *W, long long m, int P, long long c, int to_wire, hipStream_t st);
-}
+using namespace tlab;
 
 namespace {
 
-struct Fail : std::runtime_error {
-    int code;
-    Fail(int c, const std::string &s) : std::runtime_error(s), code(c) {}
-};
-void ok(int rc, const char *what) {
-    if (rc != TLAB_OK) throw Fail(rc, std::string(what) + ": " + tlab_last_error());
-}
-void hk(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw Fail(TLAB_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-double *dalloc(size_t n) {
-    double *p = nullptr;
-    hk(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(double)), "hipMalloc");
-    hk(hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(double), tlab_current_stream()), "hipMemset");
-    return p;
-}
+double *dalloc(size_t n) { return tlab::dalloc(n, true); }
 
 // ---- loopback transport: all npro_i x npro_k ranks in this process ----------------------------------------------------------------------------
 struct Loopback {
@@ -124,9 +96,6 @@ struct Rank {
 
 }  // namespace
 
-bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
-                                std::vector<double> &blo, std::vector<double> &bhi);      // rhs.cpp
-
 struct tlab_pencil_dns {
     tlab_pencil_transport tr{};
     tlab_fdm_plan_t g[3] = {nullptr, nullptr, nullptr};
@@ -135,12 +104,9 @@ struct tlab_pencil_dns {
     double visc = 0.0;
     std::vector<double> schmidt;
     std::vector<int> nxl, ioff;
-    int flow_jmin[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
-    int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
-    std::vector<int> scal_jmin, scal_jmax;
+    WallBcs bcs;
     bool fresh = false;
-    std::vector<char> clip_on;                    // [Control] ScalLimit: DNS_BOUNDS_LIMIT after the update of every substep (empty: no scalar limited)
-    std::vector<double> clip_lo, clip_hi;
+    ScalarBounds bounds;
     bool overlap = true;              // rhs_overlapped (exchanges started ahead of independent launches) instead of the literal sequence; TLAB_PENCIL_OVERLAP=0
     // tlab_pencil_dns_substep: the velocities are finished by ONE pass each behind the pressure gradient (h -= dp/dx_i, zero wall planes, q += dte h,
     // h *= kco: k_final_update, the arithmetic of k_sub3 + k_set_wall_planes + k_rk_update in the same order) where all their walls are Dirichlet;
@@ -343,7 +309,7 @@ void finish_velocities(D *d) {
     const long long n = d->n;
     static const bool fused_ok = [] { const char *e = getenv("TLAB_PENCIL_FINAL"); return !(e && atoi(e) == 0); }();
     bool dirichlet = true;
-    for (int i = 0; i < 3; ++i) dirichlet = dirichlet && d->flow_jmin[i] != TLAB_DNS_BCS_NEUMANN && d->flow_jmax[i] != TLAB_DNS_BCS_NEUMANN;
+    for (int i = 0; i < 3; ++i) dirichlet = dirichlet && d->bcs.flow_jmin[i] != TLAB_DNS_BCS_NEUMANN && d->bcs.flow_jmax[i] != TLAB_DNS_BCS_NEUMANN;
     d->fin.done = false;
     if (d->fin.on && fused_ok && dirichlet) {
         for (Rank &R : d->rk)
@@ -355,7 +321,7 @@ void finish_velocities(D *d) {
     for (Rank &R : d->rk) ok(tlab_pw_sub3(R.hq[0], R.hq[1], R.hq[2], R.txc[1], R.txc[2], R.txc[3], n), "tlab_pw_sub3");
     for (Rank &R : d->rk)
         for (int i = 0; i < 3; ++i) {
-            const int ibc = (d->flow_jmin[i] == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (d->flow_jmax[i] == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
+            const int ibc = (d->bcs.flow_jmin[i] == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (d->bcs.flow_jmax[i] == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
             if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, R.hq[i], R.hb, R.ht, R.txc[0]), "tlab_boundary_bcs_neumann_y");
             ok(tlab_pw_set_wall_planes(R.hq[i], (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
         }
@@ -416,7 +382,7 @@ void rhs(D *d, double dte) {
             if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, h, R.hb, R.ht, R.txc[0]), "tlab_boundary_bcs_neumann_y");
             ok(tlab_pw_set_wall_planes(h, (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
         };
-        for (int i = 0; i < ns; ++i) walls(R.hs[i], d->scal_jmin[i], d->scal_jmax[i]);
+        for (int i = 0; i < ns; ++i) walls(R.hs[i], d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]);
     }
 }
 
@@ -678,7 +644,7 @@ void rhs_overlapped(D *d, double dte) {
         for (int i = 0; i < ns; ++i)
             pl.push_back({-1, [=]() {
                 for (Rank &R : d->rk) {
-                    const int ibc = (d->scal_jmin[i] == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (d->scal_jmax[i] == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
+                    const int ibc = (d->bcs.scal_jmin[i] == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (d->bcs.scal_jmax[i] == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
                     if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, R.hs[i], R.hb, R.ht, R.txc[4]), "tlab_boundary_bcs_neumann_y");
                     ok(tlab_pw_set_wall_planes(R.hs[i], (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
                 }
@@ -760,21 +726,6 @@ void extremes(D *d, double *dil_min, double *dil_max, int *loc_min, int *loc_max
     tlab::monitor_ijk(imx[0], d->nx, d->ny, loc_max);
 }
 
-template <class F>
-int guarded(F f) {
-    try {
-        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
-        f();
-        return TLAB_OK;
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -814,8 +765,7 @@ int tlab_pencil_dns_create(tlab_pencil_dns_t *out, const tlab_pencil_transport *
         d->npage_k = (long long)imax * ny; d->nlz = d->npage_k / npk;
         d->isize_txc = (long long)(nx + 2) * ny * d->kmax2;
         if (nscal) d->schmidt.assign(schmidt, schmidt + nscal);
-        d->scal_jmin.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
-        d->scal_jmax.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
+        d->bcs.all_dirichlet(nscal);
         const int base = d->nxh / P, rem = d->nxh % P;
         for (int r = 0; r < P; ++r) { d->nxl.push_back(base + (r < rem ? 1 : 0)); d->ioff.push_back(r * base + std::min(r, rem)); }
         d->rk.resize(tr->nlocal);
@@ -843,14 +793,8 @@ int tlab_pencil_dns_destroy(tlab_pencil_dns_t d) {
 
 int tlab_pencil_dns_bind(tlab_pencil_dns_t d, int l, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc) {
     return guarded([&] {
-        if (!d || l < 0 || l >= (int)d->rk.size() || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs))) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_bind: bad arguments");
-        Rank &R = d->rk[l];
-        R.q.assign(q, q + 3); R.hq.assign(hq, hq + 3); R.txc.assign(txc, txc + 9);
-        R.s.assign(s, s + d->nscal); R.hs.assign(hs, hs + d->nscal);
-        for (double *p : R.q) if (!p) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_bind: null array");
-        for (double *p : R.hq) if (!p) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_bind: null array");
-        for (double *p : R.txc) if (!p) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_bind: null array");
-        R.bound = true;
+        if (!d || l < 0 || l >= (int)d->rk.size()) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_bind: bad arguments");
+        bind_arrays("tlab_pencil_dns_bind", d->nscal, d->rk[l], q, s, hq, hs, txc);
     });
 }
 
@@ -869,16 +813,8 @@ long long tlab_pencil_dns_info(tlab_pencil_dns_t d, int what) {
 
 int tlab_pencil_dns_set_bcs(tlab_pencil_dns_t d, const int *flow_jmin, const int *flow_jmax, const int *scal_jmin, const int *scal_jmax) {
     return guarded([&] {
-        if (!d || !flow_jmin || !flow_jmax || (d->nscal > 0 && (!scal_jmin || !scal_jmax))) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_set_bcs: bad arguments");
-        auto valid = [](int t) { return t == TLAB_DNS_BCS_DIRICHLET || t == TLAB_DNS_BCS_NEUMANN; };
-        for (int i = 0; i < 3; ++i)
-            if (!valid(flow_jmin[i]) || !valid(flow_jmax[i])) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_set_bcs: type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN");
-        for (int i = 0; i < d->nscal; ++i)
-            if (!valid(scal_jmin[i]) || !valid(scal_jmax[i])) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_set_bcs: type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN");
-        if (flow_jmin[1] != TLAB_DNS_BCS_DIRICHLET || flow_jmax[1] != TLAB_DNS_BCS_DIRICHLET)
-            throw Fail(TLAB_EUNSUPPORTED, "tlab_pencil_dns_set_bcs: the wall-normal velocity must be Dirichlet (impermeable walls; the pressure BCs assume v = 0)");
-        for (int i = 0; i < 3; ++i) { d->flow_jmin[i] = flow_jmin[i]; d->flow_jmax[i] = flow_jmax[i]; }
-        for (int i = 0; i < d->nscal; ++i) { d->scal_jmin[i] = scal_jmin[i]; d->scal_jmax[i] = scal_jmax[i]; }
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_set_bcs: bad arguments");
+        d->bcs.set("tlab_pencil_dns_set_bcs", d->nscal, flow_jmin, flow_jmax, scal_jmin, scal_jmax);
     });
 }
 
@@ -923,8 +859,8 @@ int tlab_pencil_dns_substep(tlab_pencil_dns_t d, double dte, double kco, int sca
         for (Rank &R : d->rk) {      // time.f90:645-664, :272-297
             for (int i = 0; i < 3 && !d->fin.done; ++i) ok(tlab_pw_rk_update(R.q[i], R.hq[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
             for (int i = 0; i < d->nscal; ++i) {      // (+ DNS_BOUNDS_LIMIT, dns_local.f90:67-90, in the same pass where the scalar is limited)
-                if (!d->clip_on.empty() && d->clip_on[i])
-                    ok(tlab_internal_pw_rk_update_clip(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n, d->clip_lo[i], d->clip_hi[i]), "tlab_pw_rk_update (bounds)");
+                if (d->bounds.active(i))
+                    ok(tlab_internal_pw_rk_update_clip(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n, d->bounds.lo[i], d->bounds.hi[i]), "tlab_pw_rk_update (bounds)");
                 else ok(tlab_pw_rk_update(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
             }
         }
@@ -952,10 +888,7 @@ int tlab_pencil_dns_time_courant(tlab_pencil_dns_t d, double cfla, double cfld, 
         }
         tck(d->tr.allreduce(d->tr.ctx, v.data(), 2, 0), "allreduce");
         pmax[0] = v[0]; pmax[1] = v[1];
-        if (dtime) {
-            const double dtc = pmax[0] > 0.0 ? cfla / pmax[0] : 1.0e300, dtd = pmax[1] > 0.0 ? cfld / pmax[1] : 1.0e300;
-            *dtime = cfla > 0.0 ? std::min(dtc, dtd) : 0.0;
-        }
+        if (dtime) *dtime = courant_dtime(cfla, cfld, pmax);
     });
 }
 
@@ -974,26 +907,9 @@ int tlab_pencil_dns_dilatation_extremes(tlab_pencil_dns_t d, double *dil_min, do
 }
 
 int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi) {
-    (void)tlab_internal_deferred_flush();
-    if (!d) { tlab_set_error("tlab_pencil_dns_set_scalar_bounds: null handle"); return TLAB_EINVAL; }
-    std::vector<char> on;
-    std::vector<double> blo, bhi;
-    if (!tlab_internal_check_bounds("tlab_pencil_dns_set_scalar_bounds", d->nscal, n, active, lo, hi, on, blo, bhi)) return TLAB_EINVAL;
-    d->clip_on.swap(on); d->clip_lo.swap(blo); d->clip_hi.swap(bhi);
-    return TLAB_OK;
+    return set_scalar_bounds("tlab_pencil_dns_set_scalar_bounds", d, n, active, lo, hi);
 }
 
 }  // extern "C"
 
-// deferred.cpp: the arrays of the ONE local rank of a Fortran / MPI host
-bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, double *const **q, double *const **s, double *const **hq, double *const **hs, int *nscal, long long *n) {
-    if (!d || d->rk.size() != 1 || !d->rk[0].bound) return false;
-    *q = d->rk[0].q.data(); *s = d->rk[0].s.data(); *hq = d->rk[0].hq.data(); *hs = d->rk[0].hs.data();
-    *nscal = d->nscal; *n = d->n;
-    return true;
-}
-// deferred.cpp: does the driver limit scalars of its own?  And the bounds of a recorded substep, put in place for the one fused call and taken back
-bool tlab_internal_pencil_has_bounds(tlab_pencil_dns_t d) { return d && !d->clip_on.empty(); }
-void tlab_internal_pencil_swap_bounds(tlab_pencil_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
-    d->clip_on.swap(on); d->clip_lo.swap(lo); d->clip_hi.swap(hi);
-}
+bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, tlab_bound_fields *out) { return bound_fields(d, out); }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/tlab_amd.h"
+#include "internal.hpp"
 #include "plan.hpp"
 #include "fftz.hpp"
 #include "poisson_host.hpp"
@@ -2759,12 +2760,7 @@ void build_low_modes(tlab_poisson_plan &P, const std::vector<double> &nodes, con
 
 }  // namespace
 
-extern hipStream_t tlab_current_stream();
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
-
 bool tlab_internal_poisson_has_own_x(tlab_poisson_plan_t P) { return P && P->fx_own; }
-bool tlab_internal_poisson_can_v_final(tlab_poisson_plan_t P);
 
 extern "C" {
 

@@ -356,8 +356,8 @@ void int2_build_tables(const DerTables &g, const std::vector<double> &x, int ibc
 // include/tlab_amd.h: debug aid (host only)
 #include "../../include/tlab_amd.h"
 #include "int1_generic.hpp"
+#include "internal.hpp"
 #include "plan.hpp"
-extern void tlab_set_error(const std::string &s);
 extern "C" int tlab_debug_int1_tables(tlab_fdm_plan_t gy, int ibc, int nm, const double *lam, double *fac, double *rb, double *rt, double *R) {
     try {
         if (!gy || !lam || !fac || !rb || !rt || !R || nm < 1 || (ibc != 1 && ibc != 2)) throw std::runtime_error("tlab_debug_int1_tables: bad arguments");

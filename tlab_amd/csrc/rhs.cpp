@@ -10,43 +10,16 @@
 #include <cmath>
 #include <cstdlib>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <functional>
 #include <vector>
 
+#include "driver_common.hpp"
 #include "kernels.hpp"
 #include "monitor.hpp"
 #include "plan.hpp"
 
 using namespace tlab;
-
-extern hipStream_t tlab_current_stream();
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
-int tlab_internal_deferred_flush();      // deferred.cpp: a recorded substep runs before the driver's state changes under it
-bool tlab_internal_partial_p1_fused(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, const double *u, const double *ub,
-                                    double scale, double *result, bool acc);
-bool tlab_internal_partial_p1_fusable(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
-bool tlab_internal_burgers_acc(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, double nu, const double *s, const double *vel,
-                               double *result);
-bool tlab_internal_gradient_final(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, const double *p, double *q, double *h, double dte,
-                                  double kco, int scale, const double *pb = nullptr, const double *pt = nullptr);
-bool tlab_internal_burgers_fusable(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
-extern "C" bool tlab_internal_dealiasing();      // capi.cpp (defined inside its extern "C" block)
-extern "C" int tlab_internal_anelastic_state(const double **rb, const double **rib, unsigned long *version);
-bool tlab_internal_poisson_can_v_final(tlab_poisson_plan_t P);                                                      // poisson.hip
-void tlab_internal_poisson_arm_v_final(tlab_poisson_plan_t P, double *q, double *h, double dte, double kco, int scale);
-bool tlab_internal_burgers_can_finish(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
-bool tlab_internal_burgers_acc_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, int nf, const double *nu, const double *const *s,
-                                 const double *vel, double *const *result, bool overwrite, const int *finish, double dte, double kco, int scale,
-                                 double *divx, double idte, unsigned fresh_mask = 0, const double *ari = nullptr, const int *clip = nullptr,
-                                 const double *clip_lo = nullptr, const double *clip_hi = nullptr);
-bool tlab_internal_burgers_fusable_anelastic(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
-bool tlab_internal_burgers_can_div(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);
-bool tlab_internal_partial_p1_sub(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, const double *u, double *result);
-bool tlab_internal_neumann_final_ok(tlab_fdm_plan_t g, int nx, int ny, int nz);
-bool tlab_internal_neumann_final(tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, double *h, double *q, double dte, double kco, int scale);
 
 struct tlab_dns {
     tlab_fdm_plan_t g[3];
@@ -61,12 +34,9 @@ struct tlab_dns {
     bool stagger = false;                          // [Staggering] StaggerHorizontalPressure: taken from the x / z plans at creation (tlab_fdm_plan_set_stagger)
     bool remove_divergence = true;                 // [Main] ... forcing = div(hq + q/dte) (rhs_global_incompressible_1.f90:177-232); false: div(hq) (:234-250)
     bool fresh = false;                            // one-shot: hq, hs count as zero on entry of the next substep (tlab_dns_begin_step)
-    int flow_jmin[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};   // BcsFlowJmin%type
-    int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
-    std::vector<int> scal_jmin, scal_jmax;         // BcsScalJmin%type, BcsScalJmax%type
-    // [Control] ScalLimit: DNS_BOUNDS_LIMIT (dns_local.f90:67-90) after the update of every substep, s = min(max(s, lo), hi) for the active scalars
-    std::vector<char> clip_on;                     // empty: no scalar is limited (the kernels of before)
-    std::vector<tlab::ClipBounds> clip_b;
+    WallBcs bcs;
+    ScalarBounds bounds;                           // [Control] ScalLimit
+    std::vector<tlab::ClipBounds> clip_b;          // ... of the substep under way, as the kernels take them (rhs_impl)
     // dynamic surface model of the scalars (BcsScalJmin/Jmax%SfcType = DNS_SFC_LINEAR, %cpl; boundary_bcs.f90:29-31, 49-50, 478-546)
     std::vector<int> sfc_jmin, sfc_jmax;
     std::vector<double> cpl_jmin, cpl_jmax;
@@ -103,17 +73,6 @@ struct tlab_dns {
 };
 
 namespace {
-struct Fail : std::runtime_error {
-    int code;
-    Fail(int c, const std::string &s) : std::runtime_error(s), code(c) {}
-};
-void ok(int rc, const char *what) {
-    if (rc != TLAB_OK) throw Fail(rc, std::string(what) + ": " + tlab_last_error());
-}
-void hk(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw Fail(TLAB_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // The wall value BOUNDARY_BCS_NEUMANN_Y (boundary_bcs.f90:368-473) gives a finished tendency h is a LINEAR functional of the y line:
 // c0 h(2) + c1 h(3) + c2 h(4) + c3 (D_N h)(2) with D_N the first derivative under the Neumann variant of the system.  Its weights are found once per
 // plan and variant by sending the unit vectors through the library's own routine (an ny x ny x 1 box holding the identity), and they decay like the
@@ -175,8 +134,36 @@ bool neumann_weights(tlab_dns *d, int ibc) {
 }
 }  // namespace
 
-long long tlab_internal_dns_points(tlab_dns_t d) { return d ? (long long)d->nx * d->ny * d->nz : 0; }      // deferred.cpp
+long long tlab_internal_dns_points(tlab_dns_t d) { return d ? (long long)d->nx * d->ny * d->nz : 0; }
 int tlab_internal_dns_nscal(tlab_dns_t d) { return d ? d->nscal : 0; }
+ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d) { return &d->bounds; }
+
+bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
+                                std::vector<double> &blo, std::vector<double> &bhi) {
+    on.clear(); blo.clear(); bhi.clear();
+    if (!active) return true;
+    if (n < 0 || n > nscal || !lo || !hi) {
+        tlab_set_error(std::string(who) + ": " + std::to_string(n) + " bounds for " + std::to_string(nscal) + " scalars, or NULL lo / hi");
+        return false;
+    }
+    on.assign((size_t)nscal, 0);
+    blo.assign((size_t)nscal, 0.0);
+    bhi.assign((size_t)nscal, 0.0);
+    bool any = false;
+    for (int is = 0; is < n; ++is) {
+        if (!active[is]) continue;
+        if (std::isnan(lo[is]) || std::isnan(hi[is]) || lo[is] > hi[is]) {
+            tlab_set_error(std::string(who) + ": scalar " + std::to_string(is + 1) + " has bounds [" + std::to_string(lo[is]) + ", " + std::to_string(hi[is]) +
+                           "] (NaN, or min > max)");
+            on.clear(); blo.clear(); bhi.clear();
+            return false;
+        }
+        on[is] = 1; blo[is] = lo[is]; bhi[is] = hi[is];
+        any = true;
+    }
+    if (!any) { on.clear(); blo.clear(); bhi.clear(); }      // nothing active: the kernels of a run without bounds
+    return true;
+}
 
 extern "C" {
 
@@ -194,7 +181,7 @@ int tlab_internal_dns_neumann_weights(tlab_dns_t d, int ibc, const double **w, i
 
 int tlab_dns_create(tlab_dns_t *out, tlab_fdm_plan_t gx, tlab_fdm_plan_t gy, tlab_fdm_plan_t gz, tlab_poisson_plan_t poisson,
                     int nx, int ny, int nz, int nscal, double visc, const double *schmidt) {
-    try {
+    return catch_fail([&] {
         if (!out || !gx || !gy || !gz || !poisson || nscal < 0 || (nscal > 0 && !schmidt) || visc <= 0.0)
             throw Fail(TLAB_EINVAL, "tlab_dns_create: bad arguments");
         if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
@@ -206,8 +193,7 @@ int tlab_dns_create(tlab_dns_t *out, tlab_fdm_plan_t gx, tlab_fdm_plan_t gy, tla
         if (d->stagger && (tlab_fdm_plan_info(gx, 7) != 1 || (nz > 1 && tlab_fdm_plan_info(gz, 7) != 1)))
             throw Fail(TLAB_EINVAL, "staggering: both the x and the z plan need their interpolation tables (tlab_fdm_plan_set_stagger)");
         d->schmidt.assign(schmidt, schmidt + nscal);
-        d->scal_jmin.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
-        d->scal_jmax.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
+        d->bcs.all_dirichlet(nscal);
         hk(hipMalloc((void **)&d->bcs_hb, (size_t)nx * nz * sizeof(double)), "hipMalloc");
         hk(hipMalloc((void **)&d->bcs_ht, (size_t)nx * nz * sizeof(double)), "hipMalloc");
         // TIME_INITIALIZE, tools/dns/time.f90:138-176
@@ -234,11 +220,7 @@ int tlab_dns_create(tlab_dns_t *out, tlab_fdm_plan_t gx, tlab_fdm_plan_t gy, tla
         }
         hk(hipMalloc((void **)&d->part, (size_t)2 * 1024 * sizeof(double)), "hipMalloc");
         *out = d.release();
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+    });
 }
 
 int tlab_dns_destroy(tlab_dns_t d) {
@@ -290,7 +272,7 @@ static void burgers_into(tlab_dns_t d, int dir, double nu, const double *s, cons
 }
 
 // bounds of scalar is, or NULL when it is not limited
-static const tlab::ClipBounds *clip_of(tlab_dns_t d, int is) { return !d->clip_on.empty() && d->clip_on[is] ? &d->clip_b[is] : nullptr; }
+static const tlab::ClipBounds *clip_of(tlab_dns_t d, int is) { return d->bounds.active(is) ? &d->clip_b[is] : nullptr; }
 
 static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs,
                      double *const *txc, bool tail_update, double kco, int scale_tendencies) {
@@ -298,6 +280,8 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     const long long n = (long long)nx * ny * nz;
     hipStream_t st = tlab_current_stream();
     follow_anelastic(d);
+    d->clip_b.resize(d->bounds.on.size());
+    for (size_t is = 0; is < d->clip_b.size(); ++is) d->clip_b[is] = {d->bounds.lo[is], d->bounds.hi[is]};
     double *u = q[0], *v = q[1], *w = q[2];
     double *tmp1 = txc[0], *tmp2 = txc[1], *tmp3 = txc[2], *tmp4 = txc[3], *tmp7 = txc[6], *tmp8 = txc[7], *tmp9 = txc[8];
     tlab_fdm_plan_t gx = d->g[0], gy = d->g[1], gz = d->g[2];
@@ -359,8 +343,8 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     {
         auto ibc_of = [](int tmin, int tmax) { return (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0); };
         bool any_neu = false, scal_neu = false;
-        for (int iq = 0; iq < 3; ++iq) any_neu = any_neu || ibc_of(d->flow_jmin[iq], d->flow_jmax[iq]) != 0;
-        for (int is = 0; is < d->nscal; ++is) scal_neu = scal_neu || ibc_of(d->scal_jmin[is], d->scal_jmax[is]) != 0;
+        for (int iq = 0; iq < 3; ++iq) any_neu = any_neu || ibc_of(d->bcs.flow_jmin[iq], d->bcs.flow_jmax[iq]) != 0;
+        for (int is = 0; is < d->nscal; ++is) scal_neu = scal_neu || ibc_of(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]) != 0;
         any_neu = any_neu || scal_neu;
         const char *npe = getenv("TLAB_NEUMANN_PLANES");
         const bool tail_fast = any_neu && tail_update && d->fuse && !literal && nz > 1 && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && !any_surface &&
@@ -369,20 +353,20 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         if (finish_scal && scal_neu && tail_fast && !(npe && atoi(npe) == 0)) {
             scal_neumann_planes = true;
             for (int is = 0; is < d->nscal; ++is) {
-                const int ibc = ibc_of(d->scal_jmin[is], d->scal_jmax[is]);
+                const int ibc = ibc_of(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
                 if (ibc != 0 && !neumann_weights(d, ibc)) scal_neumann_planes = false;
             }
         }
     }
     for (int is = 0; is < d->nscal && !scal_neumann_planes; ++is)
-        finish_scal = finish_scal && d->scal_jmin[is] == TLAB_DNS_BCS_DIRICHLET && d->scal_jmax[is] == TLAB_DNS_BCS_DIRICHLET;
+        finish_scal = finish_scal && d->bcs.scal_jmin[is] == TLAB_DNS_BCS_DIRICHLET && d->bcs.scal_jmax[is] == TLAB_DNS_BCS_DIRICHLET;
     finish_scal = finish_scal && !any_surface;      // the wall planes of a scalar with a surface model are not zero
     // scalar bounds in the epilogue that finishes scalar is: on every line, or -- Neumann walls on the wall-plane route -- on the interior lines, k_wall_fix
     // clipping the wall planes once they are set
     auto clip_into = [&](int is, int &mode, double &lo, double &hi) {
         const tlab::ClipBounds *c = clip_of(d, is);
         if (!c) return;
-        const bool neu = d->scal_jmin[is] == TLAB_DNS_BCS_NEUMANN || d->scal_jmax[is] == TLAB_DNS_BCS_NEUMANN;
+        const bool neu = d->bcs.scal_jmin[is] == TLAB_DNS_BCS_NEUMANN || d->bcs.scal_jmax[is] == TLAB_DNS_BCS_NEUMANN;
         mode = (scal_neumann_planes && neu) ? 2 : 1;
         lo = c->lo; hi = c->hi;
     };
@@ -529,13 +513,13 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // solver finishes the v equation itself (hq2 -= dp/dy; wall planes; v += dte hq2; hq2 *= kco) and tmp3 is not written
     bool v_final = false;
     bool walls_dirichlet = true;      // (a Neumann wall of any component sends all three through the unfused subtraction below)
-    for (int iq = 0; iq < 3; ++iq) walls_dirichlet = walls_dirichlet && d->flow_jmin[iq] == TLAB_DNS_BCS_DIRICHLET && d->flow_jmax[iq] == TLAB_DNS_BCS_DIRICHLET;
+    for (int iq = 0; iq < 3; ++iq) walls_dirichlet = walls_dirichlet && d->bcs.flow_jmin[iq] == TLAB_DNS_BCS_DIRICHLET && d->bcs.flow_jmax[iq] == TLAB_DNS_BCS_DIRICHLET;
     // Neumann walls somewhere (free-slip u, w; Neumann scalars): the tail below then runs per field -- gradient subtracted in its own launch,
     // BOUNDARY_BCS_NEUMANN_Y + final update in ONE launch along y (tlab_internal_neumann_final) -- and v, always Dirichlet, is finished by the solver
     auto ibc_y = [](int tmin, int tmax) { return (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0); };
     bool any_neumann = false;
-    for (int iq = 0; iq < 3; ++iq) any_neumann = any_neumann || ibc_y(d->flow_jmin[iq], d->flow_jmax[iq]) != 0;
-    for (int is = 0; is < d->nscal; ++is) any_neumann = any_neumann || ibc_y(d->scal_jmin[is], d->scal_jmax[is]) != 0;
+    for (int iq = 0; iq < 3; ++iq) any_neumann = any_neumann || ibc_y(d->bcs.flow_jmin[iq], d->bcs.flow_jmax[iq]) != 0;
+    for (int is = 0; is < d->nscal; ++is) any_neumann = any_neumann || ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]) != 0;
     const bool neu_fast = any_neumann && tail_update && d->fuse && !literal && nz > 1 && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && !any_surface &&
                           tlab_internal_poisson_can_v_final(d->poisson) && tlab_internal_neumann_final_ok(gy, nx, ny, nz) &&
                           tlab_internal_partial_p1_fusable(1, gx, nx, ny, nz) && tlab_internal_partial_p1_fusable(3, gz, nx, ny, nz);
@@ -556,7 +540,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         for (int iq = 0; iq < 3; iq += 2) {      // u along x, w along z
             const int dir = iq == 0 ? 1 : 3;
             tlab_fdm_plan_t gd = iq == 0 ? gx : gz;
-            const int ibc = ibc_y(d->flow_jmin[iq], d->flow_jmax[iq]);
+            const int ibc = ibc_y(d->bcs.flow_jmin[iq], d->bcs.flow_jmax[iq]);
             bool done;
             if (ibc == 0) done = tlab_internal_gradient_final(dir, gd, nx, ny, nz, tmp1, q[iq], hq[iq], dte, kco, scale_tendencies);
             else if (neu_planes && neumann_weights(d, ibc)) {
@@ -578,7 +562,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             if (!done) throw Fail(TLAB_EINVAL, "internal: inconsistent fused Neumann tail");
         }
         for (int is = 0; is < d->nscal && !finish_scal; ++is) {
-            const int ibc = ibc_y(d->scal_jmin[is], d->scal_jmax[is]);
+            const int ibc = ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
             if (ibc == 0) hk(launch_final_update(s[is], hs[is], nullptr, nullptr, nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)),
                              "final update");
             else if (!tlab_internal_neumann_final(gy, nx, ny, nz, ibc, hs[is], s[is], dte, kco, scale_tendencies))
@@ -587,7 +571,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
                 hk(launch_clip(s[is], c->lo, c->hi, n, st), "clip");
         }
         for (int is = 0; is < d->nscal && finish_scal && scal_neumann_planes; ++is) {      // finished by the x Burgers launch but for their wall planes
-            const int ibc = ibc_y(d->scal_jmin[is], d->scal_jmax[is]);
+            const int ibc = ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
             if (ibc == 0) continue;
             const tlab_dns::NeuW &W = d->neuw[ibc];
             const size_t np = (size_t)nx * nz;
@@ -604,7 +588,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     bool grad_final = false, grad_sub = false;
     if (tail_update && d->fuse && nz > 1 && !literal) {
         bool dirichlet = true;
-        for (int iq = 0; iq < 3; ++iq) dirichlet = dirichlet && d->flow_jmin[iq] == TLAB_DNS_BCS_DIRICHLET && d->flow_jmax[iq] == TLAB_DNS_BCS_DIRICHLET;
+        for (int iq = 0; iq < 3; ++iq) dirichlet = dirichlet && d->bcs.flow_jmin[iq] == TLAB_DNS_BCS_DIRICHLET && d->bcs.flow_jmax[iq] == TLAB_DNS_BCS_DIRICHLET;
         if (dirichlet && tlab_internal_partial_p1_fusable(1, gx, nx, ny, nz) && tlab_internal_partial_p1_fusable(3, gz, nx, ny, nz)) {
             const bool okx = tlab_internal_gradient_final(1, gx, nx, ny, nz, tmp1, q[0], hq[0], dte, kco, scale_tendencies);
             const bool okz = okx && tlab_internal_gradient_final(3, gz, nx, ny, nz, tmp1, q[2], hq[2], dte, kco, scale_tendencies);
@@ -637,7 +621,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // keeps d/dy = 0 there (BOUNDARY_BCS_NEUMANN_Y on the finished tendency; tmp1 is its work array as in the reference) ----
     auto ibc_of = [](int tmin, int tmax) { return (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0); };
     int ibc_q[3], any_q = 0;
-    for (int iq = 0; iq < 3; ++iq) any_q |= (ibc_q[iq] = ibc_of(d->flow_jmin[iq], d->flow_jmax[iq]));
+    for (int iq = 0; iq < 3; ++iq) any_q |= (ibc_q[iq] = ibc_of(d->bcs.flow_jmin[iq], d->bcs.flow_jmax[iq]));
     // planes of a field: Neumann values where selected, zeros (null) elsewhere
     auto planes = [&](int ibc, const double *h, const double *&pb, const double *&pt) {
         pb = pt = nullptr;
@@ -649,7 +633,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     const double *pb, *pt;
     // planes of a scalar: Neumann values where selected, then the dynamic surface model (BOUNDARY_BCS_SURFACE_Y, :393-396), zeros (null) elsewhere
     auto scal_planes = [&](int is, const double *&qb, const double *&qt) {
-        const int ibc = ibc_of(d->scal_jmin[is], d->scal_jmax[is]);
+        const int ibc = ibc_of(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
         planes(ibc, hs[is], qb, qt);
         if (!surface(is)) return;
         const size_t pbytes = (size_t)nx * nz * sizeof(double);
@@ -710,66 +694,32 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
 
 int tlab_rhs_global_incompressible_1(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq,
                                      double *const *hs, double *const *txc) {
-    try {
+    return catch_fail([&] {
         if (!d || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs)) || dte <= 0.0) throw Fail(TLAB_EINVAL, "tlab_rhs_global_incompressible_1: bad arguments");
         rhs_impl(d, dte, q, s, hq, hs, txc, false, 1.0, 0);
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
+    }, TLAB_EINVAL);
 }
 
 int tlab_time_substep_incompressible_explicit(tlab_dns_t d, double dte, double kco, int scale_tendencies, double *const *q,
                                               double *const *s, double *const *hq, double *const *hs, double *const *txc) {
-    try {
+    return catch_fail([&] {
         if (!d || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs)) || dte <= 0.0) throw Fail(TLAB_EINVAL, "tlab_time_substep_incompressible_explicit: bad arguments");
         rhs_impl(d, dte, q, s, hq, hs, txc, true, kco, scale_tendencies);
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
+    }, TLAB_EINVAL);
 }
 
 int tlab_dns_set_bcs(tlab_dns_t d, const int *flow_jmin, const int *flow_jmax, const int *scal_jmin, const int *scal_jmax) {
     (void)tlab_internal_deferred_flush();
-    auto valid = [](int t) { return t == TLAB_DNS_BCS_DIRICHLET || t == TLAB_DNS_BCS_NEUMANN; };
-    if (!d || !flow_jmin || !flow_jmax || (d->nscal > 0 && (!scal_jmin || !scal_jmax))) {
-        tlab_set_error("tlab_dns_set_bcs: bad arguments");
-        return TLAB_EINVAL;
-    }
-    for (int i = 0; i < 3; ++i)
-        if (!valid(flow_jmin[i]) || !valid(flow_jmax[i])) { tlab_set_error("tlab_dns_set_bcs: type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN"); return TLAB_EINVAL; }
-    for (int i = 0; i < d->nscal; ++i)
-        if (!valid(scal_jmin[i]) || !valid(scal_jmax[i])) { tlab_set_error("tlab_dns_set_bcs: type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN"); return TLAB_EINVAL; }
-    if (flow_jmin[1] != TLAB_DNS_BCS_DIRICHLET || flow_jmax[1] != TLAB_DNS_BCS_DIRICHLET) {
-        tlab_set_error("tlab_dns_set_bcs: the wall-normal velocity must be Dirichlet (impermeable walls; the pressure BCs assume v = 0)");
-        return TLAB_EUNSUPPORTED;
-    }
-    for (int i = 0; i < 3; ++i) { d->flow_jmin[i] = flow_jmin[i]; d->flow_jmax[i] = flow_jmax[i]; }
-    for (int i = 0; i < d->nscal; ++i) { d->scal_jmin[i] = scal_jmin[i]; d->scal_jmax[i] = scal_jmax[i]; }
-    // the wall-plane weights of the Neumann variants in use are built HERE (allocations, a synchronisation), not in the middle of the first substep
-    try {
+    return catch_fail([&] {
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_bcs: bad arguments");
+        d->bcs.set("tlab_dns_set_bcs", d->nscal, flow_jmin, flow_jmax, scal_jmin, scal_jmax);
+        // the wall-plane weights of the Neumann variants in use are built HERE (allocations, a synchronisation), not in the middle of the first substep
         auto variant = [](int jmin, int jmax) { return (jmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (jmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0); };
         for (int i = 0; i < 3; ++i)
             if (variant(flow_jmin[i], flow_jmax[i])) (void)neumann_weights(d, variant(flow_jmin[i], flow_jmax[i]));
         for (int i = 0; i < d->nscal; ++i)
             if (variant(scal_jmin[i], scal_jmax[i])) (void)neumann_weights(d, variant(scal_jmin[i], scal_jmax[i]));
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EHIP;
-    }
-    return TLAB_OK;
+    }, TLAB_EHIP);
 }
 
 // min / max of a device array through per-block partials reduced on the host (diagnostics: once per time step, not per substep)
@@ -793,7 +743,7 @@ int tlab_dns_set_surface_bcs(tlab_dns_t d, const int *sfc_jmin, const int *sfc_j
         tlab_set_error("tlab_dns_set_surface_bcs: bad arguments");
         return TLAB_EINVAL;
     }
-    try {
+    return catch_fail([&] {
         for (int i = 0; i < d->nscal; ++i)
             if ((sfc_jmin[i] != 0 && sfc_jmin[i] != 1) || (sfc_jmax[i] != 0 && sfc_jmax[i] != 1)) throw Fail(TLAB_EINVAL, "SfcType: 0 static or 1 linear");
         d->sfc_jmin.assign(sfc_jmin, sfc_jmin + d->nscal); d->sfc_jmax.assign(sfc_jmax, sfc_jmax + d->nscal);
@@ -807,11 +757,7 @@ int tlab_dns_set_surface_bcs(tlab_dns_t d, const int *sfc_jmin, const int *sfc_j
             }
         }
         if (!d->sfc_avg) hk(hipMalloc((void **)&d->sfc_avg, sizeof(double)), "hipMalloc");
-        return TLAB_OK;
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    }
+    });
 }
 
 // nse_eqns == DNS_EQNS_ANELASTIC (tools/dns/rhs_global_incompressible_1.f90:211-214, 275-277, 326-329; physics/opr_burgers.f90:128-183) with the
@@ -819,19 +765,12 @@ int tlab_dns_set_surface_bcs(tlab_dns_t d, const int *sfc_jmin, const int *sfc_j
 int tlab_dns_set_anelastic(tlab_dns_t d, const double *rbackground, const double *ribackground) {
     (void)tlab_internal_deferred_flush();
     if (!d) return TLAB_EINVAL;
-    try {
+    return catch_fail([&] {
         if (!rbackground || !ribackground) ok(tlab_opr_burgers_set_anelastic(0, nullptr, nullptr), "tlab_opr_burgers_set_anelastic");
         else ok(tlab_opr_burgers_set_anelastic(d->ny, rbackground, ribackground), "tlab_opr_burgers_set_anelastic");
         follow_anelastic(d);
         d->anel_owner = d->rb != nullptr;
-        return TLAB_OK;
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
+    }, TLAB_EINVAL);
 }
 
 // [PressureFilter] (operators/opr_filter.f90:46, 78; rhs_global_incompressible_1.f90:286-290): directional 1-D filters applied to p and dp/dy after
@@ -859,28 +798,19 @@ int tlab_dns_set_slab(tlab_dns_t d, int koffset) {
 }
 
 int tlab_time_courant(tlab_dns_t d, double *const *q, double cfla, double cfld, double *pmax, double *dtime) {
-    try {
+    return catch_fail([&] {
         if (!d || !q || !pmax) throw Fail(TLAB_EINVAL, "tlab_time_courant: bad arguments");
         if (d->dx2i < 0.0) throw Fail(TLAB_EINVAL, "tlab_time_courant: the plans carry no Jacobian (tlab_fdm_plan_set_aux)");
         double mn, mx;
         minmax_impl(d, q[0], q[1], q[2], 1, d->nx, d->ny, d->nz, &mn, &mx);
         pmax[0] = mx;                                   // max of |u|/dx + |v|/dy + |w|/dz over the local box (time.f90:402-451)
         pmax[1] = d->schmidtfactor * d->dx2i;           // time.f90:466
-        if (dtime && cfla > 0.0) {                      // time.f90:523-538, explicit RK: min of the two limits
-            double dtc = 1.0e300, dtd = 1.0e300;
-            if (pmax[0] > 0.0) dtc = cfla / pmax[0];
-            if (pmax[1] > 0.0) dtd = cfld / pmax[1];
-            *dtime = std::min(dtc, dtd);
-        }
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+        if (dtime && cfla > 0.0) *dtime = courant_dtime(cfla, cfld, pmax);      // (without a CFL number the caller's dtime stands)
+    });
 }
 
 int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *tmp1) {
-    try {
+    return catch_fail([&] {
         if (!d || !u || !v || !w || !result || !tmp1) throw Fail(TLAB_EINVAL, "tlab_fi_invariant_p: bad arguments");
         const int nx = d->nx, ny = d->ny, nz = d->nz;
         const long long n = (long long)nx * ny * nz;
@@ -892,28 +822,20 @@ int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const do
         ok(tlab_opr_partial(3, d->g[2], TLAB_OPR_P1, nx, ny, nz, 0, w, tmp1, nullptr), "OPR_Partial_Z");
         hk(launch_add1(result, tmp1, n, st), "add");
         hk(launch_negate(result, n, st), "negate");
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+    });
 }
 
 int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *amn, double *amx) {
-    try {
+    return catch_fail([&] {
         if (!d || !a || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_minmax: bad arguments");
         minmax_impl(d, a, nullptr, nullptr, 0, nx, ny, nz, amn, amx);
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+    });
 }
 
 // DNS_BOUNDS_CONTROL (dns_local.f90:157-230), incompressible and anelastic: div(q) accumulated into txc[0] by the three P1 derivatives, then one
 // reduction for min, max and their first locations.  Anelastic runs weight the velocities by rbackground first (:160-162, into txc[2..4]).
 int tlab_dns_dilatation_extremes(tlab_dns_t d, double *const *q, double *const *txc, double *dil_min, double *dil_max, int *loc_min, int *loc_max) {
-    try {
+    return catch_fail([&] {
         if (!d || !q || !txc || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_dns_dilatation_extremes: bad arguments");
         if (d->stagger) throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_dilatation_extremes: FI_INVARIANT_P_STAG (staggered pressure) is not built on the device");
         hipStream_t st = tlab_current_stream();      // (a recorded substep runs first: q is read below)
@@ -936,38 +858,26 @@ int tlab_dns_dilatation_extremes(tlab_dns_t d, double *const *q, double *const *
         };
         loc(imn, loc_min);
         loc(imx, loc_max);
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+    });
 }
 
 // the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
 int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff, double *pmax) {
-    try {
+    return catch_fail([&] {
         if (d->dx2i < 0.0) throw Fail(TLAB_EINVAL, "TIME_COURANT: the plans carry no Jacobian (tlab_fdm_plan_set_aux)");
         hipStream_t st = tlab_current_stream();
         hk(monitor_courant_max(u, v, w, d->od[0], d->od[1], d->od[2], nx, ny, nz, ioff, koff, d->nz_total > 1 ? 1 : 0, &pmax[0], st), "k_courant");
         pmax[1] = d->schmidtfactor * d->dx2i;
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+    });
 }
 
 // MINMAX (utils/minmax.f90:6), local part, of any device array: no driver needed
 int tlab_device_minmax(const double *a, long long n, double *amn, double *amx) {
-    try {
+    return catch_fail([&] {
         if (!a || n < 1 || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_device_minmax: bad arguments");
         if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
         hk(monitor_extremes(a, nullptr, n, amn, amx, nullptr, nullptr, tlab_current_stream()), "k_extremes");
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    }
+    });
 }
 
 // ... of an array of either kind (the drop-in MINMAX): device memory takes the kernel, host memory the host loop of minmax.f90 -- a host array
@@ -1054,7 +964,7 @@ std::pair<double, double> confirm(const std::function<double(const std::vector<i
 
 int tlab_dns_place_arrays(tlab_dns_t d, int npool, double *const *pool, const double *const *state, double dtime, int random_trials, unsigned seed,
                           int *assignment, double *report) {
-    try {
+    return catch_fail([&] {
         if (!d || !pool || !assignment || dtime <= 0.0 || random_trials < 0) throw Fail(TLAB_EINVAL, "tlab_dns_place_arrays: bad arguments");
         const int ns = d->nscal, nroles = 2 * (3 + ns) + 9;
         if (npool < nroles) throw Fail(TLAB_EINVAL, "tlab_dns_place_arrays: the pool must hold at least 2 (3 + nscal) + 9 arrays");
@@ -1121,14 +1031,7 @@ int tlab_dns_place_arrays(tlab_dns_t d, int npool, double *const *pool, const do
             std::sort(sorted.begin(), sorted.end());
             report[0] = ms_first; report[1] = ms_kept; report[2] = sorted[sorted.size() / 2]; report[3] = sorted.back(); report[4] = (double)all.size();
         }
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
+    }, TLAB_EINVAL);
 }
 
 // ---- the same question for a Tlab HOST (include/tlab_amd.h: tlab_dns_place_blocks) ----
@@ -1138,7 +1041,7 @@ int tlab_dns_place_arrays(tlab_dns_t d, int npool, double *const *pool, const do
 // and the host re-associates its pointers with the winners before any field is read.
 int tlab_dns_place_blocks(tlab_dns_t d, int ncand, double *const *cand_q, double *const *cand_s, double *const *cand_hq, double *const *cand_hs,
                           double *const *cand_txc, long long txc_stride, double dtime, int random_trials, unsigned seed, int *choice, double *report) {
-    try {
+    return catch_fail([&] {
         if (!d || ncand < 1 || !cand_q || !cand_hq || !cand_txc || !choice || dtime <= 0.0 || random_trials < 0)
             throw Fail(TLAB_EINVAL, "tlab_dns_place_blocks: bad arguments");
         const int ns = d->nscal;
@@ -1206,69 +1109,12 @@ int tlab_dns_place_blocks(tlab_dns_t d, int ncand, double *const *cand_q, double
             std::sort(sorted.begin(), sorted.end());
             report[0] = ms_first; report[1] = ms_kept; report[2] = sorted[sorted.size() / 2]; report[3] = sorted.back(); report[4] = (double)all.size();
         }
-        return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.what());
-        return f.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
+    }, TLAB_EINVAL);
 }
-
-extern "C++" {
-// shared by the three drivers: n entries (<= nscal) of active / lo / hi checked, the bounds of the active ones returned (on[is] = 0 otherwise)
-bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
-                                std::vector<double> &blo, std::vector<double> &bhi) {
-    on.clear(); blo.clear(); bhi.clear();
-    if (!active) return true;
-    if (n < 0 || n > nscal || !lo || !hi) {
-        tlab_set_error(std::string(who) + ": " + std::to_string(n) + " bounds for " + std::to_string(nscal) + " scalars, or NULL lo / hi");
-        return false;
-    }
-    on.assign((size_t)nscal, 0);
-    blo.assign((size_t)nscal, 0.0);
-    bhi.assign((size_t)nscal, 0.0);
-    bool any = false;
-    for (int is = 0; is < n; ++is) {
-        if (!active[is]) continue;
-        if (std::isnan(lo[is]) || std::isnan(hi[is]) || lo[is] > hi[is]) {
-            tlab_set_error(std::string(who) + ": scalar " + std::to_string(is + 1) + " has bounds [" + std::to_string(lo[is]) + ", " + std::to_string(hi[is]) +
-                           "] (NaN, or min > max)");
-            on.clear(); blo.clear(); bhi.clear();
-            return false;
-        }
-        on[is] = 1; blo[is] = lo[is]; bhi[is] = hi[is];
-        any = true;
-    }
-    if (!any) { on.clear(); blo.clear(); bhi.clear(); }      // nothing active: the kernels of a run without bounds
-    return true;
-}
-
-void tlab_internal_dns_swap_bounds(tlab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi);
-}      // extern "C++"
 
 int tlab_dns_set_scalar_bounds(tlab_dns_t d, int n, const int *active, const double *lo, const double *hi) {
-    (void)tlab_internal_deferred_flush();
-    if (!d) { tlab_set_error("tlab_dns_set_scalar_bounds: null handle"); return TLAB_EINVAL; }
-    std::vector<char> on;
-    std::vector<double> blo, bhi;
-    if (!tlab_internal_check_bounds("tlab_dns_set_scalar_bounds", d->nscal, n, active, lo, hi, on, blo, bhi)) return TLAB_EINVAL;
-    tlab_internal_dns_swap_bounds(d, on, blo, bhi);
-    return TLAB_OK;
+    return set_scalar_bounds("tlab_dns_set_scalar_bounds", d, n, active, lo, hi);
 }
-extern "C++" {
-// deferred.cpp: does the driver limit scalars of its own?  And the bounds of a recorded substep, put in place for the one fused call and taken back
-bool tlab_internal_dns_has_bounds(tlab_dns_t d) { return d && !d->clip_on.empty(); }
-void tlab_internal_dns_swap_bounds(tlab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
-    std::vector<double> olo(d->clip_on.size()), ohi(d->clip_on.size());
-    for (size_t i = 0; i < d->clip_b.size(); ++i) { olo[i] = d->clip_b[i].lo; ohi[i] = d->clip_b[i].hi; }
-    std::vector<tlab::ClipBounds> b(on.size());
-    for (size_t i = 0; i < on.size(); ++i) b[i] = {lo[i], hi[i]};
-    d->clip_on.swap(on); d->clip_b.swap(b);
-    lo.swap(olo); hi.swap(ohi);
-}
-}      // extern "C++"
 
 int tlab_dns_set_fusion(tlab_dns_t d, int on) {
     (void)tlab_internal_deferred_flush();
@@ -1293,13 +1139,6 @@ int tlab_pw_axpy3(double *o1, double *o2, double *o3, const double *h1, const do
 int tlab_pw_sum3(double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_sum3(a, b, c, n, tlab_current_stream())) }
 int tlab_pw_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_sub3(h1, h2, h3, a, b, c, n, tlab_current_stream())) }
 int tlab_pw_rk_update(double *q, double *h, double dte, double kco, int scale, long long n) { PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream())) }
-extern "C++" {
-// q += dte h, q = min(max(q, lo), hi), h *= kco: the scalar update of the decomposed drivers with their bounds (pencil.cpp)
-int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi) {
-    const tlab::ClipBounds c{lo, hi};
-    PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream(), &c))
-}
-}      // extern "C++"
 int tlab_pw_clip(double *a, double lo, double hi, long long n) {
     if (!a || n < 0 || std::isnan(lo) || std::isnan(hi) || lo > hi) { tlab_set_error("tlab_pw_clip: null array, n < 0, NaN bounds or lo > hi"); return TLAB_EINVAL; }
     PW_GUARD(launch_clip(a, lo, hi, n, tlab_current_stream()))
@@ -1323,3 +1162,8 @@ int tlab_pw_fill_wall_planes(double *f, double vb, double vt, int nx, int ny, in
 int tlab_pw_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz) { PW_GUARD(launch_set_wall_planes(f, pb, pt, nx, ny, nz, tlab_current_stream())) }
 
 }  // extern "C"
+
+int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi) {
+    const tlab::ClipBounds c{lo, hi};
+    PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream(), &c))
+}

@@ -11,72 +11,26 @@
 //     per output field on the way back; every rank's kx range is cut in two halves with a plan each, and the six half-size all-to-alls queue up as
 //     fwd A, fwd B, back p A, back dp A, back p B, back dp B: the solves of A run under fwd B, those of B under the returns of A.
 // The exchanges go through a tlab_slab_transport (include/tlab_amd.h): RCCL (comm.hip), the single-process loopback below, or the caller's own.
-// This file holds host logic only; every kernel is reached through the C ABI of the operator library, as a Fortran host would reach it.
-#include "../../include/tlab_amd.h"
-#include "monitor.hpp"
-
+// This file holds host logic only: the operators are reached through the C ABI of the operator library, as a Fortran host would reach them, the
+// z-slab operators with halo buffers and a few pointwise launchers (kernels.hpp) directly.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-extern hipStream_t tlab_current_stream();
-int tlab_internal_deferred_flush();      // deferred.cpp
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
-// zslab.hip: the z-slab operators with the neighbours' halo planes of every operand in buffers of their own ({lo, hi}, 3 planes each)
-bool tlab_internal_poisson_has_own_x(tlab_poisson_plan_t P);      // poisson.hip
-int tlab_internal_zslab_partial_z(tlab_zslab_plan_t P, int phase, int nx, int ny, const double *u, const double *const *u_halo, const double *ub,
-                                  const double *const *ub_halo, double scale, double *head, double *tail, const double *tail_left,
-                                  const double *head_right, double *result, int acc);
-int tlab_internal_zslab_burgers_z_n(tlab_zslab_plan_t P, int phase, int nx, int ny, int nf, const double *nu, const double *const *s,
-                                    const double *const *s_lo, const double *const *s_hi, const double *vel, double *head, double *tail,
-                                    const double *tail_left, const double *head_right, double *const *result, int acc, const int *fin, double dte,
-                                    double kco, int scale);
-int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, const double *p, const double *const *p_halo, const double *tail_left,
-                                         const double *head_right, double *q, double *h, double dte, double kco, int scale);
+#include "driver_common.hpp"
+#include "kernels.hpp"
+#include "monitor.hpp"
 
-extern "C" bool tlab_internal_anelastic();       // capi.cpp: the operator state set by tlab_opr_burgers_set_anelastic / _set_dealiasing
-extern "C" bool tlab_internal_dealiasing();
-
-extern "C" int tlab_internal_dns_neumann_weights(tlab_dns_t d, int ibc, const double **w, int *K);      // rhs.cpp
-
-namespace tlab {
-hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
-                                double *ot2, int nx, int ny, int nz, hipStream_t st);                                      // pointwise.hip
-struct ClipBounds;
-hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,
-                           hipStream_t stream, const ClipBounds *clip = nullptr);
-hipError_t launch_copy_blocks(int n, const double *const *src, double *const *dst, const long long *cnt, hipStream_t st);      // pointwise.hip
-hipError_t launch_plane_avg(const double *t, int j, int nx, int ny, int nz, double *avg, hipStream_t st);
-hipError_t launch_surface_flux_avg(double *ref, const double *t, int j, double sign, double diff, double cpl, double avg, int nx, int ny, int nz,
-                                   hipStream_t st);
-hipError_t launch_get_wall_planes(const double *f, double *hb, double *ht, int nx, int ny, int nz, hipStream_t st);
-}
+using namespace tlab;
 
 namespace {
 
-struct Fail : std::runtime_error {
-    int code;
-    Fail(int c, const std::string &s) : std::runtime_error(s), code(c) {}
-};
-void ok(int rc, const char *what) {
-    if (rc != TLAB_OK) throw Fail(rc, std::string(what) + ": " + tlab_last_error());
-}
-void hk(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw Fail(TLAB_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-double *dalloc(size_t ndoubles) {
-    double *p = nullptr;
-    hk(hipMalloc((void **)&p, std::max<size_t>(ndoubles, 1) * sizeof(double)), "hipMalloc");
-    hk(hipMemset(p, 0, std::max<size_t>(ndoubles, 1) * sizeof(double)), "hipMemset");
-    return p;
-}
+double *dalloc(size_t ndoubles) { return tlab::dalloc(ndoubles, false); }
 
 constexpr int HALO = 3;      // planes each side: the 7-diagonal right-hand side of the second derivative reaches 3 rows
 
@@ -154,9 +108,6 @@ struct Rank {
 
 }  // namespace
 
-bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
-                                std::vector<double> &blo, std::vector<double> &bhi);      // rhs.cpp
-
 struct tlab_slab_dns {
     tlab_slab_transport tr{};
     tlab_fdm_plan_t g[3] = {nullptr, nullptr, nullptr}, gy_elliptic = nullptr;
@@ -174,12 +125,9 @@ struct tlab_slab_dns {
     std::vector<int> st_start;                   // two-stage block map (tlab_pencil_repack_blocks)
     std::vector<long long> st_base;
     long long st_split = 0;                      // doubles of the A part of a pack buffer
-    int flow_jmin[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
-    int flow_jmax[3] = {TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET, TLAB_DNS_BCS_DIRICHLET};
-    std::vector<int> scal_jmin, scal_jmax;
+    WallBcs bcs;
     bool fresh = false;
-    std::vector<char> clip_on;                    // [Control] ScalLimit: DNS_BOUNDS_LIMIT after the update of every substep (empty: no scalar limited)
-    std::vector<double> clip_lo, clip_hi;
+    ScalarBounds bounds;
     std::vector<int> sfc_jmin, sfc_jmax;          // BcsScalJmin / Jmax%SfcType (0 static, 1 linear) and %cpl per scalar
     std::vector<double> cpl_jmin, cpl_jmax;
     bool remove_divergence = true;     // [Main] TermDivergence: forcing div(hq + q/dte) (rhs_global_incompressible_1.f90:177-232); false: div(hq) (:234-250)
@@ -516,9 +464,9 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
             const double *w;
             int K;
             for (int i = 0; i < 3; i += 2)
-                if (int ibc = ibc_of(d->flow_jmin[i], d->flow_jmax[i])) planes_route = planes_route && weights_of(R, ibc, w, K);
+                if (int ibc = ibc_of(d->bcs.flow_jmin[i], d->bcs.flow_jmax[i])) planes_route = planes_route && weights_of(R, ibc, w, K);
             for (int i = 0; i < ns; ++i)
-                if (int ibc = ibc_of(d->scal_jmin[i], d->scal_jmax[i])) planes_route = planes_route && weights_of(R, ibc, w, K);
+                if (int ibc = ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i])) planes_route = planes_route && weights_of(R, ibc, w, K);
         }
     }
     // wall planes of a field that was finished with zero wall tendencies
@@ -533,7 +481,7 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     // Python driver's sequence)
     std::vector<int> zfin((size_t)(3 + ns), 0);
     for (int i = 0; i < ns; ++i)
-        zfin[3 + i] = tail && d->fused_x && !surface(i) && (ibc_of(d->scal_jmin[i], d->scal_jmax[i]) == 0 || planes_route);
+        zfin[3 + i] = tail && d->fused_x && !surface(i) && (ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]) == 0 || planes_route);
     // ---- diffusion + advection (:98-162) and the pressure forcing div(hq + q/dte) (:188-260) ----
     // (Measured in round 4 and dropped: the x and y terms of the forcing inside the Burgers launches that add the last term of u resp. v, as rhs.cpp
     // does on one device.  It needs u to end with its x term and v with its y term, i.e. the x and y launches split in two; on slabs of 64 planes the
@@ -558,8 +506,8 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     // ---- pressure (:284) and its gradient (:319-320) ----
     auto dirichlet = [](int t) { return t == TLAB_DNS_BCS_DIRICHLET; };
     bool vel_dirichlet = true, scal_dirichlet = true;
-    for (int i = 0; i < 3; ++i) vel_dirichlet = vel_dirichlet && dirichlet(d->flow_jmin[i]) && dirichlet(d->flow_jmax[i]);
-    for (int i = 0; i < ns; ++i) scal_dirichlet = scal_dirichlet && dirichlet(d->scal_jmin[i]) && dirichlet(d->scal_jmax[i]);
+    for (int i = 0; i < 3; ++i) vel_dirichlet = vel_dirichlet && dirichlet(d->bcs.flow_jmin[i]) && dirichlet(d->bcs.flow_jmax[i]);
+    for (int i = 0; i < ns; ++i) scal_dirichlet = scal_dirichlet && dirichlet(d->bcs.scal_jmin[i]) && dirichlet(d->bcs.scal_jmax[i]);
     const bool grad_final = tail && (vel_dirichlet || planes_route);      // (v is always Dirichlet: tlab_slab_dns_set_bcs)
     const bool v_final = grad_final && d->fused_x && !d->gy_elliptic;      // v is finished by the inverse x-transform of dp^/dy
     d->vf.armed = v_final; d->vf.dte = tdte; d->vf.kco = kco; d->vf.scale = scale;
@@ -605,9 +553,9 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
             int tmin, tmax, is;
         };
         std::vector<Fd> F;
-        for (int i = 0; i < 3; ++i) F.push_back({R.q[i], R.hq[i], R.txc[1 + i], d->flow_jmin[i], d->flow_jmax[i], -1});
+        for (int i = 0; i < 3; ++i) F.push_back({R.q[i], R.hq[i], R.txc[1 + i], d->bcs.flow_jmin[i], d->bcs.flow_jmax[i], -1});
         for (int i = 0; i < ns; ++i)
-            if (!zfin[3 + i]) F.push_back({R.s[i], R.hs[i], nullptr, d->scal_jmin[i], d->scal_jmax[i], i});
+            if (!zfin[3 + i]) F.push_back({R.s[i], R.hs[i], nullptr, d->bcs.scal_jmin[i], d->bcs.scal_jmax[i], i});
         if (grad_final) F.erase(F.begin() + 2), F.erase(F.begin());          // v and the scalars; u, w are done (+ their wall planes below)
         if (v_final) F.erase(F.begin());                                     // the scalars
         if (!grad_final && (!vel_dirichlet || !tail)) {
@@ -634,7 +582,7 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     if (grad_final) {   // u and w are finished by the gradient kernels themselves (no gradient array)
         for (Rank &R : d->rk) {
             ok(tlab_opr_gradient_final(1, d->g[0], nx, ny, kmax, R.txc[0], R.q[0], R.hq[0], tdte, kco, scale, R.txc[1]), "tlab_opr_gradient_final");
-            if (int ibc = ibc_of(d->flow_jmin[0], d->flow_jmax[0])) wall_fix(R, R.q[0], R.hq[0], ibc);
+            if (int ibc = ibc_of(d->bcs.flow_jmin[0], d->bcs.flow_jmax[0])) wall_fix(R, R.q[0], R.hq[0], ibc);
         }
     } else {
         for (Rank &R : d->rk) padd(d, R, 1, R.txc[0], nullptr, 0.0, R.txc[1], 0);
@@ -645,7 +593,7 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     // v and the scalars do not wait for dp/dz: their update runs while the interface values travel (not with Neumann scalars, whose boundary
     // routine takes tmp1 = p as scratch)
     bool needs_bcs_routine = false;      // a field left for `finish` with a Neumann wall: BOUNDARY_BCS_NEUMANN_Y, which takes tmp1 = p as scratch
-    for (int i = 0; i < ns; ++i) needs_bcs_routine = needs_bcs_routine || (!zfin[3 + i] && ibc_of(d->scal_jmin[i], d->scal_jmax[i]) != 0);
+    for (int i = 0; i < ns; ++i) needs_bcs_routine = needs_bcs_routine || (!zfin[3 + i] && ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]) != 0);
     const bool early_finish = grad_final && (scal_dirichlet || !needs_bcs_routine);
     if (early_finish)
         for (Rank &R : d->rk) finish(R);
@@ -655,7 +603,7 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
             const double *ph[2] = {R.lo[S_P], R.hi[S_P]};
             ok(tlab_internal_zslab_gradient_final_z(R.zplan, nx, ny, R.txc[0], ph, R.tail_left, R.head_right, R.q[2], R.hq[2], tdte, kco, scale),
                "tlab_zslab_gradient_final_z");
-            if (int ibc = ibc_of(d->flow_jmin[2], d->flow_jmax[2])) wall_fix(R, R.q[2], R.hq[2], ibc);
+            if (int ibc = ibc_of(d->bcs.flow_jmin[2], d->bcs.flow_jmax[2])) wall_fix(R, R.q[2], R.hq[2], ibc);
         }
     } else {
         for (Rank &R : d->rk) zpartial(d, R, 2, R.txc[0], S_P, nullptr, 0, 0.0, R.txc[3], 0);
@@ -665,7 +613,7 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     // Neumann scalars the z pass finished: their wall planes
     for (int i = 0; i < ns; ++i)
         if (zfin[3 + i])
-            if (int ibc = ibc_of(d->scal_jmin[i], d->scal_jmax[i]))
+            if (int ibc = ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]))
                 for (Rank &R : d->rk) wall_fix(R, R.s[i], R.hs[i], ibc);
 }
 
@@ -677,21 +625,6 @@ tlab_dns_t dns_handle(D *d, Rank &R) {
         ok(tlab_dns_set_slab(R.dns, R.r * d->kmax), "tlab_dns_set_slab");
     }
     return R.dns;
-}
-
-template <class F>
-int guarded(F f) {
-    try {
-        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
-        f();
-        return TLAB_OK;
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
 }
 
 }  // namespace
@@ -724,8 +657,7 @@ int tlab_slab_dns_create(tlab_slab_dns_t *out, const tlab_slab_transport *tr, tl
         d->P = P; d->nx = nx; d->ny = ny; d->nzt = nz_total; d->kmax = nz_total / P; d->nxh = nx / 2 + 1; d->nscal = nscal; d->visc = visc;
         d->npage = (long long)nx * ny; d->n = d->npage * d->kmax;
         if (nscal) d->schmidt.assign(schmidt, schmidt + nscal);
-        d->scal_jmin.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
-        d->scal_jmax.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
+        d->bcs.all_dirichlet(nscal);
         // kx ranges of the pencils: [ioff[r], ioff[r] + nxl[r])
         const int base = d->nxh / P, rem = d->nxh % P;
         for (int r = 0; r < P; ++r) {
@@ -793,14 +725,8 @@ int tlab_slab_dns_destroy(tlab_slab_dns_t d) {
 
 int tlab_slab_dns_bind(tlab_slab_dns_t d, int l, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc) {
     return guarded([&] {
-        if (!d || l < 0 || l >= (int)d->rk.size() || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs))) throw Fail(TLAB_EINVAL, "tlab_slab_dns_bind: bad arguments");
-        Rank &R = d->rk[l];
-        R.q.assign(q, q + 3); R.hq.assign(hq, hq + 3); R.txc.assign(txc, txc + 9);
-        R.s.assign(s, s + d->nscal); R.hs.assign(hs, hs + d->nscal);
-        for (const std::vector<double *> *v : {&R.q, &R.s, &R.hq, &R.hs, &R.txc})
-            for (double *p : *v)
-                if (!p) throw Fail(TLAB_EINVAL, "tlab_slab_dns_bind: null array");
-        R.bound = true;
+        if (!d || l < 0 || l >= (int)d->rk.size()) throw Fail(TLAB_EINVAL, "tlab_slab_dns_bind: bad arguments");
+        bind_arrays("tlab_slab_dns_bind", d->nscal, d->rk[l], q, s, hq, hs, txc);
     });
 }
 
@@ -820,16 +746,8 @@ long long tlab_slab_dns_info(tlab_slab_dns_t d, int what) {
 
 int tlab_slab_dns_set_bcs(tlab_slab_dns_t d, const int *flow_jmin, const int *flow_jmax, const int *scal_jmin, const int *scal_jmax) {
     return guarded([&] {
-        if (!d || !flow_jmin || !flow_jmax || (d->nscal > 0 && (!scal_jmin || !scal_jmax))) throw Fail(TLAB_EINVAL, "tlab_slab_dns_set_bcs: bad arguments");
-        auto valid = [](int t) { return t == TLAB_DNS_BCS_DIRICHLET || t == TLAB_DNS_BCS_NEUMANN; };
-        for (int i = 0; i < 3; ++i)
-            if (!valid(flow_jmin[i]) || !valid(flow_jmax[i])) throw Fail(TLAB_EINVAL, "tlab_slab_dns_set_bcs: type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN");
-        for (int i = 0; i < d->nscal; ++i)
-            if (!valid(scal_jmin[i]) || !valid(scal_jmax[i])) throw Fail(TLAB_EINVAL, "tlab_slab_dns_set_bcs: type must be DNS_BCS_DIRICHLET or DNS_BCS_NEUMANN");
-        if (flow_jmin[1] != TLAB_DNS_BCS_DIRICHLET || flow_jmax[1] != TLAB_DNS_BCS_DIRICHLET)
-            throw Fail(TLAB_EUNSUPPORTED, "tlab_slab_dns_set_bcs: the wall-normal velocity must be Dirichlet (impermeable walls; the pressure BCs assume v = 0)");
-        for (int i = 0; i < 3; ++i) { d->flow_jmin[i] = flow_jmin[i]; d->flow_jmax[i] = flow_jmax[i]; }
-        for (int i = 0; i < d->nscal; ++i) { d->scal_jmin[i] = scal_jmin[i]; d->scal_jmax[i] = scal_jmax[i]; }
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_slab_dns_set_bcs: bad arguments");
+        d->bcs.set("tlab_slab_dns_set_bcs", d->nscal, flow_jmin, flow_jmax, scal_jmin, scal_jmax);
     });
 }
 
@@ -879,9 +797,9 @@ int tlab_slab_dns_substep(tlab_slab_dns_t d, double dte, double kco, int scale_t
         if (!d || !(dte > 0.0)) throw Fail(TLAB_EINVAL, "tlab_slab_dns_substep: bad arguments");
         rhs_halo(d, dte, true, dte, kco, scale_tendencies);
         // DNS_BOUNDS_LIMIT (dns_local.f90:67-90) on the updated scalars: a pass of its own per field (the z pass that finishes them has no bounds epilogue)
-        for (int i = 0; i < (int)d->clip_on.size(); ++i)
-            if (d->clip_on[i])
-                for (Rank &R : d->rk) ok(tlab_pw_clip(R.s[i], d->clip_lo[i], d->clip_hi[i], d->n), "tlab_pw_clip");
+        for (int i = 0; i < (int)d->bounds.on.size(); ++i)
+            if (d->bounds.on[i])
+                for (Rank &R : d->rk) ok(tlab_pw_clip(R.s[i], d->bounds.lo[i], d->bounds.hi[i], d->n), "tlab_pw_clip");
     });
 }
 
@@ -894,10 +812,7 @@ int tlab_slab_dns_time_courant(tlab_slab_dns_t d, double cfla, double cfld, doub
         for (int l = 0; l < L; ++l) ok(tlab_time_courant(dns_handle(d, d->rk[l]), d->rk[l].q.data(), cfla, cfld, &v[(size_t)2 * l], nullptr), "tlab_time_courant");
         tck(d->tr.allreduce(d->tr.ctx, v.data(), 2, 0), "allreduce");            // MPI_MAX, time.f90:522
         pmax[0] = v[0]; pmax[1] = v[1];
-        if (dtime) {
-            const double dtc = pmax[0] > 0.0 ? cfla / pmax[0] : 1.0e300, dtd = pmax[1] > 0.0 ? cfld / pmax[1] : 1.0e300;
-            *dtime = cfla > 0.0 ? std::min(dtc, dtd) : 0.0;
-        }
+        if (dtime) *dtime = courant_dtime(cfla, cfld, pmax);
     });
 }
 
@@ -976,26 +891,9 @@ int tlab_slab_dns_dilatation_bounds(tlab_slab_dns_t d, double *dil_min, double *
 }
 
 int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi) {
-    (void)tlab_internal_deferred_flush();
-    if (!d) { tlab_set_error("tlab_slab_dns_set_scalar_bounds: null handle"); return TLAB_EINVAL; }
-    std::vector<char> on;
-    std::vector<double> blo, bhi;
-    if (!tlab_internal_check_bounds("tlab_slab_dns_set_scalar_bounds", d->nscal, n, active, lo, hi, on, blo, bhi)) return TLAB_EINVAL;
-    d->clip_on.swap(on); d->clip_lo.swap(blo); d->clip_hi.swap(bhi);
-    return TLAB_OK;
+    return set_scalar_bounds("tlab_slab_dns_set_scalar_bounds", d, n, active, lo, hi);
 }
 
 }  // extern "C"
 
-// deferred.cpp: the arrays of the ONE local rank of a Fortran / MPI host (several local ranks -- loopback runs -- have no single DAXPY partner)
-bool tlab_internal_slab_bound(tlab_slab_dns_t d, double *const **q, double *const **s, double *const **hq, double *const **hs, int *nscal, long long *n) {
-    if (!d || d->rk.size() != 1 || !d->rk[0].bound) return false;
-    *q = d->rk[0].q.data(); *s = d->rk[0].s.data(); *hq = d->rk[0].hq.data(); *hs = d->rk[0].hs.data();
-    *nscal = d->nscal; *n = d->n;
-    return true;
-}
-// deferred.cpp: does the driver limit scalars of its own?  And the bounds of a recorded substep, put in place for the one fused call and taken back
-bool tlab_internal_slab_has_bounds(tlab_slab_dns_t d) { return d && !d->clip_on.empty(); }
-void tlab_internal_slab_swap_bounds(tlab_slab_dns_t d, std::vector<char> &on, std::vector<double> &lo, std::vector<double> &hi) {
-    d->clip_on.swap(on); d->clip_lo.swap(lo); d->clip_hi.swap(hi);
-}
+bool tlab_internal_slab_bound(tlab_slab_dns_t d, tlab_bound_fields *out) { return bound_fields(d, out); }

@@ -34,12 +34,9 @@
 #include "../../include/tlab_amd.h"
 #include "chunked.hpp"
 #include "device_tables.hpp"
+#include "driver_common.hpp"
 #include "plan.hpp"
 #include "profile.hpp"
-
-extern hipStream_t tlab_current_stream();
-extern void tlab_set_error(const std::string &s);
-extern bool tlab_device_ready();
 
 namespace tlab {
 
@@ -413,11 +410,6 @@ struct tlab_zslab_plan {
 
 namespace {
 
-struct Fail : std::runtime_error {
-    int code;
-    Fail(int c, const std::string &s) : std::runtime_error(s), code(c) {}
-};
-
 typedef long double ld;
 
 // slab-level spikes of the slab that starts at global row k0: V = T_loc^-1 e_0, W = T_loc^-1 (-c_last e_last)
@@ -481,21 +473,6 @@ void build_system(tlab_zslab_plan &P, const TriDiag &G, ZSysHost &out) {
     out.aSn = aSn; out.binvn = (double)((ld)1 / (ld)betan);
 }
 
-template <class F>
-int guard(F &&f) {
-    try {
-        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
-        f();
-        return TLAB_OK;
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    }
-}
-
 template <int M, int MODE>
 void launch_m(int phase, int C, const ZSlabArgs &a, hipStream_t st) {
     const long long tiles = (a.nlines + 63) / 64;
@@ -555,20 +532,10 @@ ZSlabArgs base_args(const tlab_zslab_plan &P, int nx, int ny) {
 
 }  // namespace
 
-int tlab_internal_zslab_partial_z(tlab_zslab_plan_t P, int phase, int nx, int ny, const double *u, const double *const *u_halo, const double *ub,
-                                  const double *const *ub_halo, double scale, double *head, double *tail, const double *tail_left,
-                                  const double *head_right, double *result, int acc);
-int tlab_internal_zslab_burgers_z_n(tlab_zslab_plan_t P, int phase, int nx, int ny, int nf, const double *nu, const double *const *s,
-                                    const double *const *s_lo, const double *const *s_hi, const double *vel, double *head, double *tail,
-                                    const double *tail_left, const double *head_right, double *const *result, int acc, const int *fin, double dte,
-                                    double kco, int scale);
-int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, const double *p, const double *const *p_halo, const double *tail_left,
-                                         const double *head_right, double *q, double *h, double dte, double kco, int scale);
-
 extern "C" {
 
 int tlab_zslab_plan_create(tlab_zslab_plan_t *out, tlab_fdm_plan_t gz, int kmax, int koffset, int chunk) {
-    return guard([&] {
+    return guarded([&] {
         if (!out || !gz) throw Fail(TLAB_EINVAL, "tlab_zslab_plan_create: null argument");
         const int nz = gz->t.n;
         if (!gz->t.periodic) throw Fail(TLAB_EUNSUPPORTED, "z-slab operators: the decomposed direction must be periodic");
@@ -611,7 +578,7 @@ int tlab_zslab_partial_z(tlab_zslab_plan_t P, int phase, int nx, int ny, const d
 int tlab_internal_zslab_partial_z(tlab_zslab_plan_t P, int phase, int nx, int ny, const double *u, const double *const *u_halo, const double *ub,
                                   const double *const *ub_halo, double scale, double *head, double *tail, const double *tail_left,
                                   const double *head_right, double *result, int acc) {
-    return guard([&] {
+    return guarded([&] {
         if (!P || !u || nx < 1 || ny < 1 || (phase != 1 && phase != 2)) throw Fail(TLAB_EINVAL, "tlab_zslab_partial_z: bad arguments");
         ZSlabArgs a = base_args(*P, nx, ny);
         a.in0 = u; a.in0b = ub; a.scale = scale;
@@ -632,7 +599,7 @@ extern "C" {
 
 int tlab_zslab_burgers_z(tlab_zslab_plan_t P, int phase, int nx, int ny, double nu, const double *s, const double *vel, double *head,
                          double *tail, const double *tail_left, const double *head_right, double *result, int acc) {
-    return guard([&] {
+    return guarded([&] {
         if (!P || !s || nx < 1 || ny < 1 || (phase != 1 && phase != 2)) throw Fail(TLAB_EINVAL, "tlab_zslab_burgers_z: bad arguments");
         ZSlabArgs a = base_args(*P, nx, ny);
         a.in0 = s; a.nu = nu;
@@ -659,7 +626,7 @@ int tlab_internal_zslab_burgers_z_n(tlab_zslab_plan_t P, int phase, int nx, int 
                                     const double *const *s_lo, const double *const *s_hi, const double *vel, double *head, double *tail,
                                     const double *tail_left, const double *head_right, double *const *result, int acc, const int *fin, double dte,
                                     double kco, int scale) {
-    return guard([&] {
+    return guarded([&] {
         if (!P || !s || !nu || nf < 1 || nf > 4 || nx < 1 || ny < 1 || (phase != 1 && phase != 2)) throw Fail(TLAB_EINVAL, "tlab_zslab_burgers_z_n: bad arguments");
         ZSlabArgs a = base_args(*P, nx, ny);
         a.nf = nf;
@@ -705,7 +672,7 @@ int tlab_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, const doubl
 
 int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, const double *p, const double *const *p_halo, const double *tail_left,
                                          const double *head_right, double *q, double *h, double dte, double kco, int scale) {
-    return guard([&] {
+    return guarded([&] {
         if (!P || !p || !tail_left || !head_right || !q || !h || q == h) throw Fail(TLAB_EINVAL, "tlab_zslab_gradient_final_z: bad arguments");
         ZSlabArgs a = base_args(*P, nx, ny);
         a.in0 = p; a.tail_left = tail_left; a.head_right = head_right; a.out0 = h;
