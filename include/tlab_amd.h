@@ -327,6 +327,39 @@ int tlab_dns_set_fusion(tlab_dns_t d, int on);
  * kernels of a run without bounds, the results bit for bit.  TLAB_EINVAL: n > nscal, a NaN bound, lo > hi.  tlab_time_substep_incompressible_explicit
  * applies the bounds (in the epilogue of the kernel that finishes each scalar); tlab_rhs_global_incompressible_1 does not update s and does not. */
 int tlab_dns_set_scalar_bounds(tlab_dns_t d, int n, const int *active, const double *lo, const double *hi);
+/* Buffer zones, [BufferZone] Type = relaxation (tools/dns/boundary_buffer.f90): the sponge layer h = h - tau(jloc) (a - ref) on the size planes next
+ * to Jmin (offset 0) or Jmax (offset ny - size) (RELAX_BLOCK, :463-490).  The flow blocks act on (q, hq) inside the RHS, between the last Burgers sum
+ * and the pressure forcing, so that the term is projected (rhs_global_incompressible_1.f90:170-172); the scalar blocks act on (s, hs) in the substep,
+ * after the RHS with its wall BCs and before the update (time.f90:628-630).  Jmin goes before Jmax.
+ *   end: TLAB_BUFFER_JMIN / _JMAX (_IMIN / _IMAX: TLAB_EUNSUPPORTED, x is periodic here); group: TLAB_BUFFER_FLOW (3 fields) / _SCAL (nscal fields);
+ *   tau: HOST, (size, nfields) column-major, see the tau routine below; ref: HOST, (nx, size, nz, nfields), copied into device memory the driver owns.
+ *   size = 0 or tau = NULL switches that block off; with every block off the driver launches the kernels of a run without zones, the results bit for bit.
+ *   TLAB_EINVAL: nfields other than 3 / nscal, size = 1 (the reference allocates tau and never sets it there, :360), size > ny, NaN in tau.
+ * The single-domain driver applies them on both of its routes: the flow blocks in one zone launch between the fused Burgers launches; Dirichlet
+ * scalars in the same launch, their wall planes inside a zone redone afterwards (h = 0 - tau (s - ref), update, bounds: zone bytes only); scalars with
+ * Neumann walls or a surface model in the reference's literal order (wall planes of hs, zone launch, update: one more pass over them).
+ * The type routine mirrors the ini key: TLAB_BUFFER_NONE (switches every block off), _RELAX; _FILTER and _BOTH: TLAB_EUNSUPPORTED.
+ * The z-slab and the x/z pencil drivers carry them too (their own setters below). */
+#define TLAB_BUFFER_NONE 0
+#define TLAB_BUFFER_RELAX 1
+#define TLAB_BUFFER_FILTER 2
+#define TLAB_BUFFER_BOTH 3
+#define TLAB_BUFFER_IMIN 1
+#define TLAB_BUFFER_IMAX 2
+#define TLAB_BUFFER_JMIN 3
+#define TLAB_BUFFER_JMAX 4
+#define TLAB_BUFFER_FLOW 0
+#define TLAB_BUFFER_SCAL 1
+int tlab_dns_set_buffer_type(tlab_dns_t d, int type);
+int tlab_dns_set_buffer_zone(tlab_dns_t d, int end, int group, int size, int nfields, const double *tau, const double *ref);
+/* INI_BLOCK's strength of one field (:359-371), host arithmetic only: with L = nodes[offset + size - 1] - nodes[offset],
+ * form 1 (Jmin): tau[jloc] = strength ((nodes[offset + size - 1] - nodes[j]) / L) ** sigma; form 2 (Jmax): strength ((nodes[j] - nodes[offset]) / L) ** sigma,
+ * j = offset + jloc, in the reference's operation order.  nodes: n HOST values; tau_out: size HOST values.  size < 2: TLAB_EINVAL. */
+int tlab_buffer_tau(int n, const double *nodes, int offset, int size, double strength, double sigma, int form, double *tau_out);
+/* BOUNDARY_BUFFER_RELAX_FLOW (:440-459) and BOUNDARY_BUFFER_RELAX_SCAL (:399-418), incompressible branch, on their own: the driver's blocks applied
+ * to HOST arrays of DEVICE pointers (q[3], hq[3]; s[nscal], hs[nscal]).  Planes outside the zones are neither read nor written. */
+int tlab_dns_buffer_relax_flow(tlab_dns_t d, double *const *q, double *const *hq);
+int tlab_dns_buffer_relax_scal(tlab_dns_t d, double *const *s, double *const *hs);
 /* Start of a Runge-Kutta step: TIME_RUNGEKUTTA sets hq = 0, hs = 0 there (tools/dns/time.f90:212-216).  Instead of filling the arrays,
  * tell the driver: the next tlab_rhs_global_incompressible_1 / tlab_time_substep_incompressible_explicit treats them as zero (its first
  * operator launch overwrites instead of accumulating), whatever they contain. */
@@ -355,6 +388,13 @@ int tlab_deferred_flush(void);
  * bounds (tlab_deferred_stats counts[0]; tlab_deferred_clip_stats counts[0]).  A clip of another array, before the DAXPY of its field, a second clip of one field, or bounds of a driver that has
  * its own (tlab_*_set_scalar_bounds) make the record run literally, in the order of the calls.  Off: tlab_pw_clip. */
 int tlab_deferred_clip(long long n, double lo, double hi, double *x);
+/* BOUNDARY_BUFFER_RELAX_SCAL of an unchanged host (time.f90:628-630, through tlab_amd/fortran/boundary_buffer_device.sed), on the arrays of the
+ * driver's last deferred RHS.  The sequence RHS, relaxation, DAXPY x (3 + ns), [clips], [DSCAL x (3 + ns)] runs as ONE fused substep with the
+ * driver's scalar blocks in it; the RHS applies the flow blocks itself.  A relaxation after a DAXPY, a second one, or one on a driver without scalar
+ * zones makes the record run literally, in call order.  A record WITHOUT the relaxation is replayed without the scalar blocks, fused or literal.
+ * The relax statistics give counts[2]: fused substeps that carried a recorded relaxation, relaxations executed on their own. */
+int tlab_deferred_relax_scal(tlab_dns_t d);
+int tlab_deferred_relax_stats(long long *counts);
 /* counts[6]: fused substeps run, sequences executed literally, begin_steps taken from zero fills, eager axpy, eager scal, eager zero fills */
 int tlab_deferred_stats(long long *counts);
 /* counts[2]: fused substeps that carried recorded clips (of counts[0] above), clips executed on their own (tlab_pw_clip) */
@@ -445,7 +485,8 @@ int tlab_minmax_any(const double *a, long long n, double *amn, double *amx);
 /* RHS_GLOBAL_INCOMPRESSIBLE_1()   tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
  * it works on the module arrays q, s, hq, hs, txc and on dte).  q[3] = u,v,w; s[nscal]; hq[3], hs[nscal] are
  * accumulated into; txc[9] = tmp1..tmp9, each of isize_txc_field = (nx+2)*ny*nz doubles.  HOST arrays of DEVICE pointers.
- * Convective form, RhsMode = combined, remove_divergence = yes, no buffer zone / IBM / anelastic terms. */
+ * Convective form, RhsMode = combined.  The flow blocks of the relaxation buffer zones at Jmin / Jmax are applied in the reference's place and the
+ * scalars are not relaxed here, as in the reference's RHS; zones at Imin / Imax and filter zones are refused where they are set.  No IBM terms. */
 int tlab_rhs_global_incompressible_1(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq,
                                      double *const *hs, double *const *txc);
 
@@ -525,6 +566,9 @@ int tlab_pencil_dns_destroy(tlab_pencil_dns_t d);
 int tlab_pencil_dns_bind(tlab_pencil_dns_t d, int l, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc);
 long long tlab_pencil_dns_info(tlab_pencil_dns_t d, int what);   /* 0 imax, 1 kmax, 2 kmax / npro_i, 3 doubles of a txc array, 4 nlocal, 5 first local rank */
 int tlab_pencil_dns_set_bcs(tlab_pencil_dns_t d, const int *flow_jmin, const int *flow_jmax, const int *scal_jmin, const int *scal_jmax);
+/* buffer zones, as tlab_dns_set_buffer_zone, for the local rank l with ref for that rank's box (imax, size, kmax, nfields): local, no exchange.
+ * tlab_pencil_dns_rhs applies the flow blocks before the pressure forcing, tlab_pencil_dns_substep the scalar blocks before its update. */
+int tlab_pencil_dns_set_buffer_zone(tlab_pencil_dns_t d, int l, int end, int group, int size, int nfields, const double *tau, const double *ref);
 /* scalar bounds limiting, as tlab_dns_set_scalar_bounds: applied by tlab_pencil_dns_substep in the update pass of each limited scalar */
 int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi);
 int tlab_pencil_dns_begin_step(tlab_pencil_dns_t d);
@@ -576,6 +620,10 @@ int tlab_slab_dns_begin_step(tlab_slab_dns_t d);                 /* as tlab_dns_
 int tlab_deferred_slab_rhs(tlab_slab_dns_t d, double dte);
 int tlab_deferred_pencil_rhs(tlab_pencil_dns_t d, double dte);
 int tlab_slab_dns_set_remove_divergence(tlab_slab_dns_t d, int on);
+/* buffer zones, as tlab_dns_set_buffer_zone, for the local rank l (0 .. nlocal-1) with ref for that rank's box (nx, size, kmax, nfields): y is never
+ * split, so the relaxation is local and needs no exchange.  The flow blocks act before hq is read for the pressure forcing, the scalar blocks after
+ * the wall BCs of hs and before the update (scalars under a zone take a separate update pass). */
+int tlab_slab_dns_set_buffer_zone(tlab_slab_dns_t d, int l, int end, int group, int size, int nfields, const double *tau, const double *ref);
 /* scalar bounds limiting, as tlab_dns_set_scalar_bounds: applied by tlab_slab_dns_substep, one pass per limited scalar after the substep */
 int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi);
 /* as tlab_dns_set_surface_bcs: the dynamic surface model of the scalars on z-slabs.  The plane average of BOUNDARY_BCS_SURFACE_Y (AVG1V2D,

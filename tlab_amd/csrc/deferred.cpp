@@ -40,6 +40,11 @@ struct Driver {
     std::function<int(double dte)> rhs;
     std::function<int(double dte, double kco, int scale)> substep;
     ScalarBounds *bounds = nullptr;
+    // one domain only (empty otherwise): the driver's handle, BOUNDARY_BUFFER_RELAX_SCAL on the recorded arrays, and the switch that makes the
+    // driver's substep apply its scalar buffer zones (returns the old setting)
+    tlab_dns_t dns = nullptr;
+    std::function<int()> relax_scal;
+    std::function<bool(bool)> scal_zones;
 };
 struct Pending {
     bool rhs = false;
@@ -53,12 +58,15 @@ struct Pending {
     std::vector<char> clp;                        // per scalar: clipped after its DAXPY (DNS_BOUNDS_LIMIT), with clo / chi
     std::vector<double> clo, chi;
     int nclp = 0;
+    bool relax = false;                           // tlab_deferred_relax_scal recorded straight after the RHS (time.f90:628-630)
     std::vector<Range> zeros;                     // `hq = 0` of the start of a step, not yet executed
 };
 Pending g_p;
 bool g_on = false, g_busy = false;
 long long g_stat[6] = {0, 0, 0, 0, 0, 0};        // fused substeps, literal flushes, begin_steps, eager axpy, eager scal, eager zero
 long long g_clip_stat[2] = {0, 0};                // fused substeps that carried recorded clips, clips executed on their own
+long long g_relax_stat[2] = {0, 0};               // fused substeps that carried a recorded scalar relaxation, relaxations executed on their own
+Driver g_last;                                    // the driver of the last tlab_deferred_rhs (a relaxation that meets no record runs on its arrays)
 
 struct Busy {
     bool was;
@@ -109,7 +117,10 @@ int run_substep(Pending &p, double kco, int scale) {
     ScalarBounds b;
     if (p.nclp) { b.on = p.clp; b.lo = p.clo; b.hi = p.chi; }
     p.drv.bounds->swap(b);
+    // ... and the scalar buffer zones of the driver act in it only when the record holds the relaxation: RHS + DAXPY alone does not relax the scalars
+    const bool was = p.drv.scal_zones ? p.drv.scal_zones(p.relax) : true;
     const int rc = p.drv.substep(p.dte, kco, scale);
+    if (p.drv.scal_zones) (void)p.drv.scal_zones(was);
     p.drv.bounds->swap(b);
     return rc;
 }
@@ -128,9 +139,11 @@ void record(Driver drv, double dte, int ns, long long n, double *const *q, doubl
     p.nupd = p.nscl = 0;
     p.clp.assign(ns, 0); p.clo.assign(ns, 0.0); p.chi.assign(ns, 0.0);
     p.nclp = 0;
+    p.relax = false;
 }
 
-int flush_impl() {
+// whole_ok = false: the record is cut short by a call that does not belong to the fused substep; it counts as a literal run
+int flush_impl(bool whole_ok = true) {
     if (g_busy) return TLAB_OK;
     Busy b;
     if (!g_p.rhs) return run_zeros_eagerly();
@@ -147,9 +160,10 @@ int flush_impl() {
         }
     }
     if (rc != TLAB_OK) return rc;
-    if (p.nupd == p.nf && (p.nscl == 0 || p.nscl == p.nf)) {      // the whole substep, as the patched host would have called it
+    if (whole_ok && p.nupd == p.nf && (p.nscl == 0 || p.nscl == p.nf)) {      // the whole substep, as the patched host would have called it
         ++g_stat[0];
         if (p.nclp) ++g_clip_stat[0];
+        if (p.relax) ++g_relax_stat[0];
         return run_substep(p, p.nscl ? p.kco : 1.0, p.nscl ? 1 : 0);
     }
     ++g_stat[1];
@@ -160,6 +174,7 @@ int flush_impl() {
         return rc;
     }
     rc = p.drv.rhs(p.dte);
+    if (p.relax && rc == TLAB_OK) { ++g_relax_stat[1]; rc = p.drv.relax_scal(); }      // (recorded before every DAXPY)
     for (int f = 0; f < p.nf && rc == TLAB_OK; ++f)
         if (p.upd[f]) rc = tlab_pw_rk_update(p.y[f], p.x[f], p.dte, 1.0, 0, p.n);
     for (int is = 0; is + 3 < p.nf && rc == TLAB_OK; ++is)          // (a clip was recorded after the DAXPY of its field only)
@@ -212,6 +227,35 @@ int tlab_deferred_clip_stats(long long *counts) {
     return TLAB_OK;
 }
 
+int tlab_deferred_relax_stats(long long *counts) {
+    if (!counts) return TLAB_EINVAL;
+    counts[0] = g_relax_stat[0];
+    counts[1] = g_relax_stat[1];
+    return TLAB_OK;
+}
+
+// BOUNDARY_BUFFER_RELAX_SCAL of an unchanged host (time.f90:628-630, through tlab_amd/fortran/boundary_buffer_device.sed).  Straight after the recorded
+// RHS of this driver, once, with scalar zones set: recorded, and the record runs as the one fused substep with the scalar blocks in it.  After a
+// DAXPY, a second time, or without scalar zones: the record runs literally first, then the relaxation on its own, in call order.
+int tlab_deferred_relax_scal(tlab_dns_t d) {
+    if (!d) { tlab_set_error("tlab_deferred_relax_scal: null handle"); return TLAB_EINVAL; }
+    if (g_on && g_p.rhs && g_p.drv.dns == d && !g_p.relax && g_p.nupd == 0 && g_p.nscl == 0 && tlab_internal_dns_has_scal_zones(d)) {
+        g_p.relax = true;
+        return TLAB_OK;
+    }
+    Driver drv = (g_p.rhs && g_p.drv.dns == d) ? g_p.drv : g_last;
+    if (g_on) {
+        const int rc = flush_impl(false);
+        if (rc != TLAB_OK) return rc;
+    }
+    if (drv.dns != d || !drv.relax_scal) {
+        tlab_set_error("tlab_deferred_relax_scal: no tlab_deferred_rhs of this driver came before (its arrays are not known)");
+        return TLAB_EINVAL;
+    }
+    ++g_relax_stat[1];
+    return drv.relax_scal();
+}
+
 int tlab_deferred_zero(double *a, long long n) {
     if (!a || n < 0) { tlab_set_error("tlab_deferred_zero: bad arguments"); return TLAB_EINVAL; }
     if (!g_on) { ++g_stat[5]; return tlab_pw_fill(a, 0.0, n); }
@@ -224,11 +268,10 @@ int tlab_deferred_zero(double *a, long long n) {
 }
 
 int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc) {
-    if (!g_on) return tlab_rhs_global_incompressible_1(d, dte, q, s, hq, hs, txc);
     if (!d || !q || !hq || !txc || dte <= 0.0) { tlab_set_error("tlab_deferred_rhs: bad arguments"); return TLAB_EINVAL; }
     const int ns = tlab_internal_dns_nscal(d);
     if (ns > 0 && (!s || !hs)) { tlab_set_error("tlab_deferred_rhs: bad arguments"); return TLAB_EINVAL; }
-    if (g_p.rhs) {
+    if (g_on && g_p.rhs) {
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }
@@ -244,6 +287,11 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
                                                          T.data());
     };
     drv.bounds = tlab_internal_dns_bounds(d);
+    drv.dns = d;
+    drv.relax_scal = [=] { return tlab_dns_buffer_relax_scal(d, ns ? S.data() : nullptr, ns ? HS.data() : nullptr); };
+    drv.scal_zones = [d](bool on) { return tlab_internal_dns_scal_zones_in_substep(d, on); };
+    g_last = drv;
+    if (!g_on) return drv.rhs(dte);
     record(std::move(drv), dte, ns, tlab_internal_dns_points(d), q, s, hq, hs);
     return TLAB_OK;
 }

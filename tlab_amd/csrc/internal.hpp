@@ -88,6 +88,10 @@ int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, co
 long long tlab_internal_dns_points(tlab_dns_t d);      // deferred.cpp
 int tlab_internal_dns_nscal(tlab_dns_t d);
 tlab::ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d);      // deferred.cpp: the driver's own scalar bounds (tlab_dns_set_scalar_bounds)
+// deferred.cpp: does the driver hold scalar buffer zones, and the switch that makes its substep apply them (returns the old setting)
+bool tlab_internal_dns_has_flow_zones(tlab_dns_t d);      // slab.cpp: the zones of a rank live in its single-domain handle
+bool tlab_internal_dns_has_scal_zones(tlab_dns_t d);
+bool tlab_internal_dns_scal_zones_in_substep(tlab_dns_t d, bool on);
 // shared by the three drivers: n entries (<= nscal) of active / lo / hi checked, the bounds of the active ones returned (on[is] = 0 otherwise)
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi);

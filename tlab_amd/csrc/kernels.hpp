@@ -185,6 +185,15 @@ hipError_t launch_final_update(double *q, double *h, const double *g, const doub
 hipError_t launch_clip(double *a, double lo, double hi, long long n, hipStream_t st);
 hipError_t launch_rk_update(double *q, double *h, double dte, double kco, int scale, long long n, hipStream_t st, const ClipBounds *clip = nullptr);
 hipError_t launch_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz, hipStream_t st);
+// RELAX_BLOCK of a J zone (boundary_buffer.f90:463-490) for nf <= 4 fields: h[f] -= tau[f][jloc] (a[f] - ref[f]) on the planes [offset, offset + size);
+// ref: device, (nx, size, nz) per field, and tau: device, size doubles per field, both starting at the first field of the launch
+hipError_t launch_buffer_relax(int nf, double *const *h, const double *const *a, const double *ref, const double *tau, int nx, int ny, int nz,
+                               int offset, int size, hipStream_t st);
+// ... and the tail of the substep on the plane jloc of the zone (k_buffer_relax<.., PLANE>): h = bc - tau (s - ref); s = clip(s + dte h); h *= kco.
+// bc (may be NULL) / bc[f] NULL: zero; clip (may be NULL) / clip[f] NULL: no bounds
+hipError_t launch_buffer_relax_plane(int nf, double *const *h, double *const *s, const double *ref, const double *tau, const double *const *bc,
+                                     const ClipBounds *const *clip, double dte, double kco, int scale, int nx, int ny, int nz, int offset, int size,
+                                     int jloc, hipStream_t st);
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,

@@ -328,6 +328,17 @@ void finish_velocities(D *d) {
 }
 
 // tools/dns/rhs_global_incompressible_1.f90:98-398
+// BOUNDARY_BUFFER_RELAX_FLOW (rhs_global_incompressible_1.f90:170-172) / _SCAL (time.f90:628-630): y is never split, the blocks of a rank live in its
+// single-domain handle (tlab_pencil_dns_set_buffer_zone) and act on its box; no exchange
+void relax_flow(D *d) {
+    for (Rank &R : d->rk)
+        if (R.dns && tlab_internal_dns_has_flow_zones(R.dns)) ok(tlab_dns_buffer_relax_flow(R.dns, R.q.data(), R.hq.data()), "tlab_dns_buffer_relax_flow");
+}
+void relax_scal(D *d) {
+    for (Rank &R : d->rk)
+        if (R.dns && tlab_internal_dns_has_scal_zones(R.dns)) ok(tlab_dns_buffer_relax_scal(R.dns, R.s.data(), R.hs.data()), "tlab_dns_buffer_relax_scal");
+}
+
 void rhs(D *d, double dte) {
     need_bound(d);
     if (tlab_internal_anelastic() || tlab_internal_dealiasing())
@@ -363,6 +374,7 @@ void rhs(D *d, double dte) {
         burgers_t(d, 3, kap, sc, 2, false);
         add3([i](Rank &R) { return R.hs[i]; }, 0, 1, 2);
     }
+    relax_flow(d);                                                                // :170-172
     // pressure (:188-260)
     for (Rank &R : d->rk)
         ok(tlab_pw_axpy3(R.txc[1], R.txc[2], R.txc[3], R.hq[1], R.hq[0], R.hq[2], R.q[1], R.q[0], R.q[2], 1.0 / dte, n), "tlab_pw_axpy3");
@@ -618,6 +630,7 @@ void rhs_overlapped(D *d, double dte) {
     // (the y terms of equation k + 3 write the set of equation k: they must not run before its sum; the list order of `local` guarantees it, every
     // sum of an earlier equation standing before the y term of a later one that reuses its set)
     run_pipeline(d, ops, local);
+    relax_flow(d);                                                                // :170-172
     // pressure (:188-260)
     for (Rank &R : d->rk)
         ok(tlab_pw_axpy3(R.txc[1], R.txc[2], R.txc[3], R.hq[1], R.hq[0], R.hq[2], R.q[1], R.q[0], R.q[2], 1.0 / dte, n), "tlab_pw_axpy3");
@@ -856,6 +869,7 @@ int tlab_pencil_dns_substep(tlab_pencil_dns_t d, double dte, double kco, int sca
         d->fin.on = true; d->fin.dte = dte; d->fin.kco = kco; d->fin.scale = scale_tendencies;
         struct Off { D *d; ~Off() { d->fin.on = false; } } off{d};      // (also when the RHS throws)
         if (d->overlap) rhs_overlapped(d, dte); else rhs(d, dte);
+        relax_scal(d);               // time.f90:628-630: after the RHS with its wall BCs, before the update
         for (Rank &R : d->rk) {      // time.f90:645-664, :272-297
             for (int i = 0; i < 3 && !d->fin.done; ++i) ok(tlab_pw_rk_update(R.q[i], R.hq[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
             for (int i = 0; i < d->nscal; ++i) {      // (+ DNS_BOUNDS_LIMIT, dns_local.f90:67-90, in the same pass where the scalar is limited)
@@ -904,6 +918,14 @@ int tlab_pencil_dns_dilatation_extremes(tlab_pencil_dns_t d, double *dil_min, do
         if (!d || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_dilatation_extremes: bad arguments");
         extremes(d, dil_min, dil_max, loc_min, loc_max);
     });
+}
+
+int tlab_pencil_dns_set_buffer_zone(tlab_pencil_dns_t d, int l, int end, int group, int size, int nfields, const double *tau, const double *ref) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d || l < 0 || l >= (int)d->rk.size()) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_set_buffer_zone: bad handle or local rank");
+        ok(tlab_dns_set_buffer_zone(dns_handle(d, d->rk[l]), end, group, size, nfields, tau, ref), "tlab_dns_set_buffer_zone");
+    }, TLAB_EINVAL);
 }
 
 int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi) {

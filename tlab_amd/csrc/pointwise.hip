@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdint>
 
 #include "kernels.hpp"
 #include "profile.hpp"
@@ -461,6 +462,107 @@ hipError_t launch_set_wall_planes(double *f, const double *pb, const double *pt,
     hipLaunchKernelGGL(k_set_wall_planes_opt, dim3((unsigned)(((long long)nx * nz + 255) / 256)), dim3(256), 0, st, f, pb, pt, nx, ny, nz);
     return CHECK_LAUNCH();
 }
+// RELAX_BLOCK (tools/dns/boundary_buffer.f90:463-490, idir = 2) of up to four fields that share a J zone of [BufferZone] Type = relaxation:
+//   h(:, j, :, f) = h(:, j, :, f) - tau(jloc, f) * (a(:, j, :, f) - ref(:, jloc, :, f)),   j = offset + jloc, jloc = 0 .. size-1
+// in the reference's operation order (no fused multiply-add).  The grid covers the zone's planes only: nothing outside them is read or written.
+// ref is (nx, size, nz) per field, tau a device table of size doubles per field.  V = 2: 16-byte accesses along the x-contiguous rows (nx even,
+// every array 16-byte aligned); V = 1: scalar accesses (an odd nx, which no driver has, or an array that starts on an odd double).
+// PLANE: the whole tail of the substep on ONE plane of the zone, jloc = jp, for scalars whose other planes a Burgers epilogue has finished with
+// zero wall tendencies (rhs.cpp): the reference sets the wall BC of hs first and relaxes afterwards (time.f90:628-630), so there
+//   h = bc - tau (s - ref) ;  s = clip(s + dte h) ;  h = kco h (if scale)        bc: the BC value of the plane ([nx][nz]; NULL: zero, Dirichlet)
+struct BufferZoneArgs {
+    double *h[4], *a[4];
+    const double *ref[4], *tau[4], *bc[4];
+    int clip[4];
+    double lo[4], hi[4];
+};
+template <int V, bool PLANE>
+__global__ void __launch_bounds__(256) k_buffer_relax(BufferZoneArgs A, int nf, int nx, int ny, int offset, int size, long long npts, int jp,
+                                                      double dte, double kco, int scale) {
+    const int nxv = nx / V;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npts; p += stride) {
+        const int ix = (int)(p % nxv) * V;
+        const long long row = p / nxv;
+        const int jloc = PLANE ? jp : (int)(row % size);
+        const long long k = PLANE ? row : row / size;
+        const long long i = ix + (long long)nx * (offset + jloc + (long long)ny * k);      // in the field
+        const long long r = ix + (long long)nx * (jloc + (long long)size * k);             // in the zone's reference
+        for (int f = 0; f < nf; ++f) {
+            const double t = A.tau[f][jloc];
+            double hv[V], av[V], rv[V];
+            if constexpr (V == 2) {
+                const double2 a2 = *reinterpret_cast<const double2 *>(A.a[f] + i), r2 = *reinterpret_cast<const double2 *>(A.ref[f] + r);
+                av[0] = a2.x; av[1] = a2.y; rv[0] = r2.x; rv[1] = r2.y;
+            } else {
+                av[0] = A.a[f][i]; rv[0] = A.ref[f][r];
+            }
+            if constexpr (PLANE) {
+                for (int v = 0; v < V; ++v) hv[v] = A.bc[f] ? A.bc[f][ix + v + (long long)nx * k] : 0.0;
+            } else if constexpr (V == 2) {
+                const double2 h2 = *reinterpret_cast<const double2 *>(A.h[f] + i);
+                hv[0] = h2.x; hv[1] = h2.y;
+            } else {
+                hv[0] = A.h[f][i];
+            }
+            for (int v = 0; v < V; ++v) hv[v] = __dsub_rn(hv[v], __dmul_rn(t, __dsub_rn(av[v], rv[v])));
+            if constexpr (PLANE) {
+                for (int v = 0; v < V; ++v) {
+                    av[v] = av[v] + dte * hv[v];
+                    if (A.clip[f]) av[v] = fmin(fmax(av[v], A.lo[f]), A.hi[f]);
+                    if (scale) hv[v] = kco * hv[v];
+                }
+                if constexpr (V == 2) *reinterpret_cast<double2 *>(A.a[f] + i) = make_double2(av[0], av[1]);
+                else A.a[f][i] = av[0];
+            }
+            if constexpr (V == 2) *reinterpret_cast<double2 *>(A.h[f] + i) = make_double2(hv[0], hv[1]);
+            else A.h[f][i] = hv[0];
+        }
+    }
+}
+static bool buffer_zone_args(BufferZoneArgs &A, int nf, double *const *h, double *const *a, const double *ref, const double *tau, int nx, int nz,
+                             int size) {
+    bool vec = (nx & 1) == 0;
+    const long long zone = (long long)nx * size * nz;
+    for (int f = 0; f < 4; ++f) {
+        const int g = f < nf ? f : 0;
+        A.h[f] = h[g]; A.a[f] = a[g]; A.ref[f] = ref + (long long)g * zone; A.tau[f] = tau + (long long)g * size;
+        A.bc[f] = nullptr; A.clip[f] = 0; A.lo[f] = A.hi[f] = 0.0;
+        vec = vec && (((uintptr_t)A.h[f] | (uintptr_t)A.a[f] | (uintptr_t)A.ref[f]) & 15) == 0;
+    }
+    return vec;
+}
+hipError_t launch_buffer_relax(int nf, double *const *h, const double *const *a, const double *ref, const double *tau, int nx, int ny, int nz,
+                               int offset, int size, hipStream_t st) {
+    if (nf < 1 || nf > 4 || size < 1 || offset < 0 || offset + size > ny || nx < 1 || nz < 1) return hipErrorInvalidValue;
+    BufferZoneArgs A;
+    const bool vec = buffer_zone_args(A, nf, h, const_cast<double *const *>(a), ref, tau, nx, nz, size);      // (a is only read in this form)
+    const long long zone = (long long)nx * size * nz;
+    ProfScope ps("k_buffer_relax", st, 32.0 * (double)zone * nf);
+    const long long npts = vec ? zone / 2 : zone;
+    if (vec) hipLaunchKernelGGL((k_buffer_relax<2, false>), dim3(pw_grid(npts)), dim3(256), 0, st, A, nf, nx, ny, offset, size, npts, 0, 0.0, 1.0, 0);
+    else hipLaunchKernelGGL((k_buffer_relax<1, false>), dim3(pw_grid(npts)), dim3(256), 0, st, A, nf, nx, ny, offset, size, npts, 0, 0.0, 1.0, 0);
+    return CHECK_LAUNCH();
+}
+hipError_t launch_buffer_relax_plane(int nf, double *const *h, double *const *s, const double *ref, const double *tau, const double *const *bc,
+                                     const ClipBounds *const *clip, double dte, double kco, int scale, int nx, int ny, int nz, int offset, int size,
+                                     int jloc, hipStream_t st) {
+    if (nf < 1 || nf > 4 || size < 1 || offset < 0 || offset + size > ny || jloc < 0 || jloc >= size || nx < 1 || nz < 1) return hipErrorInvalidValue;
+    BufferZoneArgs A;
+    bool vec = buffer_zone_args(A, nf, h, s, ref, tau, nx, nz, size);
+    for (int f = 0; f < nf; ++f) {
+        A.bc[f] = bc ? bc[f] : nullptr;
+        vec = vec && ((uintptr_t)A.bc[f] & 15) == 0;
+        if (clip && clip[f]) { A.clip[f] = 1; A.lo[f] = clip[f]->lo; A.hi[f] = clip[f]->hi; }
+    }
+    const long long plane = (long long)nx * nz;
+    ProfScope ps("k_buffer_relax<wall plane>", st, 32.0 * (double)plane * nf);
+    const long long npts = vec ? plane / 2 : plane;
+    if (vec) hipLaunchKernelGGL((k_buffer_relax<2, true>), dim3(pw_grid(npts)), dim3(256), 0, st, A, nf, nx, ny, offset, size, npts, jloc, dte, kco, scale);
+    else hipLaunchKernelGGL((k_buffer_relax<1, true>), dim3(pw_grid(npts)), dim3(256), 0, st, A, nf, nx, ny, offset, size, npts, jloc, dte, kco, scale);
+    return CHECK_LAUNCH();
+}
+
 // Weighted sums over the K rows next to each wall: ob[ix, k] = sum_{j < K} wb[j] a[ix, j, k], ot[ix, k] = sum_{j < K} wt[j] a[ix, ny-1-j, k], for one or
 // two fields at once (a2 / ob2 / ot2 may be NULL).  With wb, wt = the row of the Neumann operator that BOUNDARY_BCS_NEUMANN_Y applies to a finished
 // tendency (its wall value is a linear functional of the line whose weights decay like 0.38^j), this is that wall value without the y-derivative

@@ -54,6 +54,12 @@ struct tlab_dns {
     struct NeuW { double *w = nullptr; int K = 0; bool tried = false; } neuw[4];
     double *wall_planes = nullptr;
     double rb_wall[2] = {1.0, 1.0};
+    // [BufferZone] Type = relaxation: BuffFlowJmin/Jmax, BuffScalJmin/Jmax (boundary_buffer.f90) -- buff[group][end], group 0 flow / 1 scalars,
+    // end 0 Jmin / 1 Jmax; size 0: that block is off.  tau (size, nf) and ref (nx, size, nz, nf) are device memory the driver owns.
+    struct BufferBlock { int size = 0, offset = 0, nf = 0; double *tau = nullptr, *ref = nullptr; } buff[2][2];
+    // the substep applies the scalar blocks (BOUNDARY_BUFFER_RELAX_SCAL, time.f90:628-630); the deferred tail switches this off for the replay of a
+    // record that holds no tlab_deferred_relax_scal: RHS + DAXPY does not relax the scalars, whichever way it is replayed
+    bool scal_zones_in_substep = true;
     unsigned long anel_version = 0;                // change counter of the operator state these mirror (follow_anelastic)
     bool anel_owner = false;                       // this driver switched the operator state on (tlab_dns_set_anelastic): it goes with the driver
     ~tlab_dns() {
@@ -69,6 +75,15 @@ struct tlab_dns {
         if (rib) (void)hipFree(rib);
         for (NeuW &n : neuw) if (n.w) (void)hipFree(n.w);
         if (wall_planes) (void)hipFree(wall_planes);
+        for (auto &g : buff)
+            for (BufferBlock &b : g) free_block(b, false);
+    }
+    // the tables of a block go back; sync: kernels that read them may still be in flight on the library's stream
+    static void free_block(BufferBlock &b, bool sync) {
+        if (sync && (b.tau || b.ref)) (void)hipStreamSynchronize(tlab_current_stream());
+        if (b.tau) (void)hipFree(b.tau);
+        if (b.ref) (void)hipFree(b.ref);
+        b = BufferBlock();
     }
 };
 
@@ -137,6 +152,9 @@ bool neumann_weights(tlab_dns *d, int ibc) {
 long long tlab_internal_dns_points(tlab_dns_t d) { return d ? (long long)d->nx * d->ny * d->nz : 0; }
 int tlab_internal_dns_nscal(tlab_dns_t d) { return d ? d->nscal : 0; }
 ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d) { return &d->bounds; }
+bool tlab_internal_dns_has_flow_zones(tlab_dns_t d) { return d && (d->buff[0][0].size > 0 || d->buff[0][1].size > 0); }
+bool tlab_internal_dns_has_scal_zones(tlab_dns_t d) { return d && d->nscal > 0 && (d->buff[1][0].size > 0 || d->buff[1][1].size > 0); }
+bool tlab_internal_dns_scal_zones_in_substep(tlab_dns_t d, bool on) { const bool was = d->scal_zones_in_substep; d->scal_zones_in_substep = on; return was; }
 
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi) {
@@ -274,6 +292,18 @@ static void burgers_into(tlab_dns_t d, int dir, double nu, const double *s, cons
 // bounds of scalar is, or NULL when it is not limited
 static const tlab::ClipBounds *clip_of(tlab_dns_t d, int is) { return d->bounds.active(is) ? &d->clip_b[is] : nullptr; }
 
+// RELAX_BLOCK of the blocks of one group (0: BOUNDARY_BUFFER_RELAX_FLOW on q, hq; 1: BOUNDARY_BUFFER_RELAX_SCAL on s, hs), Jmin before Jmax, four fields a launch
+static bool buffer_any(tlab_dns_t d, int group) { return d->buff[group][0].size > 0 || d->buff[group][1].size > 0; }
+static void buffer_relax(tlab_dns_t d, int group, double *const *a, double *const *h, hipStream_t st) {
+    for (const tlab_dns::BufferBlock &b : d->buff[group]) {
+        if (b.size == 0) continue;
+        const long long zone = (long long)d->nx * b.size * d->nz;
+        for (int f0 = 0; f0 < b.nf; f0 += 4)
+            hk(launch_buffer_relax(std::min(4, b.nf - f0), h + f0, a + f0, b.ref + f0 * zone, b.tau + (long long)f0 * b.size, d->nx, d->ny, d->nz, b.offset,
+                                   b.size, st), "buffer zone");
+    }
+}
+
 static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs,
                      double *const *txc, bool tail_update, double kco, int scale_tendencies) {
     const int nx = d->nx, ny = d->ny, nz = d->nz;
@@ -335,6 +365,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // ride on the LAST Burgers launch that adds to hs, if that launch is the x one (the wave-per-line kernel has the registers for it; the
     // y/z tile kernels do not, measured).  The directions then run z, y, x instead of x, y, z: the terms are summed in another order, rounding only.
     static const bool finish_off = [] { const char *e = getenv("TLAB_SCALAR_FINISH"); return e && atoi(e) == 0; }();
+    const bool zone_flow = buffer_any(d, 0), zone_scal = tail_update && d->nscal > 0 && d->scal_zones_in_substep && buffer_any(d, 1);
     bool finish_scal = !finish_off && batched && !literal && tail_update && d->nscal > 0 && tlab_internal_burgers_can_finish(1, gx, nx, ny, nz);
     // Neumann scalars can ride too where the fused Neumann tail below applies: the epilogue finishes their interior with zero wall tendencies, and the
     // wall planes follow from weighted sums over the stored tendencies next to the walls (neumann_weights; k_wall_fix) instead of a derivative pass
@@ -361,6 +392,19 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     for (int is = 0; is < d->nscal && !scal_neumann_planes; ++is)
         finish_scal = finish_scal && d->bcs.scal_jmin[is] == TLAB_DNS_BCS_DIRICHLET && d->bcs.scal_jmax[is] == TLAB_DNS_BCS_DIRICHLET;
     finish_scal = finish_scal && !any_surface;      // the wall planes of a scalar with a surface model are not zero
+    // Scalars under a buffer zone: the reference relaxes hs AFTER its wall BCs and BEFORE the update (time.f90:628-630).
+    //  - Dirichlet scalars that the x Burgers epilogue finishes (zone_epi): the zone term joins hs in the mid-sequence zone launch, so the epilogue
+    //    finishes every interior plane with it (summed in another order: rounding only).  The epilogue writes zero wall tendencies and leaves s on
+    //    the wall planes as it was (clipped, which a field that came out of the last substep's clip already is): the wall planes inside a zone
+    //    are redone by the plane form of the zone kernel, h = 0 - tau (s - ref), s += dte h, bounds, h *= kco.  Zone bytes only.
+    //    (A pressure filter does not change this: the scalars never see the pressure.)
+    //  - every other route (Neumann walls, whose wall value is a functional of the tendency WITHOUT the zone term; the surface model; the literal
+    //    sequence): the literal order as passes of their own at the end -- wall planes, zone launch, k_rk_update.
+    // The flow stays on the fused route either way.
+    const bool walls_shared = (d->buff[1][0].size == ny && d->buff[1][1].size > 0) || (d->buff[1][1].size == ny && d->buff[1][0].size > 0);
+    const bool zone_epi = zone_scal && finish_scal && !scal_neumann_planes && !walls_shared;
+    if (zone_scal && !zone_epi) finish_scal = scal_neumann_planes = false;
+    const bool zone_tail = zone_scal && !zone_epi;
     // scalar bounds in the epilogue that finishes scalar is: on every line, or -- Neumann walls on the wall-plane route -- on the interior lines, k_wall_fix
     // clipping the wall planes once they are set
     auto clip_into = [&](int is, int &mode, double &lo, double &hi) {
@@ -413,6 +457,10 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
                                                  any_clip ? clip : nullptr, clo, chi))
                     throw Fail(TLAB_EINVAL, "internal: inconsistent fused Burgers path");
             }
+            // BOUNDARY_BUFFER_RELAX_FLOW (:170-172): after the second launch every component has been overwritten once and none is finished (the
+            // third launch finishes u and differentiates it): one zone launch for the three.  The terms are summed in another order, rounding only.
+            if (zone_flow && &L == &plan[1]) buffer_relax(d, 0, q, hq, st);
+            if (zone_epi && &L == &plan[1]) buffer_relax(d, 1, s, hs, st);       // (the scalars are finished by the third launch too)
         }
     } else if (batched) {
         const int order_xyz[3] = {1, 2, 3}, order_zyx[3] = {3, 2, 1};
@@ -437,6 +485,8 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
                                                  any_clip ? clip : nullptr, clo, chi))
                     throw Fail(TLAB_EINVAL, "internal: inconsistent fused Burgers path");
             }
+            if (zone_flow && k == 0) buffer_relax(d, 0, q, hq, st);      // after the first launch (it may overwrite), before the last (it may differentiate)
+            if (zone_epi && k == 0) buffer_relax(d, 1, s, hs, st);
         }
     }
     for (size_t e = 0; e < eqs.size() && !batched; ++e) {
@@ -452,6 +502,31 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             else {   // mixed: add the temporaries one at a time (k_add3 with zero-sized partners is not worth a kernel)
                 hk(hipMemsetAsync(tmp9, 0, (size_t)n * sizeof(double), st), "memset");
                 hk(launch_add3(eqs[e].dst, pend[0], npend > 1 ? pend[1] : tmp9, tmp9, n, st), "add3");
+            }
+        }
+    }
+    if (zone_flow && !batched) buffer_relax(d, 0, q, hq, st);      // BOUNDARY_BUFFER_RELAX_FLOW in the reference's place (:170-172)
+    // the tail of the scalars under a buffer zone, once the wall planes of hs hold their BC values: BOUNDARY_BUFFER_RELAX_SCAL, s += dte hs, bounds, hs *= kco
+    auto zone_scal_tail = [&] {
+        buffer_relax(d, 1, s, hs, st);
+        for (int is = 0; is < d->nscal; ++is) hk(launch_rk_update(s[is], hs[is], dte, kco, scale_tendencies, n, st, clip_of(d, is)), "rk update");
+    };
+    if (zone_epi) {      // the wall planes inside the zones, after the epilogue that finished the rest (nothing below reads s or hs)
+        for (int end = 0; end < 2; ++end) {
+            const tlab_dns::BufferBlock &b = d->buff[1][end];
+            if (b.size == 0) continue;
+            const long long zone = (long long)nx * b.size * nz;
+            for (int f0 = 0; f0 < b.nf; f0 += 4) {
+                const tlab::ClipBounds *cl[4] = {nullptr, nullptr, nullptr, nullptr};
+                for (int f = f0; f < std::min(b.nf, f0 + 4); ++f) cl[f - f0] = clip_of(d, f);
+                // the wall plane the block starts from, and the opposite one where the block spans the whole height (tau need not vanish there: sigma = 0).
+                // (zone_epi excludes a wall plane that BOTH blocks hold: the plane form restarts from the BC value, so it runs once per plane)
+                for (int wall = 0; wall < 2; ++wall) {
+                    const int j = wall == 0 ? 0 : ny - 1;
+                    if (j < b.offset || j >= b.offset + b.size) continue;
+                    hk(launch_buffer_relax_plane(std::min(4, b.nf - f0), hs + f0, s + f0, b.ref + f0 * zone, b.tau + (long long)f0 * b.size, nullptr, cl, dte, kco,
+                                                 scale_tendencies, nx, ny, nz, b.offset, b.size, j - b.offset, st), "buffer zone (wall plane)");
+                }
             }
         }
     }
@@ -561,7 +636,13 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
                           tlab_internal_neumann_final(gy, nx, ny, nz, ibc, hq[iq], q[iq], dte, kco, scale_tendencies);
             if (!done) throw Fail(TLAB_EINVAL, "internal: inconsistent fused Neumann tail");
         }
-        for (int is = 0; is < d->nscal && !finish_scal; ++is) {
+        for (int is = 0; is < d->nscal && zone_tail; ++is) {      // (tmp1 and the two planes are free: u, v, w are finished)
+            const int ibc = ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
+            if (ibc != 0) ok(tlab_boundary_bcs_neumann_y(gy, ibc, nx, ny, nz, hs[is], d->bcs_hb, d->bcs_ht, tmp1), "BOUNDARY_BCS_NEUMANN_Y");
+            hk(launch_set_wall_planes(hs[is], (ibc & 1) ? d->bcs_hb : nullptr, (ibc & 2) ? d->bcs_ht : nullptr, nx, ny, nz, st), "wall planes");
+        }
+        if (zone_tail) zone_scal_tail();
+        for (int is = 0; is < d->nscal && !finish_scal && !zone_tail; ++is) {
             const int ibc = ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
             if (ibc == 0) hk(launch_final_update(s[is], hs[is], nullptr, nullptr, nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)),
                              "final update");
@@ -677,8 +758,10 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         }
         for (int is = 0; is < d->nscal && !finish_scal; ++is) {      // (finish_scal: done in the epilogue of the x Burgers launch)
             scal_planes(is, pb, pt);
-            hk(launch_final_update(s[is], hs[is], nullptr, pb, pt, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)), "final update");
+            if (zone_tail) hk(launch_set_wall_planes(hs[is], pb, pt, nx, ny, nz, st), "wall planes");
+            else hk(launch_final_update(s[is], hs[is], nullptr, pb, pt, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)), "final update");
         }
+        if (zone_tail) zone_scal_tail();
     } else {
         if (!anel && !grad_sub) hk(launch_sub3(hq[0], hq[1], hq[2], tmp2, tmp3, tmp4, n, st), "sub3");
         for (int iq = 0; iq < 3; ++iq) {
@@ -1121,6 +1204,90 @@ int tlab_dns_set_fusion(tlab_dns_t d, int on) {
     if (!d) return TLAB_EINVAL;
     d->fuse = on != 0;
     return TLAB_OK;
+}
+
+// ---- [BufferZone] Type = relaxation (tools/dns/boundary_buffer.f90) ----
+// INI_BLOCK :359-371 on the host, in the reference's operation order: dummy = 1 / L, then strength * ((dy) * dummy) ** sigma
+int tlab_buffer_tau(int n, const double *nodes, int offset, int size, double strength, double sigma, int form, double *tau_out) {
+    if (!nodes || !tau_out || n < 1 || offset < 0 || size < 2 || offset + size > n || (form != 1 && form != 2)) {
+        tlab_set_error(size == 1 ? "tlab_buffer_tau: a zone of one plane has no length (the reference leaves tau unset there)"
+                                 : "tlab_buffer_tau: bad arguments (0 <= offset, 2 <= size, offset + size <= n, form 1 = Jmin or 2 = Jmax)");
+        return TLAB_EINVAL;
+    }
+    const double dummy = 1.0 / (nodes[offset + size - 1] - nodes[offset]);
+    for (int jloc = 0; jloc < size; ++jloc) {
+        const int j = offset + jloc;
+        const double dy = form == 2 ? nodes[j] - nodes[offset] : nodes[offset + size - 1] - nodes[j];
+        tau_out[jloc] = strength * std::pow(dy * dummy, sigma);
+    }
+    return TLAB_OK;
+}
+
+int tlab_dns_set_buffer_type(tlab_dns_t d, int type) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_type: null handle");
+        if (type == TLAB_BUFFER_FILTER || type == TLAB_BUFFER_BOTH)
+            throw Fail(TLAB_EUNSUPPORTED, "[BufferZone] Type = filter / both: the filter zones are not built on the device (relaxation only)");
+        if (type != TLAB_BUFFER_NONE && type != TLAB_BUFFER_RELAX) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_type: unknown type");
+        if (type == TLAB_BUFFER_NONE)
+            for (auto &g : d->buff)
+                for (tlab_dns::BufferBlock &b : g) tlab_dns::free_block(b, true);
+    });
+}
+
+int tlab_dns_set_buffer_zone(tlab_dns_t d, int end, int group, int size, int nfields, const double *tau, const double *ref) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: null handle");
+        if (end == TLAB_BUFFER_IMIN || end == TLAB_BUFFER_IMAX)
+            throw Fail(TLAB_EUNSUPPORTED, "buffer zones at Imin / Imax: x is periodic in this library (they belong to spatially evolving runs)");
+        if ((end != TLAB_BUFFER_JMIN && end != TLAB_BUFFER_JMAX) || (group != TLAB_BUFFER_FLOW && group != TLAB_BUFFER_SCAL))
+            throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: end = TLAB_BUFFER_JMIN / _JMAX, group = TLAB_BUFFER_FLOW / _SCAL");
+        tlab_dns::BufferBlock &b = d->buff[group == TLAB_BUFFER_FLOW ? 0 : 1][end == TLAB_BUFFER_JMIN ? 0 : 1];
+        tlab_dns::BufferBlock nb;
+        if (size != 0 && tau) {
+            const int want = group == TLAB_BUFFER_FLOW ? 3 : d->nscal;
+            if (nfields != want || nfields < 1) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: nfields must be 3 (flow) or nscal (scalars)");
+            if (size == 1) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: a zone of one plane (the reference leaves its tau unset)");
+            if (size < 0 || size > d->ny) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: size must lie in 2 .. ny");
+            if (!ref) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: ref is NULL");
+            for (long long i = 0; i < (long long)size * nfields; ++i)
+                if (std::isnan(tau[i])) throw Fail(TLAB_EINVAL, "tlab_dns_set_buffer_zone: NaN in tau");
+            nb.size = size; nb.nf = nfields; nb.offset = end == TLAB_BUFFER_JMIN ? 0 : d->ny - size;
+            const size_t tb = (size_t)size * nfields * sizeof(double), rb = (size_t)d->nx * size * d->nz * nfields * sizeof(double);
+            try {
+                hk(hipMalloc((void **)&nb.tau, tb), "hipMalloc");
+                hk(hipMalloc((void **)&nb.ref, rb), "hipMalloc");
+                hk(hipMemcpy(nb.tau, tau, tb, hipMemcpyHostToDevice), "hipMemcpy");
+                hk(hipMemcpy(nb.ref, ref, rb, hipMemcpyHostToDevice), "hipMemcpy");
+            } catch (...) {
+                if (nb.tau) (void)hipFree(nb.tau);
+                if (nb.ref) (void)hipFree(nb.ref);
+                throw;
+            }
+        }
+        tlab_dns::free_block(b, true);
+        b = nb;
+    }, TLAB_EINVAL);
+}
+
+int tlab_dns_buffer_relax_flow(tlab_dns_t d, double *const *q, double *const *hq) {
+    return guarded([&] {
+        if (!d || !q || !hq) throw Fail(TLAB_EINVAL, "tlab_dns_buffer_relax_flow: bad arguments");
+        for (int i = 0; i < 3; ++i)
+            if (!q[i] || !hq[i]) throw Fail(TLAB_EINVAL, "tlab_dns_buffer_relax_flow: null array");
+        buffer_relax(d, 0, q, hq, tlab_current_stream());
+    });
+}
+
+int tlab_dns_buffer_relax_scal(tlab_dns_t d, double *const *s, double *const *hs) {
+    return guarded([&] {
+        if (!d || (d->nscal > 0 && (!s || !hs))) throw Fail(TLAB_EINVAL, "tlab_dns_buffer_relax_scal: bad arguments");
+        for (int i = 0; i < d->nscal; ++i)
+            if (!s[i] || !hs[i]) throw Fail(TLAB_EINVAL, "tlab_dns_buffer_relax_scal: null array");
+        buffer_relax(d, 1, s, hs, tlab_current_stream());
+    });
 }
 
 // ---- the pointwise pieces on their own, for drivers that interleave communication (z-slab decomposition) ----

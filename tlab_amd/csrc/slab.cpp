@@ -479,9 +479,17 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     };
     // scalars are finished by the z pass itself: Dirichlet walls, or Neumann ones on the wall-plane route (TLAB_SLAB_FUSED_X=0: separate update, the
     // Python driver's sequence)
+    // Relaxation buffer zones (tlab_slab_dns_set_buffer_zone): y is never split, so both parts are local.  The blocks of a rank live in its
+    // single-domain handle; the flow blocks act once every Burgers sum of hq is complete and before hq is read for the forcing (and before the halo
+    // planes of hq3 travel); scalars under a zone are not finished by the z pass: wall planes of hs, zone launch, update, the reference's order.
+    bool zone_flow = false, zone_scal = false;
+    for (Rank &R : d->rk) {
+        zone_flow = zone_flow || (R.dns && tlab_internal_dns_has_flow_zones(R.dns));
+        zone_scal = zone_scal || (tail && R.dns && tlab_internal_dns_has_scal_zones(R.dns));
+    }
     std::vector<int> zfin((size_t)(3 + ns), 0);
     for (int i = 0; i < ns; ++i)
-        zfin[3 + i] = tail && d->fused_x && !surface(i) && (ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]) == 0 || planes_route);
+        zfin[3 + i] = !zone_scal && tail && d->fused_x && !surface(i) && (ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]) == 0 || planes_route);
     // ---- diffusion + advection (:98-162) and the pressure forcing div(hq + q/dte) (:188-260) ----
     // (Measured in round 4 and dropped: the x and y terms of the forcing inside the Burgers launches that add the last term of u resp. v, as rhs.cpp
     // does on one device.  It needs u to end with its x term and v with its y term, i.e. the x and y launches split in two; on slabs of 64 planes the
@@ -494,6 +502,9 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     for (Rank &R : d->rk) badd_all(d, R, 2, false);
     twait(d, w);
     for (Rank &R : d->rk) zburgers_all(d, R, 2, &zfin, tdte, kco, scale);
+    if (zone_flow)      // BOUNDARY_BUFFER_RELAX_FLOW (rhs_global_incompressible_1.f90:170-172)
+        for (Rank &R : d->rk)
+            if (R.dns) ok(tlab_dns_buffer_relax_flow(R.dns, R.q.data(), R.hq.data()), "tlab_dns_buffer_relax_flow");
     w = halo_start(d, 1, [&](Rank &R, int) { return Slot{R.hq[2], S_HQ3}; });          // w's halo planes are still valid
     for (Rank &R : d->rk) padd(d, R, 2, R.hq[1], R.q[1], idte, R.txc[0], 0);
     for (Rank &R : d->rk) padd(d, R, 1, R.hq[0], R.q[0], idte, R.txc[0], 1);
@@ -574,8 +585,12 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
                 surface_flux_local(R, f.is);
                 pb = R.sref_b[f.is]; pt = R.sref_t[f.is];
             }
-            if (!tail) ok(tlab_pw_set_wall_planes(f.h, pb, pt, nx, ny, kmax), "tlab_pw_set_wall_planes");
+            if (!tail || (zone_scal && f.is >= 0)) ok(tlab_pw_set_wall_planes(f.h, pb, pt, nx, ny, kmax), "tlab_pw_set_wall_planes");
             else ok(tlab_pw_final_update(f.q, f.h, f.g, pb, pt, tdte, kco, scale, nx, ny, kmax), "tlab_pw_final_update");
+        }
+        if (zone_scal) {      // BOUNDARY_BUFFER_RELAX_SCAL after the BCs (time.f90:628-630), then the update
+            if (R.dns) ok(tlab_dns_buffer_relax_scal(R.dns, R.s.data(), R.hs.data()), "tlab_dns_buffer_relax_scal");
+            for (int i = 0; i < ns; ++i) ok(tlab_pw_rk_update(R.s[i], R.hs[i], tdte, kco, scale, n), "tlab_pw_rk_update");
         }
     };
     w = halo_start(d, 1, [&](Rank &R, int) { return Slot{R.txc[0], S_P}; });
@@ -888,6 +903,14 @@ int tlab_slab_dns_dilatation_bounds(tlab_slab_dns_t d, double *dil_min, double *
         *dil_min = mn[0];
         *dil_max = mx[0];
     });
+}
+
+int tlab_slab_dns_set_buffer_zone(tlab_slab_dns_t d, int l, int end, int group, int size, int nfields, const double *tau, const double *ref) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d || l < 0 || l >= (int)d->rk.size()) throw Fail(TLAB_EINVAL, "tlab_slab_dns_set_buffer_zone: bad handle or local rank");
+        ok(tlab_dns_set_buffer_zone(dns_handle(d, d->rk[l]), end, group, size, nfields, tau, ref), "tlab_dns_set_buffer_zone");
+    }, TLAB_EINVAL);
 }
 
 int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi) {

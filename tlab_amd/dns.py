@@ -57,6 +57,51 @@ def _bounds_arrays(lo, hi, active):
     return n, (ctypes.c_int * m)(*act), (ctypes.c_double * m)(*lo), (ctypes.c_double * m)(*hi)
 
 
+def zone_tables(y, nx, ny, nz, nscal, points_jmin, points_jmax, params_u, params_s, hard_u, hard_s, ref, global_field):
+    """The blocks of Dns.set_buffer_zones for a decomposed driver, over the GLOBAL box: yields (end, group, size, nfields, tau, g) with tau (nfields,
+    size) = (size, nfields) column-major and g the reference fields (nfields, nz, size, nx), or g = None for a block that is off.  The plane means of
+    LoadBuffer = no span the whole plane (COV2V2D all-reduces over the ranks): global_field(name, i) returns field i of "q" / "s" as a host array
+    (nz, ny, nx), or None where not every rank is local -- then hard_* or ref must be given."""
+    L = load()
+    dp = ctypes.POINTER(ctypes.c_double)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    for end, key, size, form in ((3, "jmin", int(points_jmin), 1), (4, "jmax", int(points_jmax), 2)):
+        offset = 0 if end == 3 else ny - size
+        for group, gkey, name, params, hard in ((0, "flow", "q", params_u, hard_u), (1, "scal", "s", params_s, hard_s)):
+            nf = 3 if group == 0 else nscal
+            if size == 0 or nf == 0:
+                yield end, group, 0, nf, None, None
+                continue
+            p = [float(v) for v in np.atleast_1d(params)]
+            if len(p) == 1:
+                strength, sigma = [p[0]] * nf, 2.0
+            elif len(p) == 2:
+                strength, sigma = [p[0]] * nf, p[1]
+            elif len(p) == nf + 1:
+                strength, sigma = p[:nf], p[nf]
+            else:
+                raise TlabError("BufferZone.Parameters: 1, 2 or nfields + 1 values")
+            tau = np.zeros((nf, max(size, 1)))
+            for iq in range(nf):
+                check(L.tlab_buffer_tau(ny, y.ctypes.data_as(dp), offset, size, strength[iq], sigma, form, tau[iq].ctypes.data_as(dp)), "tlab_buffer_tau")
+            if ref is not None and (gkey, key) in ref:
+                g = np.ascontiguousarray(ref[(gkey, key)], dtype=np.float64)
+                if g.shape != (nf, nz, size, nx):
+                    raise TlabError("buffer zone ref: global shape (nfields, nz, size, nx)")
+            else:
+                g = np.empty((nf, nz, size, nx))
+                for iq in range(nf):
+                    if hard is not None:
+                        g[iq] = float(hard[iq])
+                        continue
+                    a3 = global_field(name, iq)
+                    if a3 is None:
+                        raise TlabError("set_buffer_zones: the plane means span all ranks; give hard_u / hard_s or ref when ranks live in other processes")
+                    for jloc in range(size):      # COV2V2D (utils/averages.f90:244-267): serial sum, i fastest then k, / (nx nz)
+                        g[iq, :, jloc, :] = float(np.cumsum(np.ascontiguousarray(a3[:, offset + jloc, :]).ravel())[-1]) / float(nx * nz)
+            yield end, group, size, nf, tau, g
+
+
 def _extremes(mn, mx, lmin, lmax, locations):
     """(DilMin, DilMax[, (i, j, k) of the minimum, (i, j, k) of the maximum]) of the dilatation_extremes methods"""
     if not locations:
@@ -93,6 +138,7 @@ class Dns:
         import torch
         self.nx, self.ny, self.nz = len(x), len(y), len(z)
         self.n = self.nx * self.ny * self.nz
+        self.y = np.ascontiguousarray(y, dtype=np.float64)          # g(2)%nodes: the buffer zones' strength (set_buffer_zones)
         self.nscal = int(nscal)
         self.visc = float(visc)
         self.schmidt = np.ascontiguousarray(schmidt, dtype=np.float64)[: self.nscal]
@@ -162,6 +208,72 @@ class Dns:
         scalar becomes min(max(s, lo), hi).  lo, hi, active: one entry per scalar (active defaults to all); None switches limiting off."""
         n, act, l, h = _bounds_arrays(lo, hi, active)
         check(load().tlab_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_dns_set_scalar_bounds")
+
+    def set_buffer_zones(self, points_jmin=0, points_jmax=0, params_u=(1.0, 2.0), params_s=(1.0, 2.0), hard_u=None, hard_s=None, ref=None,
+                         type="relaxation", points_imin=0, points_imax=0):
+        """[BufferZone] Type = relaxation with PointsUJmin = PointsSJmin = points_jmin, PointsUJmax = PointsSJmax = points_jmax (the reference demands
+        the pairs equal, dns_read_local.f90:380-386), ParametersU / ParametersS = 1, 2 or nfields + 1 values (strength(s), sigma; boundary_buffer.f90:91-139).
+        The reference fields are built like INI_BLOCK with LoadBuffer = no (:291-333) from the fields the object holds NOW: per plane the mean in the
+        reference's serial order, or the constants hard_u (3) / hard_s (nscal) of HardValues; or ref = {("flow" | "scal", "jmin" | "jmax"): array of
+        shape (nfields, nz, size, nx)} as a loaded buffer would give them.  points 0 switches that end off.  type "filter" / "both" and zones at
+        Imin / Imax are refused by the library (TLAB_EUNSUPPORTED)."""
+        L = load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        code = {"none": 0, "relaxation": 1, "filter": 2, "both": 3}.get(str(type).strip().lower())
+        if code is None:
+            raise TlabError("BufferZone.Type: none, relaxation, filter or both")
+        check(L.tlab_dns_set_buffer_type(self._h, code), "tlab_dns_set_buffer_type")
+        for end, pts in ((1, points_imin), (2, points_imax)):
+            if int(pts) > 0:
+                check(L.tlab_dns_set_buffer_zone(self._h, end, 0, int(pts), 3, None, None), "tlab_dns_set_buffer_zone")
+        if code == 0:
+            return
+        y = self.y
+        for end, key, size, form in ((3, "jmin", int(points_jmin), 1), (4, "jmax", int(points_jmax), 2)):
+            offset = 0 if end == 3 else self.ny - size
+            for group, gkey, fields, params, hard in ((0, "flow", self.q, params_u, hard_u), (1, "scal", self.s, params_s, hard_s)):
+                nf = len(fields)
+                if size == 0 or nf == 0:
+                    check(L.tlab_dns_set_buffer_zone(self._h, end, group, 0, nf, None, None), "tlab_dns_set_buffer_zone")
+                    continue
+                p = [float(v) for v in np.atleast_1d(params)]
+                if len(p) == 1:
+                    strength, sigma = [p[0]] * nf, 2.0
+                elif len(p) == 2:
+                    strength, sigma = [p[0]] * nf, p[1]
+                elif len(p) == nf + 1:
+                    strength, sigma = p[:nf], p[nf]
+                else:
+                    raise TlabError("BufferZone.Parameters: 1, 2 or nfields + 1 values")
+                tau = np.zeros((nf, max(size, 1)))                      # (size, nfields) column-major
+                for iq in range(nf):
+                    check(L.tlab_buffer_tau(self.ny, y.ctypes.data_as(dp), offset, size, strength[iq], sigma, form, tau[iq].ctypes.data_as(dp)), "tlab_buffer_tau")
+                if ref is not None and (gkey, key) in ref:
+                    r = np.ascontiguousarray(ref[(gkey, key)], dtype=np.float64)
+                    if r.shape != (nf, self.nz, size, self.nx):
+                        raise TlabError("buffer zone ref: shape (nfields, nz, size, nx)")
+                else:
+                    r = np.empty((nf, self.nz, size, self.nx))
+                    for iq, t in enumerate(fields):
+                        if hard is not None:
+                            r[iq] = float(hard[iq])
+                            continue
+                        a3 = t.view(self.nz, self.ny, self.nx)[:, offset:offset + size, :].cpu().numpy()
+                        for jloc in range(size):      # COV2V2D (utils/averages.f90:244-267): serial sum, i fastest then k, / (nx nz)
+                            r[iq, :, jloc, :] = float(np.cumsum(np.ascontiguousarray(a3[:, jloc, :]).ravel())[-1]) / float(self.nx * self.nz)
+                check(L.tlab_dns_set_buffer_zone(self._h, end, group, size, nf, tau.ctypes.data_as(dp), r.ctypes.data_as(dp)), "tlab_dns_set_buffer_zone")
+
+    def buffer_relax_flow(self):
+        """BOUNDARY_BUFFER_RELAX_FLOW on (q, hq) as an operator of its own."""
+        _use_torch_stream()
+        q, _, hq, _, _ = self._arrays()
+        check(load().tlab_dns_buffer_relax_flow(self._h, q, hq), "tlab_dns_buffer_relax_flow")
+
+    def buffer_relax_scal(self):
+        """BOUNDARY_BUFFER_RELAX_SCAL on (s, hs) as an operator of its own."""
+        _use_torch_stream()
+        _, s, _, hs, _ = self._arrays()
+        check(load().tlab_dns_buffer_relax_scal(self._h, s, hs), "tlab_dns_buffer_relax_scal")
 
     def set_fusion(self, on):
         """on (default): pointwise sums folded into the operator kernels; off: the reference's literal sequence."""

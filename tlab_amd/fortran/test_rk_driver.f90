@@ -139,7 +139,7 @@ contains
         return
     end subroutine TIME_RUNGEKUTTA
 
-    ! TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT   tools/dns/time.f90:559-664 (EQNS_CONVECTIVE, EQNS_RHS_COMBINED; no sources, no buffer zone)
+    ! TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT   tools/dns/time.f90:559-664 (EQNS_CONVECTIVE, EQNS_RHS_COMBINED; no sources; this mini-driver sets no buffer zones -- a host with them: tlab_amd_buffer.f90)
     subroutine TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT()
         use TLab_Arrays, only: q, s, txc
         use DNS_ARRAYS, only: hq, hs

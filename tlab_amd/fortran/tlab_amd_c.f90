@@ -288,6 +288,44 @@ module TLab_AMD_C
             type(c_ptr), value :: pencil, active, lo, hi
             integer(c_int), value :: n
         end function
+        ! [BufferZone] Type = relaxation at Jmin / Jmax of a patched host (single-domain driver): iend = 3 Jmin / 4 Jmax, group = 0 flow / 1 scalars,
+        ! tau(size, nfields) and ref(imax, size, kmax, nfields) = item%tau, item%ref of boundary_buffer.f90 as they stand (HOST); size = 0: off
+        integer(c_int) function tlab_dns_set_buffer_type(dns, itype) bind(C, name='tlab_dns_set_buffer_type')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+            integer(c_int), value :: itype
+        end function
+        integer(c_int) function tlab_dns_set_buffer_zone(dns, iend, group, size, nfields, tau, ref) bind(C, name='tlab_dns_set_buffer_zone')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, tau, ref
+            integer(c_int), value :: iend, group, size, nfields
+        end function
+        integer(c_int) function tlab_buffer_tau(n, nodes, offset, size, strength, sigma, form, tau_out) bind(C, name='tlab_buffer_tau')
+            import :: c_int, c_double
+            integer(c_int), value :: n, offset, size, form
+            real(c_double), value :: strength, sigma
+            real(c_double), intent(in) :: nodes(*)
+            real(c_double), intent(out) :: tau_out(*)
+        end function
+        ! BOUNDARY_BUFFER_RELAX_SCAL of an unchanged time loop: recorded after the deferred RHS, part of the one fused substep (csrc/deferred.cpp)
+        integer(c_int) function tlab_deferred_relax_scal(dns) bind(C, name='tlab_deferred_relax_scal')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+        end function
+        integer(c_int) function tlab_deferred_relax_stats(counts) bind(C, name='tlab_deferred_relax_stats')
+            import :: c_int, c_long_long
+            integer(c_long_long), intent(out) :: counts(2)
+        end function
+        integer(c_int) function tlab_dns_buffer_relax_flow(dns, q, hq) bind(C, name='tlab_dns_buffer_relax_flow')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+            type(c_ptr), intent(in) :: q(*), hq(*)        ! host arrays of device pointers
+        end function
+        integer(c_int) function tlab_dns_buffer_relax_scal(dns, s, hs) bind(C, name='tlab_dns_buffer_relax_scal')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+            type(c_ptr), intent(in) :: s(*), hs(*)
+        end function
         integer(c_int) function tlab_rhs_global_incompressible_1(dns, dte, q, s, hq, hs, txc) bind(C, name='tlab_rhs_global_incompressible_1')
             import :: c_int, c_ptr, c_double
             type(c_ptr), value :: dns

@@ -77,6 +77,15 @@ SIGNATURES = {
     "tlab_deferred_clip": (c_int, [ctypes.c_longlong, c_dbl, c_dbl, c_vp]),
     "tlab_deferred_clip_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "tlab_pointer_on_device": (c_int, [c_vp]),
+    "tlab_dns_set_buffer_type": (c_int, [c_vp, c_int]),
+    "tlab_dns_set_buffer_zone": (c_int, [c_vp, c_int, c_int, c_int, c_int, _dp, _dp]),
+    "tlab_buffer_tau": (c_int, [c_int, _dp, c_int, c_int, c_dbl, c_dbl, c_int, _dp]),
+    "tlab_dns_buffer_relax_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    "tlab_dns_buffer_relax_scal": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    "tlab_deferred_relax_scal": (c_int, [c_vp]),
+    "tlab_deferred_relax_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
+    "tlab_slab_dns_set_buffer_zone": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, _dp, _dp]),
+    "tlab_pencil_dns_set_buffer_zone": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, _dp, _dp]),
     "tlab_dns_begin_step": (c_int, [c_vp]),
     "tlab_deferred_enable": (c_int, [c_int]),
     "tlab_deferred_rhs": (c_int, [c_vp, c_dbl, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),

@@ -412,6 +412,7 @@ class NativePencilDns:
             raise TlabError("transport: loopback or rccl")
         self.transport = transport
         self.nx, self.ny, self.nzt = len(x), len(y), len(z)
+        self._y = np.array(y, dtype=np.float64)          # g(2)%nodes: the buffer zones' strength (set_buffer_zones)
         self.nscal, self.visc = int(nscal), float(visc)
         self.schmidt = [float(v) for v in schmidt][: self.nscal]
         self.g = [FdmPlan(x, True, True, hyper_bc1_ext=hyper_bc1_ext), FdmPlan(y, False, yuniform, hyper_bc1_ext=hyper_bc1_ext),
@@ -459,6 +460,34 @@ class NativePencilDns:
         """Scalar bounds limiting after the update of every substep, as Dns.set_scalar_bounds (None: off)."""
         n, act, l, h = _bounds_arrays(lo, hi, active)
         check(load().tlab_pencil_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_pencil_dns_set_scalar_bounds")
+
+    def set_buffer_zones(self, points_jmin=0, points_jmax=0, params_u=(1.0, 2.0), params_s=(1.0, 2.0), hard_u=None, hard_s=None, ref=None):
+        """[BufferZone] Type = relaxation at Jmin / Jmax, as Dns.set_buffer_zones; each local rank takes its box of the global reference fields
+        (see NativeSlabDns.set_buffer_zones for the plane means when ranks live in other processes)."""
+        import torch
+        from .dns import zone_tables
+        L = load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        all_local = len(self.local_ranks) == self.npi * self.npk
+
+        def global_field(name, i):
+            if not all_local:
+                return None
+            out = torch.empty(self.nzt, self.ny, self.nx, dtype=torch.float64, device="cuda")
+            for r, t in self.gather_local(name, i).items():
+                pi, pk = self.pro(r)
+                out[pk * self.kmax:(pk + 1) * self.kmax, :, pi * self.imax:(pi + 1) * self.imax] = t.view(self.kmax, self.ny, self.imax)
+            return out.cpu().numpy()
+        for end, group, size, nf, tau, g in zone_tables(self._y, self.nx, self.ny, self.nzt, self.nscal, points_jmin, points_jmax, params_u, params_s,
+                                                        hard_u, hard_s, ref, global_field):
+            for l, r in enumerate(self.local_ranks):
+                if size == 0:
+                    check(L.tlab_pencil_dns_set_buffer_zone(self._h, l, end, group, 0, nf, None, None), "tlab_pencil_dns_set_buffer_zone")
+                    continue
+                pi, pk = self.pro(r)
+                box = np.ascontiguousarray(g[:, pk * self.kmax:(pk + 1) * self.kmax, :, pi * self.imax:(pi + 1) * self.imax])
+                check(L.tlab_pencil_dns_set_buffer_zone(self._h, l, end, group, size, nf, tau.ctypes.data_as(dp), box.ctypes.data_as(dp)),
+                      "tlab_pencil_dns_set_buffer_zone")
 
     def RHS_GLOBAL_INCOMPRESSIBLE_1(self, dte):
         _use_torch_stream()

@@ -148,6 +148,7 @@ class NativeSlabDns:
         self.size = P
         self.local_ranks = list(range(self._tr.first, self._tr.first + self._tr.nlocal))
         self.nx, self.ny, self.nzt = len(x), len(y), len(z)
+        self._y = np.array(y, dtype=np.float64)          # g(2)%nodes: the buffer zones' strength (set_buffer_zones)
         self.nscal, self.visc = int(nscal), float(visc)
         self.schmidt = [float(v) for v in schmidt][: self.nscal]
         self.g = list(plans) if plans is not None else [
@@ -226,6 +227,31 @@ class NativeSlabDns:
         """Scalar bounds limiting after the update of every substep, as Dns.set_scalar_bounds (None: off)."""
         n, act, l, h = _bounds_arrays(lo, hi, active)
         check(load().tlab_slab_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_slab_dns_set_scalar_bounds")
+
+    def set_buffer_zones(self, points_jmin=0, points_jmax=0, params_u=(1.0, 2.0), params_s=(1.0, 2.0), hard_u=None, hard_s=None, ref=None):
+        """[BufferZone] Type = relaxation at Jmin / Jmax, as Dns.set_buffer_zones.  The plane means of LoadBuffer = no are means over the WHOLE plane
+        (COV2V2D all-reduces over the ranks): they are formed here when every rank is local (loopback), in the reference's serial order over the
+        global plane; a run spread over processes gives hard_u / hard_s, or ref = {("flow" | "scal", "jmin" | "jmax"): global array of shape
+        (nfields, nz, size, nx)}, of which each local rank takes its planes."""
+        import torch
+        from .dns import zone_tables
+        L = load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        all_local = len(self.local_ranks) == self.size
+
+        def global_field(name, i):
+            if not all_local:
+                return None
+            return torch.cat([self.st[r][name][i] for r in self.local_ranks]).view(self.nzt, self.ny, self.nx).cpu().numpy()
+        for end, group, size, nf, tau, g in zone_tables(self._y, self.nx, self.ny, self.nzt, self.nscal, points_jmin, points_jmax, params_u, params_s,
+                                                        hard_u, hard_s, ref, global_field):
+            for l, r in enumerate(self.local_ranks):
+                if size == 0:
+                    check(L.tlab_slab_dns_set_buffer_zone(self._h, l, end, group, 0, nf, None, None), "tlab_slab_dns_set_buffer_zone")
+                    continue
+                box = np.ascontiguousarray(g[:, r * self.kmax:(r + 1) * self.kmax])
+                check(L.tlab_slab_dns_set_buffer_zone(self._h, l, end, group, size, nf, tau.ctypes.data_as(dp), box.ctypes.data_as(dp)),
+                      "tlab_slab_dns_set_buffer_zone")
 
     def set_remove_divergence(self, on):
         """dns.ini [Main] TermDivergence (as Dns.set_remove_divergence): off = the forcing of the pressure equation is div(hq) alone."""
