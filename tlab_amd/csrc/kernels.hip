@@ -7,6 +7,7 @@
 //             lane l holds the M = n/64 consecutive points [l*M, (l+1)*M) in registers (coalesced 16-B loads),
 //             stencil halos come from the neighbouring lanes, the 64-unknown separator system is solved by
 //             parallel cyclic reduction with wave shuffles.  No LDS traffic for periodic (circulant) systems.
+//             512-point periodic lines cross global memory lane-linearly and change layout in a wave-private LDS row (STG below).
 //  k_rtile  : derivative along a strided index (Y, Z).  One WORKGROUP per tile of 64 lines x n points:
 //             lanes <-> 64 memory-contiguous lines (512-B coalesced rows), wave w holds rows [w*M, (w+1)*M) in
 //             registers, coefficient rows are wave-uniform scalar loads, the P x P separator system goes through LDS.
@@ -286,28 +287,82 @@ __device__ __forceinline__ void xsten(double (&f)[M], const double (&u)[M], cons
     else xstencil_periodic<M, SYM>(f, u, um, up, s);
 }
 
-template <int M>
+// STG (one wave per line, M = 8): the line arrays cross global memory lane-linearly -- register pair q of lane l is the 16 bytes at 16 l + 1024 q of the
+// 4-KiB line, so that every load / store instruction covers 1 KiB of consecutive bytes instead of a quarter of each of the line's 32 128-byte lines --
+// and change between that layout and the chunk layout of the solves (lane l owns bytes [64 l, 64 l + 64)) through a wave-private row in LDS.
+// Row pitch 80 bytes per 64-byte chunk (16 bytes of padding: the 16-lane groups of a chunk-side ds_read_b128 land on 16 distinct four-bank slots), 5120 bytes
+// per wave; q is the offset immediate of the ds_ instructions on both sides (1280 q lane-linear, 16 q chunk-wise): two address registers per lane.
+// The row belongs to one wave, whose LDS operations complete in order: no barrier, only the compiler is kept from reordering the two sides.
+constexpr int XSTG_ROW = 64 * 80;           // bytes per wave
+typedef double xd2_t __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) xd2_t ldsd2_t;
+struct XStage {
+    ldsd2_t *lin, *chk;          // this lane's 16 bytes of the row in the lane-linear / the chunk layout (q = 0)
+};
+__device__ __forceinline__ void xstage_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// lane-linear registers (as loaded) -> chunk layout, in place
+template <bool STG, int M>
+__device__ __forceinline__ void xin(double (&u)[M], const XStage &sg) {
+    if constexpr (STG) {
+        xstage_order();
+#pragma unroll
+        for (int q = 0; q < M / 2; ++q) sg.lin[80 * q] = xd2_t{u[2 * q], u[2 * q + 1]};
+        xstage_order();
+#pragma unroll
+        for (int q = 0; q < M / 2; ++q) {
+            const xd2_t v = sg.chk[q];
+            u[2 * q] = v.x;
+            u[2 * q + 1] = v.y;
+        }
+    }
+}
+// chunk layout -> lane-linear registers (as stored), in place
+template <bool STG, int M>
+__device__ __forceinline__ void xout(double (&u)[M], const XStage &sg) {
+    if constexpr (STG) {
+        xstage_order();
+#pragma unroll
+        for (int q = 0; q < M / 2; ++q) sg.chk[q] = xd2_t{u[2 * q], u[2 * q + 1]};
+        xstage_order();
+#pragma unroll
+        for (int q = 0; q < M / 2; ++q) {
+            const xd2_t v = sg.lin[80 * q];
+            u[2 * q] = v.x;
+            u[2 * q + 1] = v.y;
+        }
+    }
+}
+// STG: 64 double2 between the register pairs of a lane (xload / xstore), and register p of the lane-linear layout is element xlin(p) from the lane's first
+template <int M, bool STG = false>
 __device__ __forceinline__ void xload(double (&u)[M], const double *__restrict__ p) {
 #pragma unroll
     for (int q = 0; q < M / 2; ++q) {
-        const double2 v = reinterpret_cast<const double2 *>(p)[q];
+        const double2 v = reinterpret_cast<const double2 *>(p)[STG ? 64 * q : q];
         u[2 * q] = v.x;
         u[2 * q + 1] = v.y;
     }
 }
-template <int M>
+template <int M, bool STG = false>
 __device__ __forceinline__ void xstore(double *__restrict__ p, const double (&u)[M]) {
 #pragma unroll
-    for (int q = 0; q < M / 2; ++q) reinterpret_cast<double2 *>(p)[q] = make_double2(u[2 * q], u[2 * q + 1]);
+    for (int q = 0; q < M / 2; ++q) reinterpret_cast<double2 *>(p)[STG ? 64 * q : q] = make_double2(u[2 * q], u[2 * q + 1]);
 }
+template <bool STG>
+__device__ __forceinline__ constexpr int xlin(int p) { return STG ? (p >> 1) * 128 + (p & 1) : p; }
 
 // LV / LV2: table form of the first- / second-derivative system (see xcoef)
 // OCC = 2: two workgroups per CU (two waves per SIMD) asked of the compiler, and the lane-variant tables re-read from LDS where they are used instead of
 // being kept in ~140 registers across the loop over lines and fields (512-point lines: 256 VGPRs + 102 AGPRs = one wave per SIMD otherwise)
 // CLIP: the finishing epilogue also applies the scalar bounds (XLineArgs::fclip); a separate instantiation, so that the kernels of runs without bounds
 // are those of before
-template <int M, int MODE, int LV, int WPL, int LV2 = LV, int TPB = 256, bool CL = false, bool PER = false, int OCC = 1, bool CLIP = false>
+// STG: coalesced line accesses through a wave-private LDS row (above); the row of wave w follows everything else in LDS
+template <int M, int MODE, int LV, int WPL, int LV2 = LV, int TPB = 256, bool CL = false, bool PER = false, int OCC = 1, bool CLIP = false, bool STG = false>
 __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline(XLineArgs a) {
+    static_assert(!STG || (M == 8 && WPL == 1 && PER), "the staged form exists for one wave per periodic 512-point line");
     // (CL with one wave per line: stage_red leaves the rows of the two-level reduction empty)
     extern __shared__ double xlds[];
     constexpr bool NEED1 = (MODE != MODE_P2);
@@ -371,6 +426,14 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
         }
     }
     if (LV != 0 || LV2 != 0 || WPL > 1) __syncthreads();
+    XStage sg;
+    if constexpr (STG) {
+        constexpr size_t SOFF = (NEED1 ? TABW1 + REDW : 0) + (NEED2 ? TABW2 + REDW : 0);      // doubles before the rows
+        static_assert(SOFF % 2 == 0, "the rows are 16-byte aligned");
+        ldsd2_t *row = (ldsd2_t *)(xlds + SOFF) + wib * (XSTG_ROW / 16);
+        sg.lin = row + 5 * (lane >> 2) + (lane & 3);
+        sg.chk = row + 5 * lane;
+    }
     XSys<WPL, CL> y1, y2;
     if (NEED1) xsys_init<M, LV, WPL, CL>(y1, a.y1, lds1, red1, gl, n);
     if (NEED2) xsys_init<M, LV2, WPL, CL>(y2, a.y2, lds2, red2, gl, n);
@@ -387,11 +450,11 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
             if constexpr (WPL == 1) continue;       // independent waves
             line = a.nlines - 1;                    // the waves of a workgroup meet at barriers: compute, do not store
         }
-        const long long off = line * n + gl * M;
+        const long long off = line * n + (STG ? 2 * lane : gl * M);        // STG: lane-linear, 16 bytes per lane and 1 KiB per instruction
         const bool next = line0 + stride < a.nlines;            // workgroup-uniform
         long long nline = line0 + stride + lib;
         if (nline >= a.nlines) nline = a.nlines - 1;
-        const long long noff = nline * n + gl * M;
+        const long long noff = nline * n + (STG ? 2 * lane : gl * M);
         // many rows per lane: the lane-variant tables are loop-invariant and the compiler would keep all 2 x 5 x M of them in registers
         // (182 spilled VGPRs at M = 32); an opaque copy of the LDS pointers per line makes it re-read them where they are used
         if constexpr (LV == 2 || (LV == 1 && (M >= 16 || OCC > 1))) { if (NEED1) asm volatile("" : "+v"(y1.lds)); }
@@ -404,8 +467,9 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
 #pragma unroll
                 for (int p = 0; p < M; ++p) v[p] = pn[p];
             } else {
-                xload<M>(v, a.in1 + off);
+                xload<M, STG>(v, a.in1 + off);
             }
+            xin<STG, M>(v, sg);
             have_pn = false;
             // software pipeline over the fields: with one wave per SIMD nothing else hides the memory latency, so the operand of the NEXT
             // field and the old tendency of THIS one are requested before the two solves of this field start (2.9-3.0 -> 2.65-2.75 ms at 512^3;
@@ -425,15 +489,17 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
                 } else if (have_next) {
 #pragma unroll
                     for (int p = 0; p < M; ++p) u[p] = un[p];
+                    xin<STG, M>(u, sg);
                 } else {
-                    xload<M>(u, src + off);
+                    xload<M, STG>(u, src + off);
+                    xin<STG, M>(u, sg);
                 }
                 constexpr bool PIPE = (M <= 16) && !(CL && LV == 2 && LV2 == 2);     // 32 rows per lane: the extra line-sets would spill
                 double o[M];
-                if (PIPE && a.acc) xload<M>(o, dst + off);
+                if (PIPE && a.acc) xload<M, STG>(o, dst + off);
                 have_next = PIPE && (f + 1 < a.nf) && (a.fs[f + 1] != a.in1);
-                if (have_next) xload<M>(un, a.fs[f + 1] + off);
-                if (PIPE && M <= 8 && f + 1 == a.nf && next) { xload<M>(pn, a.in1 + noff); have_pn = true; }     // the next line's velocity
+                if (have_next) xload<M, STG>(un, a.fs[f + 1] + off);
+                if (PIPE && M <= 8 && f + 1 == a.nf && next) { xload<M, STG>(pn, a.in1 + noff); have_pn = true; }     // the next line's velocity
                 double um[3], up[3];
                 xhalo<M, WPL>(cx, u, um, up);
                 double x1[M], x2[M];
@@ -444,7 +510,8 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
 #pragma unroll
                 for (int p = 0; p < M; ++p) x2[p] = nuf * x2[p] - v[p] * x1[p];      // opr_burgers.f90:513
                 if (a.acc) {
-                    if (!PIPE) xload<M>(o, dst + off);
+                    if (!PIPE) xload<M, STG>(o, dst + off);
+                    xin<STG, M>(o, sg);
 #pragma unroll
                     for (int p = 0; p < M; ++p) x2[p] = o[p] + x2[p];
                 }
@@ -456,7 +523,7 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
                         xhalo<M, WPL>(cx, wq, um, up);
                         xsten<M, false, WPL, PER>(x1, wq, um, up, a.s1, lane);
                         xsolve<M, LV, WPL, CL>(x1, y1, cx, n);
-                        if (live) xstore<M>(a.fdiv + off, x1);
+                        if (live) { xout<STG, M>(x1, sg); xstore<M, STG>(a.fdiv + off, x1); }
                     }
                     if (a.ffin[f]) {          // the tendency of this field is complete: wall planes, Runge-Kutta update, scaling (k_final_update's arithmetic)
                         const int j = (int)(line % a.fny);
@@ -474,10 +541,10 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
                                 for (int p = 0; p < M; ++p) u[p] = fmin(fmax(u[p], lo), hi);
                             }
                         }
-                        if (live) xstore<M>(const_cast<double *>(src) + off, u);
+                        if (live) { xout<STG, M>(u, sg); xstore<M, STG>(const_cast<double *>(src) + off, u); }
                     }
                 }
-                if (live) xstore<M>(dst + off, x2);
+                if (live) { xout<STG, M>(x2, sg); xstore<M, STG>(dst + off, x2); }
             }
         } else {
             double u[M];
@@ -485,7 +552,7 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
 #pragma unroll
                 for (int p = 0; p < M; ++p) u[p] = pn[p];
             } else {
-                xload<M>(u, a.in0 + off);
+                xload<M, STG>(u, a.in0 + off);
             }
             if (MODE == MODE_P1 && a.in0b != nullptr) {   // operand = in0 + s * in0b
                 double ub[M];
@@ -493,16 +560,17 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
 #pragma unroll
                     for (int p = 0; p < M; ++p) ub[p] = pbn[p];
                 } else {
-                    xload<M>(ub, a.in0b + off);
+                    xload<M, STG>(ub, a.in0b + off);
                 }
 #pragma unroll
                 for (int p = 0; p < M; ++p) u[p] = u[p] + ub[p] * a.in0b_scale;
             }
+            xin<STG, M>(u, sg);          // (the operand sum above is element-wise: done in the layout of the loads)
             have_pn = false;
             if constexpr (M <= 8) {
                 if (next) {
-                    xload<M>(pn, a.in0 + noff);
-                    if constexpr (MODE == MODE_P1) { if (a.in0b != nullptr) xload<M>(pbn, a.in0b + noff); }
+                    xload<M, STG>(pn, a.in0 + noff);
+                    if constexpr (MODE == MODE_P1) { if (a.in0b != nullptr) xload<M, STG>(pbn, a.in0b + noff); }
                     have_pn = true;
                 }
             }
@@ -510,10 +578,10 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
             double h[MODE == MODE_P1 ? M : 1], qv[MODE == MODE_P1 ? M : 1];
             if constexpr (MODE == MODE_P1) {
                 if (a.fq != nullptr) {
-                    xload<M>(h, a.out0 + off);
-                    xload<M>(qv, a.fq + off);
+                    xload<M, STG>(h, a.out0 + off);
+                    xload<M, STG>(qv, a.fq + off);
                 } else if (a.acc) {
-                    xload<M>(h, a.out0 + off);
+                    xload<M, STG>(h, a.out0 + off);
                 }
             }
             double um[3], up[3];
@@ -528,32 +596,35 @@ __global__ void __launch_bounds__(TPB, (OCC > 1 && TPB > 256) ? 1 : OCC) k_xline
                 xsolve<M, LV2, WPL, CL>(x2, y2, cx, n);
             }
             if (!live) continue;                     // (WPL > 1: after the last barrier of this line)
+            // STG: the epilogues are element-wise, so the results change to the layout of the loads and h, qv and the wall planes stay in it
+            if (NEED1) xout<STG, M>(x1, sg);
+            if (NEED2) xout<STG, M>(x2, sg);
             if constexpr (MODE == MODE_P1) {
                 if (a.fq != nullptr) {          // final-update epilogue: the line is (j, k) = (line % ny, line / ny)
                     const int j = (int)(line % a.fny);
                     const bool wall = (j == 0) || (j == a.fny - 1);
                     const double *wp = wall ? (j == 0 ? a.fpb : a.fpt) : nullptr;      // given wall tendencies (Neumann walls), or zero
-                    if (wp != nullptr) wp += (line / a.fny) * n + gl * M;
+                    if (wp != nullptr) wp += (line / a.fny) * n + (STG ? 2 * lane : gl * M);
 #pragma unroll
                     for (int p = 0; p < M; ++p) {
-                        const double hv = wall ? (wp ? wp[p] : 0.0) : h[p] - x1[p];
+                        const double hv = wall ? (wp ? wp[xlin<STG>(p)] : 0.0) : h[p] - x1[p];
                         qv[p] = qv[p] + a.fdte * hv;
                         h[p] = a.fscale ? a.fkco * hv : hv;
                     }
-                    xstore<M>(a.fq + off, qv);
-                    xstore<M>(a.out0 + off, h);
+                    xstore<M, STG>(a.fq + off, qv);
+                    xstore<M, STG>(a.out0 + off, h);
                 } else {
                     if (a.acc) {
 #pragma unroll
                         for (int p = 0; p < M; ++p) x1[p] = (a.acc == 2) ? h[p] - x1[p] : h[p] + x1[p];
                     }
-                    xstore<M>(a.out0 + off, x1);
+                    xstore<M, STG>(a.out0 + off, x1);
                 }
             } else if constexpr (MODE == MODE_P2) {
-                xstore<M>(a.out0 + off, x2);
+                xstore<M, STG>(a.out0 + off, x2);
             } else {   // MODE_P2_P1
-                xstore<M>(a.out0 + off, x2);
-                xstore<M>(a.out1 + off, x1);
+                xstore<M, STG>(a.out0 + off, x2);
+                xstore<M, STG>(a.out1 + off, x1);
             }
         }
     }
@@ -974,8 +1045,15 @@ __global__ void __launch_bounds__(256) k_transpose(const double *__restrict__ a,
 // ============================================================================================
 static inline int imin(long long a, long long b) { return (int)(a < b ? a : b); }
 
-template <int M, int LV, int WPL, int LV2 = LV, int TPB = 256, bool CL = false, bool PER = false, int OCC = 1>
-static hipError_t launch_xline_m(int mode, const XLineArgs &a_in, hipStream_t st) {
+template <auto KERN>
+static void xline_go(int grid, int tpb, size_t lds, hipStream_t st, const XLineArgs &a) {
+    static bool attr = false;       // per kernel
+    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(tpb), lds, st, a);
+}
+// STG: the staged forms of the kernel (k_xline above); instantiated for the first derivative and the fused Burgers launch only
+template <int M, int LV, int WPL, int LV2 = LV, int TPB = 256, bool CL = false, bool PER = false, int OCC = 1, bool STG = false>
+static hipError_t launch_xline_m(int mode, const XLineArgs &a_in, hipStream_t st, bool direct_tag = false) {
     static const int lb = [] { const char *e = getenv("TLAB_XLINE_LINE_BARRIERS"); return e ? atoi(e) : 1; }();
     XLineArgs a = a_in;
     a.line_barriers = lb;
@@ -987,7 +1065,8 @@ static hipError_t launch_xline_m(int mode, const XLineArgs &a_in, hipStream_t st
     auto tabbytes = [](int lv) { return lv == 1 ? (size_t)5 * M * P * sizeof(double) : lv == 2 ? (size_t)5 * M * P * sizeof(float) : (size_t)0; };
     const size_t redbytes = CL ? ((size_t)XRL * P + 6 * WPL) * sizeof(double) : 0;
     const size_t lds = (mode != MODE_P2 ? tabbytes(LV) + redbytes : 0) + (mode != MODE_P1 ? tabbytes(LV2) + redbytes : 0) +
-                       (WPL > 1 ? ((size_t)LPB * 14 * WPL + LPB) * sizeof(double) : 0);      // exchange buffers + one arrival counter per line
+                       (WPL > 1 ? ((size_t)LPB * 14 * WPL + LPB) * sizeof(double) : 0) +     // exchange buffers + one arrival counter per line
+                       (STG ? (size_t)(TPB / 64) * XSTG_ROW : 0);                            // one row per wave
     const double pts = (double)a.nlines * P * M;
     static const char *names[5] = {"", "k_xline<P1>", "k_xline<P2>", "k_xline<P2_P1>", "k_xline<BURGERS>"};
     const double bpp[5] = {0, 16, 16, 24, 24};
@@ -997,6 +1076,14 @@ static hipError_t launch_xline_m(int mode, const XLineArgs &a_in, hipStream_t st
         for (int f = 0; f < a.nf; ++f) bytes += pts * ((a.fs[f] == a.in1 ? 0 : 8) + 8 + (a.acc ? 8 : 0) + (a.ffin[f] ? 8 : 0));
         if (a.fdiv) bytes += pts * 8;       // epilogues: updated scalar, x term of the pressure forcing
     }
+    if constexpr (STG) {      // (CL: the fused Burgers launch and its CLIP twin; otherwise the first derivative)
+        if (mode != (CL ? MODE_BURGERS : MODE_P1)) return hipErrorInvalidValue;
+        ProfScope ps(names[mode], st, bytes);
+        if constexpr (!CL) xline_go<&k_xline<M, MODE_P1, LV, WPL, LV2, TPB, CL, PER, OCC, false, true>>(grid, TPB, lds, st, a);
+        else if (a.fclip[0] || a.fclip[1] || a.fclip[2] || a.fclip[3]) xline_go<&k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC, true, true>>(grid, TPB, lds, st, a);
+        else xline_go<&k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC, false, true>>(grid, TPB, lds, st, a);
+        return hipGetLastError();
+    }
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xline<M, MODE_P1, LV, WPL, LV2, TPB, CL, PER, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1005,7 +1092,7 @@ static hipError_t launch_xline_m(int mode, const XLineArgs &a_in, hipStream_t st
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_xline<M, MODE_BURGERS, LV, WPL, LV2, TPB, CL, PER, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr = true;
     }
-    ProfScope ps(names[mode], st, bytes);
+    ProfScope ps(direct_tag ? (mode == MODE_P1 ? "k_xline<P1,direct>" : "k_xline<BURGERS,direct>") : names[mode], st, bytes);
     switch (mode) {
     case MODE_P1: hipLaunchKernelGGL((k_xline<M, MODE_P1, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a); break;
     case MODE_P2: hipLaunchKernelGGL((k_xline<M, MODE_P2, LV, WPL, LV2, TPB, CL, PER, OCC>), dim3(grid), dim3(TPB), lds, st, a); break;
@@ -1086,6 +1173,14 @@ hipError_t launch_xline(int mode, int n, int chunks, bool lane_variant, const XL
         // (256 VGPRs, no AGPRs, two waves per SIMD) instead of everything in 256 + 102 registers and one wave per SIMD: 3.09 -> 2.94 ms on a box in
         // its fast state, 3.26 -> 3.20 on one in its slow state (A/B, profiles/r05/xline_occupancy.txt); TLAB_XLINE_OCC=1 keeps the old form
         static const int occ = [] { const char *e = getenv("TLAB_XLINE_OCC"); return e ? atoi(e) : 3; }();
+        // coalesced line accesses through a wave-private LDS row (k_xline, STG) for the default forms of the first derivative and of the fused Burgers
+        // launch; TLAB_XLINE_STAGE=0 keeps the direct accesses, read per launch (A/B in one process), reported as k_xline<...,direct>
+        if (a.s1.periodic && ((mode == MODE_P1 && occ != 5) || (mode == MODE_BURGERS && occ == 3))) {
+            const char *se = getenv("TLAB_XLINE_STAGE");
+            if (se == nullptr || atoi(se) != 0)
+                return mode == MODE_P1 ? launch_xline_m<8, 1, 1, 1, 256, false, true, 1, true>(mode, a, st) : launch_xline_m<8, 1, 1, 1, 256, true, true, 2, true>(mode, a, st);
+            return mode == MODE_P1 ? launch_xline_m<8, 1, 1, 1, 256, false, true>(mode, a, st, true) : launch_xline_m<8, 1, 1, 1, 256, true, true, 2>(mode, a, st, true);
+        }
         if (a.s1.periodic && occ == 2 && mode == MODE_BURGERS) return launch_xline_m<8, 1, 1, 1, 256, false, true, 2>(mode, a, st);
         if (a.s1.periodic && occ == 3 && mode == MODE_BURGERS) return launch_xline_m<8, 1, 1, 1, 256, true, true, 2>(mode, a, st);
         if (a.s1.periodic && occ == 4 && mode == MODE_BURGERS) return launch_xline_m<8, 1, 1, 1, 512, true, true, 2>(mode, a, st);      // one 8-wave workgroup per CU sharing the tables
