@@ -360,6 +360,45 @@ int tlab_buffer_tau(int n, const double *nodes, int offset, int size, double str
  * to HOST arrays of DEVICE pointers (q[3], hq[3]; s[nscal], hs[nscal]).  Planes outside the zones are neither read nor written. */
 int tlab_dns_buffer_relax_flow(tlab_dns_t d, double *const *q, double *const *hq);
 int tlab_dns_buffer_relax_scal(tlab_dns_t d, double *const *s, double *const *hs);
+/* Body forces, [Rotation] and [BodyForce]: TLab_Sources_Flow (src/physics/tlab_sources.f90:36-92), which the reference's substep calls on (q, s, hq)
+ * before the RHS (tools/dns/time.f90:610-612).  One kernel launch applies both: Rotation_Coriolis (rotation.f90:103-143) first, then
+ * hq_i = hq_i + g_i b for every g_i != 0 with b of Gravity_Buoyancy (gravity.f90:232-342), unfused multiplies and adds in the reference's order.
+ *   Coriolis: type TLAB_COR_EXPLICIT (vector = f already divided by Rossby: hq1 = (hq1 + f3 v) - f2 w, and cyclic) or TLAB_COR_NORMALIZED
+ *     (hq1 += f2 (geo_w - w), hq3 += f2 (u - geo_u), geo_u = cos(p1) p2, geo_w = -sin(p1) p2 formed on the host; vector (0, f2, 0) only: f1 or f3 != 0
+ *     is TLAB_EINVAL, the reference stops there).  parameters: 2 values, read for _NORMALIZED only.
+ *   Buoyancy: vector = g already divided by Froude; nscalars = buoyancy%scalar(1); parameters: nparameters HOST values (those beyond read as zero);
+ *     inb_scal_array: for TLAB_BOD_LINEAR the independent term is parameters[inb_scal_array] (gravity.f90:253); bbackground: ny HOST values, copied,
+ *     or NULL for zeros.  TLAB_BOD_HOMOGENEOUS b = p1; _LINEAR b = ((c1 s1 + c2 s2) + c3 s3) - (ref(j) - c0) with 1..3 scalars, the general branch
+ *     (:279-291) otherwise (at most 6 scalars with a factor above small_wp: more is TLAB_EUNSUPPORTED); _BILINEAR b = ((c0 s1 + c1 s2) + (c2 s1) s2) - ref(j); _QUADRATIC
+ *     b = (c0 s1)(s1 - c1) - ref(j), c0 = -p1 / (p2/2)^2.
+ *   TLAB_EUNSUPPORTED, nothing stored: _EXPLICIT (Thermo_Anelastic_BUOYANCY), _NORMALIZEDMEAN and _SUBTRACTMEAN (they need the plane means FI_DIAGNOSTIC
+ *     refreshes every substep), nscalars > nscal (diagnostic arrays such as liquid water are not held on the device).
+ *   TLAB_EINVAL: an unknown type, NaN or infinite values, a null handle, a type that reads scalars on a driver without them.  The arguments are
+ *     checked before the handle.  Type 0 switches the term off; with both off, or all vectors zero, the driver launches the kernels of a run without
+ *     forces, the results bit for bit.
+ * tlab_time_substep_incompressible_explicit applies them once: on the fused routes where the flow buffer-zone launch goes (every tendency holds a
+ * partial sum, none is finished; q and s are those from before the update), on the literal routes after the Burgers sums; always before the pressure
+ * forcing and the wall planes of hq2 that become the Neumann data of the Poisson solver, so the force is projected.  Against the reference the terms
+ * are summed in another order: rounding only.  tlab_rhs_global_incompressible_1 does not apply them (the reference's RHS does not either).
+ * Not built: subsidence, SpecialForcing, TLab_Sources_Scal (radiation, sedimentation, chemistry), Gravity_Buoyancy_Source, the statistics' buoyancy. */
+#define TLAB_COR_NONE 0
+#define TLAB_COR_EXPLICIT 4
+#define TLAB_COR_NORMALIZED 12
+#define TLAB_BOD_NONE 0
+#define TLAB_BOD_EXPLICIT 4
+#define TLAB_BOD_HOMOGENEOUS 5
+#define TLAB_BOD_LINEAR 6
+#define TLAB_BOD_BILINEAR 7
+#define TLAB_BOD_QUADRATIC 8
+#define TLAB_BOD_NORMALIZEDMEAN 9
+#define TLAB_BOD_SUBTRACTMEAN 10
+int tlab_dns_set_coriolis(tlab_dns_t d, int type, const double *vector, const double *parameters);
+int tlab_dns_set_buoyancy(tlab_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters, int inb_scal_array,
+                          const double *bbackground);
+/* TLab_Sources_Flow on its own: hq += the terms above and nothing else.  HOST arrays of DEVICE pointers q[3], s[nscal], hq[3]; a component no force
+ * touches is neither read nor written, a velocity or scalar no active term needs is not read.  At most 2^31 - 1 points. */
+int tlab_dns_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq);
+long long tlab_dns_info(tlab_dns_t d, int what);      /* 0 nx, 1 ny, 2 nz, 3 nscal, 4 points of a field; -1: null handle or unknown code */
 /* Start of a Runge-Kutta step: TIME_RUNGEKUTTA sets hq = 0, hs = 0 there (tools/dns/time.f90:212-216).  Instead of filling the arrays,
  * tell the driver: the next tlab_rhs_global_incompressible_1 / tlab_time_substep_incompressible_explicit treats them as zero (its first
  * operator launch overwrites instead of accumulating), whatever they contain. */
@@ -395,6 +434,14 @@ int tlab_deferred_clip(long long n, double lo, double hi, double *x);
  * The relax statistics give counts[2]: fused substeps that carried a recorded relaxation, relaxations executed on their own. */
 int tlab_deferred_relax_scal(tlab_dns_t d);
 int tlab_deferred_relax_stats(long long *counts);
+/* TLab_Sources_Flow of an unchanged host (time.f90:610, through tlab_amd/fortran/tlab_sources_device.sed).  Layer off: tlab_dns_sources_flow.  On: a
+ * pending record runs first and the call is kept as a marker.  A tlab_deferred_rhs of the same driver on the same arrays straight after it makes the
+ * record sources, RHS, [relaxation], DAXPY x (3 + ns), [clips], [DSCAL x (3 + ns)], which runs as the ONE fused substep with the forces in it.  A
+ * record WITHOUT the marker is replayed without forces.  Anything else -- another driver, other arrays, a second marker, something that wants the
+ * stream while only the marker is pending -- makes the marker run literally, in call order, after REAL zero fills where zero fills were recorded.
+ * The statistics give counts[2]: fused substeps that carried the marker, markers executed on their own. */
+int tlab_deferred_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq);
+int tlab_deferred_sources_stats(long long *counts);
 /* counts[6]: fused substeps run, sequences executed literally, begin_steps taken from zero fills, eager axpy, eager scal, eager zero fills */
 int tlab_deferred_stats(long long *counts);
 /* counts[2]: fused substeps that carried recorded clips (of counts[0] above), clips executed on their own (tlab_pw_clip) */
@@ -569,6 +616,11 @@ int tlab_pencil_dns_set_bcs(tlab_pencil_dns_t d, const int *flow_jmin, const int
 /* buffer zones, as tlab_dns_set_buffer_zone, for the local rank l with ref for that rank's box (imax, size, kmax, nfields): local, no exchange.
  * tlab_pencil_dns_rhs applies the flow blocks before the pressure forcing, tlab_pencil_dns_substep the scalar blocks before its update. */
 int tlab_pencil_dns_set_buffer_zone(tlab_pencil_dns_t d, int l, int end, int group, int size, int nfields, const double *tau, const double *ref);
+/* body forces, as tlab_dns_set_coriolis / _set_buoyancy, for every local rank (bbackground is the global profile: every box has the full y extent).
+ * tlab_pencil_dns_substep applies them in one launch per rank once the Burgers sums of hq are complete, before the forcing; tlab_pencil_dns_rhs does not. */
+int tlab_pencil_dns_set_coriolis(tlab_pencil_dns_t d, int type, const double *vector, const double *parameters);
+int tlab_pencil_dns_set_buoyancy(tlab_pencil_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters,
+                                 int inb_scal_array, const double *bbackground);
 /* scalar bounds limiting, as tlab_dns_set_scalar_bounds: applied by tlab_pencil_dns_substep in the update pass of each limited scalar */
 int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi);
 int tlab_pencil_dns_begin_step(tlab_pencil_dns_t d);
@@ -624,6 +676,12 @@ int tlab_slab_dns_set_remove_divergence(tlab_slab_dns_t d, int on);
  * split, so the relaxation is local and needs no exchange.  The flow blocks act before hq is read for the pressure forcing, the scalar blocks after
  * the wall BCs of hs and before the update (scalars under a zone take a separate update pass). */
 int tlab_slab_dns_set_buffer_zone(tlab_slab_dns_t d, int l, int end, int group, int size, int nfields, const double *tau, const double *ref);
+/* body forces, as tlab_dns_set_coriolis / _set_buoyancy, for every local rank (bbackground is the global profile: every box has the full y extent).
+ * tlab_slab_dns_substep applies them in one launch per rank after the first term of every tendency and before the z pass that finishes the scalars;
+ * tlab_slab_dns_rhs does not. */
+int tlab_slab_dns_set_coriolis(tlab_slab_dns_t d, int type, const double *vector, const double *parameters);
+int tlab_slab_dns_set_buoyancy(tlab_slab_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters,
+                               int inb_scal_array, const double *bbackground);
 /* scalar bounds limiting, as tlab_dns_set_scalar_bounds: applied by tlab_slab_dns_substep, one pass per limited scalar after the substep */
 int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi);
 /* as tlab_dns_set_surface_bcs: the dynamic surface model of the scalars on z-slabs.  The plane average of BOUNDARY_BCS_SURFACE_Y (AVG1V2D,

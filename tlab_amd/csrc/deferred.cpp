@@ -20,6 +20,7 @@
 // MI355X): such a host calls tlab_deferred_flush() or tlab_sync() first, or keeps the layer off (the default).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -59,6 +60,8 @@ struct Pending {
     std::vector<double> clo, chi;
     int nclp = 0;
     bool relax = false;                           // tlab_deferred_relax_scal recorded straight after the RHS (time.f90:628-630)
+    bool sources = false;                         // tlab_deferred_sources_flow came straight before the RHS, same driver and arrays (time.f90:610-612)
+    std::function<int()> sources_flow;            // ... and the routine on its own, for a literal run
     std::vector<Range> zeros;                     // `hq = 0` of the start of a step, not yet executed
 };
 Pending g_p;
@@ -66,6 +69,16 @@ bool g_on = false, g_busy = false;
 long long g_stat[6] = {0, 0, 0, 0, 0, 0};        // fused substeps, literal flushes, begin_steps, eager axpy, eager scal, eager zero
 long long g_clip_stat[2] = {0, 0};                // fused substeps that carried recorded clips, clips executed on their own
 long long g_relax_stat[2] = {0, 0};               // fused substeps that carried a recorded scalar relaxation, relaxations executed on their own
+long long g_src_stat[2] = {0, 0};                 // fused substeps that carried the sources marker, markers executed on their own
+// tlab_deferred_sources_flow not yet followed by anything: the call is kept; a tlab_deferred_rhs of the same driver on the same arrays takes it into
+// its record, anything else makes it run literally, in call order
+struct Marker {
+    bool on = false;
+    tlab_dns_t d = nullptr;
+    std::vector<double *> q, s, hq;
+    int run() const { return tlab_dns_sources_flow(d, q.data(), s.empty() ? nullptr : s.data(), hq.data()); }
+};
+Marker g_src;
 Driver g_last;                                    // the driver of the last tlab_deferred_rhs (a relaxation that meets no record runs on its arrays)
 
 struct Busy {
@@ -119,7 +132,10 @@ int run_substep(Pending &p, double kco, int scale) {
     p.drv.bounds->swap(b);
     // ... and the scalar buffer zones of the driver act in it only when the record holds the relaxation: RHS + DAXPY alone does not relax the scalars
     const bool was = p.drv.scal_zones ? p.drv.scal_zones(p.relax) : true;
+    // ... and the body forces only when it holds the sources marker
+    const bool forces_were = tlab_internal_dns_forces_in_substep(p.sources);
     const int rc = p.drv.substep(p.dte, kco, scale);
+    (void)tlab_internal_dns_forces_in_substep(forces_were);
     if (p.drv.scal_zones) (void)p.drv.scal_zones(was);
     p.drv.bounds->swap(b);
     return rc;
@@ -140,17 +156,31 @@ void record(Driver drv, double dte, int ns, long long n, double *const *q, doubl
     p.clp.assign(ns, 0); p.clo.assign(ns, 0.0); p.chi.assign(ns, 0.0);
     p.nclp = 0;
     p.relax = false;
+    p.sources = false;
+    p.sources_flow = nullptr;
 }
 
 // whole_ok = false: the record is cut short by a call that does not belong to the fused substep; it counts as a literal run
 int flush_impl(bool whole_ok = true) {
     if (g_busy) return TLAB_OK;
     Busy b;
-    if (!g_p.rhs) return run_zeros_eagerly();
+    if (!g_p.rhs) {                    // zero fills and / or a sources marker that nothing followed: literally, in call order
+        int rc = run_zeros_eagerly();
+        if (g_src.on) {
+            Marker m;
+            std::swap(m, g_src);
+            ++g_src_stat[1];
+            if (rc == TLAB_OK) rc = m.run();
+        }
+        return rc;
+    }
     Pending p;
     std::swap(p, g_p);                 // whatever runs below sees an empty description
     int rc = TLAB_OK;
-    if (zeros_are_the_tendencies(p)) {
+    const bool fused = whole_ok && p.nupd == p.nf && (p.nscl == 0 || p.nscl == p.nf);
+    // (a record with the sources marker that runs literally executes REAL zero fills: the routine on its own adds to what the tendencies hold, and
+    // tendencies that only count as zero hold the last step's values)
+    if (zeros_are_the_tendencies(p) && !(p.sources && !fused && p.nupd != p.nf)) {
         ++g_stat[2];
         rc = p.drv.begin_step();
     } else {
@@ -164,6 +194,7 @@ int flush_impl(bool whole_ok = true) {
         ++g_stat[0];
         if (p.nclp) ++g_clip_stat[0];
         if (p.relax) ++g_relax_stat[0];
+        if (p.sources) ++g_src_stat[0];
         return run_substep(p, p.nscl ? p.kco : 1.0, p.nscl ? 1 : 0);
     }
     ++g_stat[1];
@@ -173,7 +204,8 @@ int flush_impl(bool whole_ok = true) {
             if (p.scl[f]) rc = tlab_pw_scale(p.x[f], p.kco, p.n);
         return rc;
     }
-    rc = p.drv.rhs(p.dte);
+    if (p.sources) { ++g_src_stat[1]; rc = p.sources_flow(); }      // (the marker stood before the RHS)
+    if (rc == TLAB_OK) rc = p.drv.rhs(p.dte);
     if (p.relax && rc == TLAB_OK) { ++g_relax_stat[1]; rc = p.drv.relax_scal(); }      // (recorded before every DAXPY)
     for (int f = 0; f < p.nf && rc == TLAB_OK; ++f)
         if (p.upd[f]) rc = tlab_pw_rk_update(p.y[f], p.x[f], p.dte, 1.0, 0, p.n);
@@ -190,7 +222,7 @@ static int g_sticky = TLAB_OK;
 int tlab_internal_deferred_flush() {
     if (g_busy) return TLAB_OK;
     int rc = TLAB_OK;
-    if (g_on && (g_p.rhs || !g_p.zeros.empty())) rc = flush_impl();
+    if (g_on && (g_p.rhs || !g_p.zeros.empty() || g_src.on)) rc = flush_impl();
     if (rc != TLAB_OK && g_sticky == TLAB_OK) g_sticky = rc;
     return rc;
 }
@@ -256,10 +288,33 @@ int tlab_deferred_relax_scal(tlab_dns_t d) {
     return drv.relax_scal();
 }
 
+int tlab_deferred_sources_stats(long long *counts) {
+    if (!counts) return TLAB_EINVAL;
+    counts[0] = g_src_stat[0];
+    counts[1] = g_src_stat[1];
+    return TLAB_OK;
+}
+
+// TLab_Sources_Flow of an unchanged host (time.f90:610, through tlab_amd/fortran/tlab_sources_device.sed).  Off: the routine on its own.  On: a pending
+// record runs first, then the call is kept as a marker for the tlab_deferred_rhs that follows (see Marker above).
+int tlab_deferred_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq) {
+    if (!g_on) return tlab_dns_sources_flow(d, q, s, hq);
+    if (!d || !q || !hq) { tlab_set_error("tlab_deferred_sources_flow: bad arguments"); return TLAB_EINVAL; }
+    const int ns = tlab_internal_dns_nscal(d);
+    if (ns > 0 && !s) { tlab_set_error("tlab_deferred_sources_flow: bad arguments"); return TLAB_EINVAL; }
+    if (g_p.rhs || g_src.on) {         // (a marker nothing followed runs literally, after the zero fills that came before it)
+        const int rc = flush_impl();
+        if (rc != TLAB_OK) return rc;
+    }
+    g_src.on = true; g_src.d = d;
+    g_src.q.assign(q, q + 3); g_src.s.assign(s, s + ns); g_src.hq.assign(hq, hq + 3);
+    return TLAB_OK;
+}
+
 int tlab_deferred_zero(double *a, long long n) {
     if (!a || n < 0) { tlab_set_error("tlab_deferred_zero: bad arguments"); return TLAB_EINVAL; }
     if (!g_on) { ++g_stat[5]; return tlab_pw_fill(a, 0.0, n); }
-    if (g_p.rhs) {                       // a substep is still described: it runs first (its fields may be the ones zeroed here)
+    if (g_p.rhs || g_src.on) {                       // a substep is still described: it runs first (its fields may be the ones zeroed here)
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }
@@ -271,7 +326,13 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
     if (!d || !q || !hq || !txc || dte <= 0.0) { tlab_set_error("tlab_deferred_rhs: bad arguments"); return TLAB_EINVAL; }
     const int ns = tlab_internal_dns_nscal(d);
     if (ns > 0 && (!s || !hs)) { tlab_set_error("tlab_deferred_rhs: bad arguments"); return TLAB_EINVAL; }
-    if (g_on && g_p.rhs) {
+    // a sources marker belongs to this RHS when it names the same driver and the same arrays; otherwise it runs literally now
+    bool sources = false;
+    if (g_on && g_src.on) {
+        sources = g_src.d == d && std::equal(q, q + 3, g_src.q.begin()) && std::equal(hq, hq + 3, g_src.hq.begin()) && std::equal(s, s + ns, g_src.s.begin());
+        if (sources) g_src = Marker();
+    }
+    if (g_on && (g_p.rhs || g_src.on)) {
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }
@@ -293,6 +354,8 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
     g_last = drv;
     if (!g_on) return drv.rhs(dte);
     record(std::move(drv), dte, ns, tlab_internal_dns_points(d), q, s, hq, hs);
+    g_p.sources = sources;
+    if (sources) g_p.sources_flow = [=] { return tlab_dns_sources_flow(d, Q.data(), ns ? S.data() : nullptr, HQ.data()); };
     return TLAB_OK;
 }
 
@@ -300,10 +363,10 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
 // bound: tlab_internal_{slab,pencil}_bound found the arrays of the one local rank (b)
 static int deferred_decomposed(Driver drv, bool bound, const tlab_bound_fields &b, double dte) {
     if (!g_on || !bound || !(dte > 0.0)) {      // off, or nothing to match the BLAS calls against (several local ranks): at once
-        if (g_on) { const int rc = flush_impl(); if (rc != TLAB_OK) return rc; }
+        if (g_on) { const int rc = flush_impl(); if (rc != TLAB_OK) return rc; }      // (with a sources marker that nothing of its driver followed)
         return drv.rhs(dte);
     }
-    if (g_p.rhs) {
+    if (g_p.rhs || g_src.on) {
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }

@@ -92,6 +92,10 @@ tlab::ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d);      // deferred.cpp
 bool tlab_internal_dns_has_flow_zones(tlab_dns_t d);      // slab.cpp: the zones of a rank live in its single-domain handle
 bool tlab_internal_dns_has_scal_zones(tlab_dns_t d);
 bool tlab_internal_dns_scal_zones_in_substep(tlab_dns_t d, bool on);
+// deferred.cpp: the switch that makes the substeps of the three drivers apply the body forces (returns the old setting; one for the process, it is
+// held only around the one replayed call); slab.cpp, pencil.cpp: the forces of a rank live in its single-domain handle -- set, and the switch on?
+bool tlab_internal_dns_forces_in_substep(bool on);
+bool tlab_internal_dns_forces_active(tlab_dns_t d);
 // shared by the three drivers: n entries (<= nscal) of active / lo / hi checked, the bounds of the active ones returned (on[is] = 0 otherwise)
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi);

@@ -194,6 +194,19 @@ hipError_t launch_buffer_relax(int nf, double *const *h, const double *const *a,
 hipError_t launch_buffer_relax_plane(int nf, double *const *h, double *const *s, const double *ref, const double *tau, const double *const *bc,
                                      const ClipBounds *const *clip, double dte, double kco, int scale, int nx, int ny, int nz, int offset, int size,
                                      int jloc, hipStream_t st);
+// TLab_Sources_Flow (tlab_sources.f90:36-92) in one launch (k_body_force): Coriolis, then hq_i += g_i b.  cor: 0 off, 1 EQNS_COR_EXPLICIT, 2
+// EQNS_COR_NORMALIZED; bod: 0 off, 1 HOMOGENEOUS, 2 LINEAR with 1..3 scalars, 3 LINEAR general branch, 4 BILINEAR, 5 QUADRATIC.  f, g: the vectors;
+// c: the coefficients as the kernel takes them; sidx: which scalar feeds slot is (ns slots in use); prof: ny device values (bod >= 2).  Arrays no
+// active term needs are not accessed and may be NULL; with nothing active nothing is launched.  At most 2^31 - 1 points.
+constexpr int BODY_FORCE_MAX_SCAL = 6;
+struct BodyForce {
+    int cor = 0, bod = 0, ns = 0;
+    double f[3] = {0, 0, 0}, g[3] = {0, 0, 0}, c[BODY_FORCE_MAX_SCAL] = {0, 0, 0, 0, 0, 0}, geo_u = 0.0, geo_w = 0.0;
+    int sidx[BODY_FORCE_MAX_SCAL] = {0, 1, 2, 3, 4, 5};
+    bool any() const { return (cor == 1 && (f[0] != 0.0 || f[1] != 0.0 || f[2] != 0.0)) || (cor == 2 && f[1] != 0.0) || (bod != 0 && (g[0] != 0.0 || g[1] != 0.0 || g[2] != 0.0)); }
+};
+hipError_t launch_body_force(const BodyForce &F, double *const *hq, const double *const *q, const double *const *s, const double *prof, int nx, int ny,
+                             int nz, hipStream_t st);
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,

@@ -339,6 +339,14 @@ void relax_scal(D *d) {
         if (R.dns && tlab_internal_dns_has_scal_zones(R.dns)) ok(tlab_dns_buffer_relax_scal(R.dns, R.s.data(), R.hs.data()), "tlab_dns_buffer_relax_scal");
 }
 
+// TLab_Sources_Flow (time.f90:610; tlab_pencil_dns_set_coriolis / _set_buoyancy) of the substep under way: y is never split, so the launch of a rank
+// acts on its box with the global profile.  Called where every Burgers sum of hq is complete and before hq is read for the forcing.
+void body_forces(D *d) {
+    if (!d->fin.on) return;      // (the RHS on its own adds no force)
+    for (Rank &R : d->rk)
+        if (R.dns && tlab_internal_dns_forces_active(R.dns)) ok(tlab_dns_sources_flow(R.dns, R.q.data(), R.s.data(), R.hq.data()), "tlab_dns_sources_flow");
+}
+
 void rhs(D *d, double dte) {
     need_bound(d);
     if (tlab_internal_anelastic() || tlab_internal_dealiasing())
@@ -375,6 +383,7 @@ void rhs(D *d, double dte) {
         add3([i](Rank &R) { return R.hs[i]; }, 0, 1, 2);
     }
     relax_flow(d);                                                                // :170-172
+    body_forces(d);
     // pressure (:188-260)
     for (Rank &R : d->rk)
         ok(tlab_pw_axpy3(R.txc[1], R.txc[2], R.txc[3], R.hq[1], R.hq[0], R.hq[2], R.q[1], R.q[0], R.q[2], 1.0 / dte, n), "tlab_pw_axpy3");
@@ -631,6 +640,7 @@ void rhs_overlapped(D *d, double dte) {
     // sum of an earlier equation standing before the y term of a later one that reuses its set)
     run_pipeline(d, ops, local);
     relax_flow(d);                                                                // :170-172
+    body_forces(d);
     // pressure (:188-260)
     for (Rank &R : d->rk)
         ok(tlab_pw_axpy3(R.txc[1], R.txc[2], R.txc[3], R.hq[1], R.hq[0], R.hq[2], R.q[1], R.q[0], R.q[2], 1.0 / dte, n), "tlab_pw_axpy3");
@@ -925,6 +935,24 @@ int tlab_pencil_dns_set_buffer_zone(tlab_pencil_dns_t d, int l, int end, int gro
     return catch_fail([&] {
         if (!d || l < 0 || l >= (int)d->rk.size()) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_set_buffer_zone: bad handle or local rank");
         ok(tlab_dns_set_buffer_zone(dns_handle(d, d->rk[l]), end, group, size, nfields, tau, ref), "tlab_dns_set_buffer_zone");
+    }, TLAB_EINVAL);
+}
+
+int tlab_pencil_dns_set_coriolis(tlab_pencil_dns_t d, int type, const double *vector, const double *parameters) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) ok(tlab_dns_set_coriolis(nullptr, type, vector, parameters), "tlab_dns_set_coriolis");      // (the argument checks come first, as there)
+        for (Rank &R : d->rk) ok(tlab_dns_set_coriolis(dns_handle(d, R), type, vector, parameters), "tlab_dns_set_coriolis");
+    }, TLAB_EINVAL);
+}
+
+int tlab_pencil_dns_set_buoyancy(tlab_pencil_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters,
+                                 int inb_scal_array, const double *bbackground) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) ok(tlab_dns_set_buoyancy(nullptr, type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
+        for (Rank &R : d->rk)
+            ok(tlab_dns_set_buoyancy(dns_handle(d, R), type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
     }, TLAB_EINVAL);
 }
 

@@ -563,6 +563,178 @@ hipError_t launch_buffer_relax_plane(int nf, double *const *h, double *const *s,
     return CHECK_LAUNCH();
 }
 
+// TLab_Sources_Flow (src/physics/tlab_sources.f90:36-92): Rotation_Coriolis (rotation.f90:103-143) and then hq_i = hq_i + g_i b with b of
+// Gravity_Buoyancy (gravity.f90:232-342), in ONE pass: every input is read once, every affected tendency read and written once, an array no active
+// term touches is not accessed.  Unfused multiplies and adds (bf_mul / bf_add / bf_sub) in the reference's operation order: the numpy restatement
+// gives the same bits.
+//   COR: 0 off; 1 EQNS_COR_EXPLICIT, a term whose factor f is zero is left out (hq + 0 v = hq); 2 EQNS_COR_NORMALIZED (f2 alone; geo_u, geo_w from the host)
+//   BOD: 0 off; 1 HOMOGENEOUS b = c[0]; 2 LINEAR with 1..3 scalars b = ((c1 s1 + c2 s2) + c3 s3) - prof(j), prof = ref - c0; 3 LINEAR, general
+//        branch b = prof(j) + c_is s_is over the ns scalars kept by the host (prof = c0 - ref); 4 BILINEAR; 5 QUADRATIC (c[0] = c0, c[1] = c1)
+// prof: ny device values made by the setter.  All choices are template or kernel arguments: uniform over the launch.
+// V = 2: 16-byte accesses (nx even, every array 16-byte aligned); V = 1: scalar accesses.  The fields are whole and contiguous, so element p of the
+// launch is double(s) p V of every array; only the row index of prof(j) needs a division, a 32-bit one (the launch refuses boxes beyond 2^31 points).
+struct BodyForceArgs {
+    double *h[3];
+    const double *q[3], *s[BODY_FORCE_MAX_SCAL], *prof;
+    double f[3], g[3], c[BODY_FORCE_MAX_SCAL], geo_u, geo_w;
+    int ns;
+    unsigned hmask, qmask;      // bit i: hq_i is updated / q_i is read
+};
+// a * b, a + b, a - b that the compiler may not contract into a fused multiply-add (the __d*_rn functions of the HIP headers are plain operators
+// compiled under the headers' own contraction setting: after inlining they fuse)
+__device__ __forceinline__ double bf_mul(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double bf_add(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ double bf_sub(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+template <int V>
+struct BfVec { double v[V]; };
+template <int V>
+__device__ __forceinline__ BfVec<V> bf_load(const double *a, unsigned p) {
+    BfVec<V> r;
+    if constexpr (V == 2) { const double2 t = reinterpret_cast<const double2 *>(a)[p]; r.v[0] = t.x; r.v[1] = t.y; }
+    else r.v[0] = a[p];
+    return r;
+}
+template <int V>
+__device__ __forceinline__ void bf_store(double *a, unsigned p, const BfVec<V> &r) {
+    if constexpr (V == 2) reinterpret_cast<double2 *>(a)[p] = make_double2(r.v[0], r.v[1]);
+    else a[p] = r.v[0];
+}
+template <int V, int COR, int BOD>
+__global__ void __launch_bounds__(256) k_body_force(BodyForceArgs A, unsigned nxv, unsigned ny, unsigned npts) {
+    const unsigned stride = gridDim.x * blockDim.x;
+    for (unsigned p = blockIdx.x * blockDim.x + threadIdx.x; p < npts; p += stride) {
+        BfVec<V> q[3], b;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            if (COR != 0 && (A.qmask >> i & 1u)) q[i] = bf_load<V>(A.q[i], p);
+        if constexpr (BOD == 1) {
+            for (int v = 0; v < V; ++v) b.v[v] = A.c[0];
+        } else if constexpr (BOD != 0) {
+            const double pr = A.prof[(p / nxv) % ny];
+            if constexpr (BOD == 3) {
+                for (int v = 0; v < V; ++v) b.v[v] = pr;
+#pragma unroll
+                for (int is = 0; is < BODY_FORCE_MAX_SCAL; ++is)
+                    if (is < A.ns) {
+                        const BfVec<V> s = bf_load<V>(A.s[is], p);
+                        for (int v = 0; v < V; ++v) b.v[v] = bf_add(b.v[v], bf_mul(A.c[is], s.v[v]));
+                    }
+            } else {
+                const BfVec<V> s1 = bf_load<V>(A.s[0], p);
+                if constexpr (BOD == 2) {
+                    for (int v = 0; v < V; ++v) b.v[v] = bf_mul(A.c[0], s1.v[v]);
+                    if (A.ns > 1) {
+                        const BfVec<V> s2 = bf_load<V>(A.s[1], p);
+                        for (int v = 0; v < V; ++v) b.v[v] = bf_add(b.v[v], bf_mul(A.c[1], s2.v[v]));
+                    }
+                    if (A.ns > 2) {
+                        const BfVec<V> s3 = bf_load<V>(A.s[2], p);
+                        for (int v = 0; v < V; ++v) b.v[v] = bf_add(b.v[v], bf_mul(A.c[2], s3.v[v]));
+                    }
+                } else if constexpr (BOD == 4) {
+                    const BfVec<V> s2 = bf_load<V>(A.s[1], p);
+                    for (int v = 0; v < V; ++v)
+                        b.v[v] = bf_add(bf_add(bf_mul(A.c[0], s1.v[v]), bf_mul(A.c[1], s2.v[v])), bf_mul(bf_mul(A.c[2], s1.v[v]), s2.v[v]));
+                } else {
+                    for (int v = 0; v < V; ++v) b.v[v] = bf_mul(bf_mul(A.c[0], s1.v[v]), bf_sub(s1.v[v], A.c[1]));
+                }
+                for (int v = 0; v < V; ++v) b.v[v] = bf_sub(b.v[v], pr);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (!(A.hmask >> i & 1u)) continue;
+            BfVec<V> h = bf_load<V>(A.h[i], p);
+            if constexpr (COR == 1) {      // r_i = r_i + f_k u_j - f_j u_k, (i, j, k) cyclic
+                const int j = (i + 1) % 3, k = (i + 2) % 3;
+                if (A.f[k] != 0.0)
+                    for (int v = 0; v < V; ++v) h.v[v] = bf_add(h.v[v], bf_mul(A.f[k], q[j].v[v]));
+                if (A.f[j] != 0.0)
+                    for (int v = 0; v < V; ++v) h.v[v] = bf_sub(h.v[v], bf_mul(A.f[j], q[k].v[v]));
+            } else if constexpr (COR == 2) {
+                if (i == 0)
+                    for (int v = 0; v < V; ++v) h.v[v] = bf_add(h.v[v], bf_mul(A.f[1], bf_sub(A.geo_w, q[2].v[v])));
+                if (i == 2)
+                    for (int v = 0; v < V; ++v) h.v[v] = bf_add(h.v[v], bf_mul(A.f[1], bf_sub(q[0].v[v], A.geo_u)));
+            }
+            if (BOD != 0 && A.g[i] != 0.0)
+                for (int v = 0; v < V; ++v) h.v[v] = bf_add(h.v[v], bf_mul(A.g[i], b.v[v]));
+            bf_store<V>(A.h[i], p, h);
+        }
+    }
+}
+template <int V, int COR>
+static void body_force_launch_bod(int bod, const BodyForceArgs &A, unsigned nxv, unsigned ny, unsigned npts, hipStream_t st) {
+    const dim3 grid(pw_grid(npts)), block(256);
+    switch (bod) {
+    case 0: hipLaunchKernelGGL((k_body_force<V, COR, 0>), grid, block, 0, st, A, nxv, ny, npts); break;
+    case 1: hipLaunchKernelGGL((k_body_force<V, COR, 1>), grid, block, 0, st, A, nxv, ny, npts); break;
+    case 2: hipLaunchKernelGGL((k_body_force<V, COR, 2>), grid, block, 0, st, A, nxv, ny, npts); break;
+    case 3: hipLaunchKernelGGL((k_body_force<V, COR, 3>), grid, block, 0, st, A, nxv, ny, npts); break;
+    case 4: hipLaunchKernelGGL((k_body_force<V, COR, 4>), grid, block, 0, st, A, nxv, ny, npts); break;
+    default: hipLaunchKernelGGL((k_body_force<V, COR, 5>), grid, block, 0, st, A, nxv, ny, npts); break;
+    }
+}
+template <int V>
+static void body_force_launch(int cor, int bod, const BodyForceArgs &A, unsigned nxv, unsigned ny, unsigned npts, hipStream_t st) {
+    if (cor == 0) body_force_launch_bod<V, 0>(bod, A, nxv, ny, npts, st);
+    else if (cor == 1) body_force_launch_bod<V, 1>(bod, A, nxv, ny, npts, st);
+    else body_force_launch_bod<V, 2>(bod, A, nxv, ny, npts, st);
+}
+hipError_t launch_body_force(const BodyForce &F, double *const *hq, const double *const *q, const double *const *s, const double *prof, int nx, int ny,
+                             int nz, hipStream_t st) {
+    if (nx < 1 || ny < 1 || nz < 1 || (long long)nx * ny * nz > 0x7fffffffLL || F.cor < 0 || F.cor > 2 || F.bod < 0 || F.bod > 5 || F.ns < 0 ||
+        F.ns > BODY_FORCE_MAX_SCAL)
+        return hipErrorInvalidValue;
+    BodyForceArgs A{};
+    int cor = F.cor, bod = F.bod;
+    if (cor == 2 && F.f[1] == 0.0) cor = 0;
+    if (bod != 0 && F.g[0] == 0.0 && F.g[1] == 0.0 && F.g[2] == 0.0) bod = 0;
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        A.f[i] = F.f[i]; A.g[i] = bod ? F.g[i] : 0.0;
+        if (cor == 1) {
+            if (F.f[k] != 0.0) { A.hmask |= 1u << i; A.qmask |= 1u << j; }
+            if (F.f[j] != 0.0) { A.hmask |= 1u << i; A.qmask |= 1u << k; }
+        }
+        if (A.g[i] != 0.0) A.hmask |= 1u << i;
+    }
+    if (cor == 1 && A.qmask == 0) cor = 0;
+    if (cor == 2) { A.hmask |= 5u; A.qmask = 5u; }
+    if (A.hmask == 0) return hipSuccess;      // nothing acts: no launch
+    A.geo_u = F.geo_u; A.geo_w = F.geo_w; A.ns = F.ns; A.prof = prof;
+    const int nsread = bod == 2 || bod == 3 ? F.ns : bod == 4 ? 2 : bod == 5 ? 1 : 0;
+    if ((nsread > 0 && !s) || (bod >= 2 && !prof) || (bod == 2 && (F.ns < 1 || F.ns > 3))) return hipErrorInvalidValue;
+    bool vec = (nx & 1) == 0;
+    int nread = 0;
+    for (int i = 0; i < 3; ++i) {
+        A.h[i] = hq[i]; A.q[i] = q[i];
+        if (A.hmask >> i & 1u) { if (!hq[i]) return hipErrorInvalidValue; vec = vec && ((uintptr_t)hq[i] & 15) == 0; }
+        if (A.qmask >> i & 1u) { if (!q[i]) return hipErrorInvalidValue; vec = vec && ((uintptr_t)q[i] & 15) == 0; ++nread; }
+    }
+    for (int is = 0; is < BODY_FORCE_MAX_SCAL; ++is) {
+        A.c[is] = F.c[is];
+        A.s[is] = is < nsread ? s[F.sidx[is]] : nullptr;
+        if (is < nsread) { if (!A.s[is]) return hipErrorInvalidValue; vec = vec && ((uintptr_t)A.s[is] & 15) == 0; ++nread; }
+    }
+    const long long n = (long long)nx * ny * nz;
+    int nh = 0;
+    for (int i = 0; i < 3; ++i) nh += (int)(A.hmask >> i & 1u);
+    ProfScope ps("k_body_force", st, 8.0 * (double)n * (nread + 2 * nh));
+    if (vec) body_force_launch<2>(cor, bod, A, (unsigned)(nx / 2), (unsigned)ny, (unsigned)(n / 2), st);
+    else body_force_launch<1>(cor, bod, A, (unsigned)nx, (unsigned)ny, (unsigned)n, st);
+    return CHECK_LAUNCH();
+}
+
 // Weighted sums over the K rows next to each wall: ob[ix, k] = sum_{j < K} wb[j] a[ix, j, k], ot[ix, k] = sum_{j < K} wt[j] a[ix, ny-1-j, k], for one or
 // two fields at once (a2 / ob2 / ot2 may be NULL).  With wb, wt = the row of the Neumann operator that BOUNDARY_BCS_NEUMANN_Y applies to a finished
 // tendency (its wall value is a linear functional of the line whose weights decay like 0.38^j), this is that wall value without the y-derivative

@@ -60,6 +60,10 @@ struct tlab_dns {
     // the substep applies the scalar blocks (BOUNDARY_BUFFER_RELAX_SCAL, time.f90:628-630); the deferred tail switches this off for the replay of a
     // record that holds no tlab_deferred_relax_scal: RHS + DAXPY does not relax the scalars, whichever way it is replayed
     bool scal_zones_in_substep = true;
+    // [Rotation] and [BodyForce] (tlab_dns_set_coriolis / _set_buoyancy): TLab_Sources_Flow as the one launch of k_body_force; bprof: the ny values
+    // the buoyancy function subtracts (or starts from), made from bbackground when it is set
+    tlab::BodyForce force;
+    double *bprof = nullptr;
     unsigned long anel_version = 0;                // change counter of the operator state these mirror (follow_anelastic)
     bool anel_owner = false;                       // this driver switched the operator state on (tlab_dns_set_anelastic): it goes with the driver
     ~tlab_dns() {
@@ -75,6 +79,7 @@ struct tlab_dns {
         if (rib) (void)hipFree(rib);
         for (NeuW &n : neuw) if (n.w) (void)hipFree(n.w);
         if (wall_planes) (void)hipFree(wall_planes);
+        if (bprof) (void)hipFree(bprof);
         for (auto &g : buff)
             for (BufferBlock &b : g) free_block(b, false);
     }
@@ -155,6 +160,11 @@ ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d) { return &d->bounds; }
 bool tlab_internal_dns_has_flow_zones(tlab_dns_t d) { return d && (d->buff[0][0].size > 0 || d->buff[0][1].size > 0); }
 bool tlab_internal_dns_has_scal_zones(tlab_dns_t d) { return d && d->nscal > 0 && (d->buff[1][0].size > 0 || d->buff[1][1].size > 0); }
 bool tlab_internal_dns_scal_zones_in_substep(tlab_dns_t d, bool on) { const bool was = d->scal_zones_in_substep; d->scal_zones_in_substep = on; return was; }
+// the substeps of the three drivers apply the body forces (time.f90:610); the deferred tail switches this off for the replay of a record that holds no
+// tlab_deferred_sources_flow: RHS + DAXPY alone adds no force, whichever way it is replayed
+static bool g_forces_in_substep = true;
+bool tlab_internal_dns_forces_in_substep(bool on) { const bool was = g_forces_in_substep; g_forces_in_substep = on; return was; }
+bool tlab_internal_dns_forces_active(tlab_dns_t d) { return d && g_forces_in_substep && d->force.any(); }
 
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi) {
@@ -304,6 +314,11 @@ static void buffer_relax(tlab_dns_t d, int group, double *const *a, double *cons
     }
 }
 
+// TLab_Sources_Flow (tlab_sources.f90:36-92) on (q, s, hq): Rotation_Coriolis, then hq_i += g_i b, one launch
+static void body_force(tlab_dns_t d, double *const *q, double *const *s, double *const *hq, hipStream_t st) {
+    hk(launch_body_force(d->force, hq, q, s, d->bprof, d->nx, d->ny, d->nz, st), "body force");
+}
+
 static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs,
                      double *const *txc, bool tail_update, double kco, int scale_tendencies) {
     const int nx = d->nx, ny = d->ny, nz = d->nz;
@@ -365,6 +380,8 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // ride on the LAST Burgers launch that adds to hs, if that launch is the x one (the wave-per-line kernel has the registers for it; the
     // y/z tile kernels do not, measured).  The directions then run z, y, x instead of x, y, z: the terms are summed in another order, rounding only.
     static const bool finish_off = [] { const char *e = getenv("TLAB_SCALAR_FINISH"); return e && atoi(e) == 0; }();
+    // TLab_Sources_Flow runs before the RHS in the substep (time.f90:610-612), never in the RHS on its own
+    const bool forces = tail_update && tlab_internal_dns_forces_active(d);
     const bool zone_flow = buffer_any(d, 0), zone_scal = tail_update && d->nscal > 0 && d->scal_zones_in_substep && buffer_any(d, 1);
     bool finish_scal = !finish_off && batched && !literal && tail_update && d->nscal > 0 && tlab_internal_burgers_can_finish(1, gx, nx, ny, nz);
     // Neumann scalars can ride too where the fused Neumann tail below applies: the epilogue finishes their interior with zero wall tendencies, and the
@@ -461,6 +478,9 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             // third launch finishes u and differentiates it): one zone launch for the three.  The terms are summed in another order, rounding only.
             if (zone_flow && &L == &plan[1]) buffer_relax(d, 0, q, hq, st);
             if (zone_epi && &L == &plan[1]) buffer_relax(d, 1, s, hs, st);       // (the scalars are finished by the third launch too)
+            // the body forces share the slot: every tendency holds a valid partial sum, q and s are those from before the update, and the forcing
+            // of the pressure and the wall planes of hq2 are formed later, so the force is projected.  Summed in another order: rounding only.
+            if (forces && &L == &plan[1]) body_force(d, q, s, hq, st);
         }
     } else if (batched) {
         const int order_xyz[3] = {1, 2, 3}, order_zyx[3] = {3, 2, 1};
@@ -487,6 +507,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             }
             if (zone_flow && k == 0) buffer_relax(d, 0, q, hq, st);      // after the first launch (it may overwrite), before the last (it may differentiate)
             if (zone_epi && k == 0) buffer_relax(d, 1, s, hs, st);
+            if (forces && k == 0) body_force(d, q, s, hq, st);
         }
     }
     for (size_t e = 0; e < eqs.size() && !batched; ++e) {
@@ -506,6 +527,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         }
     }
     if (zone_flow && !batched) buffer_relax(d, 0, q, hq, st);      // BOUNDARY_BUFFER_RELAX_FLOW in the reference's place (:170-172)
+    if (forces && !batched) body_force(d, q, s, hq, st);           // (the tendencies were zeroed or accumulated above; the forcing follows)
     // the tail of the scalars under a buffer zone, once the wall planes of hs hold their BC values: BOUNDARY_BUFFER_RELAX_SCAL, s += dte hs, bounds, hs *= kco
     auto zone_scal_tail = [&] {
         buffer_relax(d, 1, s, hs, st);
@@ -1288,6 +1310,128 @@ int tlab_dns_buffer_relax_scal(tlab_dns_t d, double *const *s, double *const *hs
             if (!s[i] || !hs[i]) throw Fail(TLAB_EINVAL, "tlab_dns_buffer_relax_scal: null array");
         buffer_relax(d, 1, s, hs, tlab_current_stream());
     });
+}
+
+// ---- [Rotation] and [BodyForce]: TLab_Sources_Flow (src/physics/tlab_sources.f90:36-92) ----
+static bool all_finite(const double *v, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int tlab_dns_set_coriolis(tlab_dns_t d, int type, const double *vector, const double *parameters) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (type != TLAB_COR_NONE && type != TLAB_COR_EXPLICIT && type != TLAB_COR_NORMALIZED) throw Fail(TLAB_EINVAL, "tlab_dns_set_coriolis: unknown type");
+        tlab::BodyForce F;
+        if (type != TLAB_COR_NONE) {
+            if (!vector || !all_finite(vector, 3)) throw Fail(TLAB_EINVAL, "tlab_dns_set_coriolis: vector is NULL or holds NaN / infinite values");
+            for (int i = 0; i < 3; ++i) F.f[i] = vector[i];
+            F.cor = 1;
+        }
+        if (type == TLAB_COR_NORMALIZED) {
+            if (!parameters || !all_finite(parameters, 2)) throw Fail(TLAB_EINVAL, "tlab_dns_set_coriolis: parameters is NULL or holds NaN / infinite values");
+            if (vector[0] != 0.0 || vector[2] != 0.0)
+                throw Fail(TLAB_EINVAL, "[Rotation] Type = normalized: only the vector (0, f2, 0) is allowed (the reference stops on an active y equation)");
+            F.cor = 2;
+            F.geo_u = std::cos(parameters[0]) * parameters[1];       // rotation.f90:127-128, on the host
+            F.geo_w = -std::sin(parameters[0]) * parameters[1];
+        }
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_coriolis: null handle");
+        d->force.cor = F.cor; d->force.geo_u = F.geo_u; d->force.geo_w = F.geo_w;
+        for (int i = 0; i < 3; ++i) d->force.f[i] = F.f[i];
+    }, TLAB_EINVAL);
+}
+
+int tlab_dns_set_buoyancy(tlab_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters, int inb_scal_array,
+                          const double *bbackground) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (type == TLAB_BOD_EXPLICIT)
+            throw Fail(TLAB_EUNSUPPORTED, "[BodyForce] Type = explicit needs Thermo_Anelastic_BUOYANCY, which is not built on the device");
+        if (type == TLAB_BOD_NORMALIZEDMEAN || type == TLAB_BOD_SUBTRACTMEAN)
+            throw Fail(TLAB_EUNSUPPORTED, "[BodyForce] Type = normalizedmean / subtractmean need the plane means FI_DIAGNOSTIC refreshes every substep: not built on the device");
+        if (type != TLAB_BOD_NONE && (type < TLAB_BOD_HOMOGENEOUS || type > TLAB_BOD_QUADRATIC)) throw Fail(TLAB_EINVAL, "tlab_dns_set_buoyancy: unknown type");
+        tlab::BodyForce F;
+        std::vector<double> prof;
+        if (type != TLAB_BOD_NONE) {
+            if (!vector || !all_finite(vector, 3)) throw Fail(TLAB_EINVAL, "tlab_dns_set_buoyancy: vector is NULL or holds NaN / infinite values");
+            if (nparameters < 0 || nscalars < 0 || inb_scal_array < 0 || (nparameters > 0 && !parameters) || !all_finite(parameters, nparameters))
+                throw Fail(TLAB_EINVAL, "tlab_dns_set_buoyancy: negative counts, parameters NULL, or NaN / infinite parameters");
+            if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_buoyancy: null handle");
+            auto par = [&](int i) { return i < nparameters ? parameters[i] : 0.0; };      // (a key the ini file leaves out reads as zero)
+            for (int i = 0; i < 3; ++i) F.g[i] = vector[i];
+            const int ny = d->ny;
+            std::vector<double> ref((size_t)ny, 0.0);
+            if (bbackground) {
+                if (!all_finite(bbackground, ny)) throw Fail(TLAB_EINVAL, "tlab_dns_set_buoyancy: NaN / infinite values in bbackground");
+                ref.assign(bbackground, bbackground + ny);
+            }
+            prof.resize((size_t)ny);
+            if (type != TLAB_BOD_HOMOGENEOUS && d->nscal == 0) throw Fail(TLAB_EINVAL, "[BodyForce] Type = linear / bilinear / quadratic on a driver without scalars");
+            if (type == TLAB_BOD_HOMOGENEOUS) {
+                F.bod = 1; F.c[0] = par(0);
+            } else if (type == TLAB_BOD_LINEAR) {
+                if (nscalars > d->nscal)
+                    throw Fail(TLAB_EUNSUPPORTED, "[BodyForce] linear: the buoyancy reads scalar arrays beyond the prognostic scalars (diagnostic arrays are not held on the device)");
+                const double c0 = par(inb_scal_array);
+                if (nscalars >= 1 && nscalars <= 3) {      // gravity.f90:255-277
+                    F.bod = 2; F.ns = nscalars;
+                    for (int is = 0; is < nscalars; ++is) F.c[is] = par(is);
+                    for (int j = 0; j < ny; ++j) prof[j] = ref[j] - c0;
+                } else {                                    // :279-291
+                    F.bod = 3;
+                    for (int is = 0; is < nscalars; ++is) {
+                        if (!(std::fabs(par(is)) > 1.0e-20)) continue;      // small_wp
+                        if (F.ns == tlab::BODY_FORCE_MAX_SCAL) throw Fail(TLAB_EUNSUPPORTED, "[BodyForce] linear: more than 6 scalars with a non-zero factor");
+                        F.c[F.ns] = par(is); F.sidx[F.ns] = is; ++F.ns;
+                    }
+                    for (int j = 0; j < ny; ++j) prof[j] = c0 - ref[j];
+                }
+            } else if (type == TLAB_BOD_BILINEAR) {
+                if (d->nscal < 2) throw Fail(TLAB_EINVAL, "[BodyForce] Type = bilinear needs two scalars");
+                F.bod = 4; F.ns = 2;
+                for (int i = 0; i < 3; ++i) F.c[i] = par(i);
+                prof = ref;
+            } else {
+                F.bod = 5; F.ns = 1;
+                const double h = par(1) / 2.0;
+                F.c[0] = -par(0) / (h * h);                  // :306
+                F.c[1] = par(1);
+                if (!std::isfinite(F.c[0])) throw Fail(TLAB_EINVAL, "[BodyForce] Type = quadratic: parameters(2) = 0");
+                prof = ref;
+            }
+        }
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_buoyancy: null handle");
+        if (F.bod >= 2) {
+            const size_t bytes = (size_t)d->ny * sizeof(double);
+            if (!d->bprof) hk(hipMalloc((void **)&d->bprof, bytes), "hipMalloc");
+            hk(hipStreamSynchronize(tlab_current_stream()), "sync");      // (a kernel that reads the old profile may still be in flight)
+            hk(hipMemcpy(d->bprof, prof.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        d->force.bod = F.bod; d->force.ns = F.ns;
+        for (int i = 0; i < 3; ++i) d->force.g[i] = F.g[i];
+        for (int i = 0; i < tlab::BODY_FORCE_MAX_SCAL; ++i) { d->force.c[i] = F.c[i]; d->force.sidx[i] = F.sidx[i]; }
+    }, TLAB_EINVAL);
+}
+
+int tlab_dns_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq) {
+    return guarded([&] {
+        if (!d || !q || !hq || (d->nscal > 0 && !s)) throw Fail(TLAB_EINVAL, "tlab_dns_sources_flow: bad arguments");
+        body_force(d, q, s, hq, tlab_current_stream());
+    });
+}
+
+long long tlab_dns_info(tlab_dns_t d, int what) {
+    if (!d) return -1;
+    switch (what) {
+    case 0: return d->nx;
+    case 1: return d->ny;
+    case 2: return d->nz;
+    case 3: return d->nscal;
+    case 4: return (long long)d->nx * d->ny * d->nz;
+    default: return -1;
+    }
 }
 
 // ---- the pointwise pieces on their own, for drivers that interleave communication (z-slab decomposition) ----

@@ -496,6 +496,11 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     // extra velocity reads and the smaller launches cost what the two saved passes return: 28.17 against 28.04 ms for 8 loopback ranks at 512^3.)
     int w = halo_start(d, 3 + ns, [&](Rank &R, int i) { return Slot{i < 3 ? R.q[i] : R.s[i - 3], i}; });
     for (Rank &R : d->rk) badd_all(d, R, 1, fresh);
+    // TLab_Sources_Flow (time.f90:610; tlab_slab_dns_set_coriolis / _set_buoyancy): y is never split, so the launch of a rank acts on its box with the
+    // global profile.  Every tendency holds its first term now, and q, s are untouched until the second z pass finishes the scalars.
+    if (tail)
+        for (Rank &R : d->rk)
+            if (R.dns && tlab_internal_dns_forces_active(R.dns)) ok(tlab_dns_sources_flow(R.dns, R.q.data(), R.s.data(), R.hq.data()), "tlab_dns_sources_flow");
     twait(d, w);
     for (Rank &R : d->rk) zburgers_all(d, R, 1);
     w = msg_start(d, 2 * (3 + ns));
@@ -910,6 +915,24 @@ int tlab_slab_dns_set_buffer_zone(tlab_slab_dns_t d, int l, int end, int group, 
     return catch_fail([&] {
         if (!d || l < 0 || l >= (int)d->rk.size()) throw Fail(TLAB_EINVAL, "tlab_slab_dns_set_buffer_zone: bad handle or local rank");
         ok(tlab_dns_set_buffer_zone(dns_handle(d, d->rk[l]), end, group, size, nfields, tau, ref), "tlab_dns_set_buffer_zone");
+    }, TLAB_EINVAL);
+}
+
+int tlab_slab_dns_set_coriolis(tlab_slab_dns_t d, int type, const double *vector, const double *parameters) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) ok(tlab_dns_set_coriolis(nullptr, type, vector, parameters), "tlab_dns_set_coriolis");      // (the argument checks come first, as there)
+        for (Rank &R : d->rk) ok(tlab_dns_set_coriolis(dns_handle(d, R), type, vector, parameters), "tlab_dns_set_coriolis");
+    }, TLAB_EINVAL);
+}
+
+int tlab_slab_dns_set_buoyancy(tlab_slab_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters,
+                               int inb_scal_array, const double *bbackground) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) ok(tlab_dns_set_buoyancy(nullptr, type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
+        for (Rank &R : d->rk)
+            ok(tlab_dns_set_buoyancy(dns_handle(d, R), type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
     }, TLAB_EINVAL);
 }
 

@@ -102,6 +102,46 @@ def zone_tables(y, nx, ny, nz, nscal, points_jmin, points_jmax, params_u, params
             yield end, group, size, nf, tau, g
 
 
+CORIOLIS_TYPES = {"none": 0, "explicit": 4, "normalized": 12}
+BUOYANCY_TYPES = {"none": 0, "explicit": 4, "homogeneous": 5, "linear": 6, "bilinear": 7, "quadratic": 8, "normalizedmean": 9, "subtractmean": 10}
+
+
+def body_force_args(nscal, coriolis, buoyancy):
+    """The arguments of tlab_*_set_coriolis and tlab_*_set_buoyancy (after the handle) from the small dicts or tuples of set_body_forces."""
+    dp = ctypes.POINTER(ctypes.c_double)
+
+    def arr(v, n=None):
+        a = np.zeros(0 if v is None else len(v)) if n is None else np.zeros(n)
+        if v is not None:
+            v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+            a[:min(len(a), len(v))] = v[:len(a)]
+        return a
+
+    def code(v, table, what):
+        if isinstance(v, str):
+            if v.strip().lower() not in table:
+                raise TlabError("%s: one of %s" % (what, ", ".join(table)))
+            return table[v.strip().lower()]
+        return int(v)
+    if coriolis is None:
+        cor = (0, None, None)
+    else:
+        c = dict(zip(("type", "vector", "parameters"), coriolis)) if isinstance(coriolis, (tuple, list)) else dict(coriolis)
+        vec, par = arr(c.get("vector", (0.0, 0.0, 0.0)), 3), arr(c.get("parameters", (0.0, 1.0)), 2)
+        cor = (code(c.get("type", "explicit"), CORIOLIS_TYPES, "Rotation.Type"), vec, par)
+    if buoyancy is None:
+        bod = (0, None, 0, None, 0, nscal, None)
+    else:
+        b = dict(zip(("type", "vector", "parameters", "bbackground"), buoyancy)) if isinstance(buoyancy, (tuple, list)) else dict(buoyancy)
+        par = arr(b.get("parameters", ()))
+        bb = None if b.get("bbackground") is None else np.ascontiguousarray(b["bbackground"], dtype=np.float64)
+        bod = (code(b.get("type", "linear"), BUOYANCY_TYPES, "BodyForce.Type"), arr(b.get("vector", (0.0, 0.0, 0.0)), 3), int(b.get("scalars", nscal)), par,
+               len(par), int(b.get("inb_scal_array", nscal)), bb)
+    p = lambda a: None if a is None or len(a) == 0 else a.ctypes.data_as(dp)      # noqa: E731
+    keep = (cor, bod)                                                              # (the arrays live as long as the pointers)
+    return (cor[0], p(cor[1]), p(cor[2])), (bod[0], p(bod[1]), bod[2], p(bod[3]), bod[4], bod[5], p(bod[6])), keep
+
+
 def _extremes(mn, mx, lmin, lmax, locations):
     """(DilMin, DilMax[, (i, j, k) of the minimum, (i, j, k) of the maximum]) of the dilatation_extremes methods"""
     if not locations:
@@ -274,6 +314,24 @@ class Dns:
         _use_torch_stream()
         _, s, _, hs, _ = self._arrays()
         check(load().tlab_dns_buffer_relax_scal(self._h, s, hs), "tlab_dns_buffer_relax_scal")
+
+    def set_body_forces(self, coriolis=None, buoyancy=None):
+        """[Rotation] and [BodyForce] (TLab_Sources_Flow, applied once per substep before the pressure forcing).  None switches the term off.
+        coriolis: {"type": "explicit" | "normalized", "vector": f / Rossby (3), "parameters": (angle, geostrophic speed)} or the tuple (type, vector,
+        parameters).  buoyancy: {"type": "homogeneous" | "linear" | "bilinear" | "quadratic", "vector": g / Froude (3), "parameters": (...),
+        "scalars": buoyancy%scalar(1) (default nscal), "inb_scal_array": (default nscal; linear: c0 = parameters[inb_scal_array]),
+        "bbackground": ny values or None} or the tuple (type, vector, parameters[, bbackground]).  "explicit", "normalizedmean" and "subtractmean"
+        buoyancy are refused by the library (TLAB_EUNSUPPORTED)."""
+        cor, bod, keep = body_force_args(self.nscal, coriolis, buoyancy)
+        check(load().tlab_dns_set_coriolis(self._h, *cor), "tlab_dns_set_coriolis")
+        check(load().tlab_dns_set_buoyancy(self._h, *bod), "tlab_dns_set_buoyancy")
+        del keep
+
+    def sources_flow(self):
+        """TLab_Sources_Flow on (q, s, hq) as an operator of its own: hq += Coriolis + buoyancy."""
+        _use_torch_stream()
+        q, s, hq, _, _ = self._arrays()
+        check(load().tlab_dns_sources_flow(self._h, q, s, hq), "tlab_dns_sources_flow")
 
     def set_fusion(self, on):
         """on (default): pointwise sums folded into the operator kernels; off: the reference's literal sequence."""

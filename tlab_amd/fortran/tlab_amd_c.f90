@@ -316,6 +316,41 @@ module TLab_AMD_C
             import :: c_int, c_long_long
             integer(c_long_long), intent(out) :: counts(2)
         end function
+        ! [Rotation] and [BodyForce] of a patched host (tlab_amd_sources.f90): vector(3), parameters and bbackground(jmax) in HOST memory; itype = the
+        ! reference's EQNS_COR_* / EQNS_BOD_* codes; nscalars = buoyancy%scalar(1); bbackground may be c_null_ptr (zeros)
+        integer(c_int) function tlab_dns_set_coriolis(dns, itype, vector, parameters) bind(C, name='tlab_dns_set_coriolis')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: dns
+            integer(c_int), value :: itype
+            real(c_double), intent(in) :: vector(3), parameters(2)
+        end function
+        integer(c_int) function tlab_dns_set_buoyancy(dns, itype, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground) &
+            bind(C, name='tlab_dns_set_buoyancy')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: dns, bbackground
+            integer(c_int), value :: itype, nscalars, nparameters, inb_scal_array
+            real(c_double), intent(in) :: vector(3), parameters(*)
+        end function
+        integer(c_long_long) function tlab_dns_info(dns, what) bind(C, name='tlab_dns_info')      ! 0 nx, 1 ny, 2 nz, 3 nscal, 4 points of a field
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: dns
+            integer(c_int), value :: what
+        end function
+        ! TLab_Sources_Flow on (q, s, hq): on its own, and as the marker of the deferred tail (csrc/deferred.cpp)
+        integer(c_int) function tlab_dns_sources_flow(dns, q, s, hq) bind(C, name='tlab_dns_sources_flow')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+            type(c_ptr), intent(in) :: q(*), s(*), hq(*)      ! host arrays of device pointers
+        end function
+        integer(c_int) function tlab_deferred_sources_flow(dns, q, s, hq) bind(C, name='tlab_deferred_sources_flow')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+            type(c_ptr), intent(in) :: q(*), s(*), hq(*)
+        end function
+        integer(c_int) function tlab_deferred_sources_stats(counts) bind(C, name='tlab_deferred_sources_stats')
+            import :: c_int, c_long_long
+            integer(c_long_long), intent(out) :: counts(2)
+        end function
         integer(c_int) function tlab_dns_buffer_relax_flow(dns, q, hq) bind(C, name='tlab_dns_buffer_relax_flow')
             import :: c_int, c_ptr
             type(c_ptr), value :: dns

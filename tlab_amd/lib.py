@@ -86,6 +86,16 @@ SIGNATURES = {
     "tlab_deferred_relax_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "tlab_slab_dns_set_buffer_zone": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, _dp, _dp]),
     "tlab_pencil_dns_set_buffer_zone": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, _dp, _dp]),
+    "tlab_dns_set_coriolis": (c_int, [c_vp, c_int, _dp, _dp]),
+    "tlab_dns_set_buoyancy": (c_int, [c_vp, c_int, _dp, c_int, _dp, c_int, c_int, _dp]),
+    "tlab_dns_sources_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    "tlab_dns_info": (ctypes.c_longlong, [c_vp, c_int]),
+    "tlab_deferred_sources_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    "tlab_deferred_sources_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
+    "tlab_slab_dns_set_coriolis": (c_int, [c_vp, c_int, _dp, _dp]),
+    "tlab_slab_dns_set_buoyancy": (c_int, [c_vp, c_int, _dp, c_int, _dp, c_int, c_int, _dp]),
+    "tlab_pencil_dns_set_coriolis": (c_int, [c_vp, c_int, _dp, _dp]),
+    "tlab_pencil_dns_set_buoyancy": (c_int, [c_vp, c_int, _dp, c_int, _dp, c_int, c_int, _dp]),
     "tlab_dns_begin_step": (c_int, [c_vp]),
     "tlab_deferred_enable": (c_int, [c_int]),
     "tlab_deferred_rhs": (c_int, [c_vp, c_dbl, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),

@@ -228,6 +228,14 @@ class NativeSlabDns:
         n, act, l, h = _bounds_arrays(lo, hi, active)
         check(load().tlab_slab_dns_set_scalar_bounds(self._h, n, act, l, h), "tlab_slab_dns_set_scalar_bounds")
 
+    def set_body_forces(self, coriolis=None, buoyancy=None):
+        """[Rotation] and [BodyForce], as Dns.set_body_forces, on every local rank; bbackground is the global profile (y is never split)."""
+        from .dns import body_force_args
+        cor, bod, keep = body_force_args(self.nscal, coriolis, buoyancy)
+        check(load().tlab_slab_dns_set_coriolis(self._h, *cor), "tlab_slab_dns_set_coriolis")
+        check(load().tlab_slab_dns_set_buoyancy(self._h, *bod), "tlab_slab_dns_set_buoyancy")
+        del keep
+
     def set_buffer_zones(self, points_jmin=0, points_jmax=0, params_u=(1.0, 2.0), params_s=(1.0, 2.0), hard_u=None, hard_s=None, ref=None):
         """[BufferZone] Type = relaxation at Jmin / Jmax, as Dns.set_buffer_zones.  The plane means of LoadBuffer = no are means over the WHOLE plane
         (COV2V2D all-reduces over the ranks): they are formed here when every rank is local (loopback), in the reference's serial order over the
