@@ -30,22 +30,20 @@
 
 #include "driver_common.hpp"
 
-using tlab::ScalarBounds;
+using namespace tlab;
 
 namespace {
 struct Range { double *p; long long n; };
 // the driver behind a recorded RHS -- tlab_dns (one domain), tlab_slab_dns or tlab_pencil_dns, the same tail behind each of them: its three entry
-// points on its handle (and, one domain, on the arrays handed to the RHS) and its own scalar bounds
+// points on its handle (and, one domain, on the arrays handed to the RHS), the substep with the tail it is handed
 struct Driver {
     std::function<int()> begin_step;
     std::function<int(double dte)> rhs;
-    std::function<int(double dte, double kco, int scale)> substep;
-    ScalarBounds *bounds = nullptr;
-    // one domain only (empty otherwise): the driver's handle, BOUNDARY_BUFFER_RELAX_SCAL on the recorded arrays, and the switch that makes the
-    // driver's substep apply its scalar buffer zones (returns the old setting)
+    std::function<int(double dte, const SubstepTail &tail)> substep;
+    bool has_bounds = false;      // it holds scalar bounds of its own (they cannot change under a record: tlab_*_set_scalar_bounds flushes first)
+    // one domain only (empty otherwise): the driver's handle and BOUNDARY_BUFFER_RELAX_SCAL on the recorded arrays
     tlab_dns_t dns = nullptr;
     std::function<int()> relax_scal;
-    std::function<bool(bool)> scal_zones;
 };
 struct Pending {
     bool rhs = false;
@@ -56,8 +54,7 @@ struct Pending {
     std::vector<double *> x, y;                   // per field: tendency, state
     std::vector<char> upd, scl;
     int nupd = 0, nscl = 0;
-    std::vector<char> clp;                        // per scalar: clipped after its DAXPY (DNS_BOUNDS_LIMIT), with clo / chi
-    std::vector<double> clo, chi;
+    ScalarBounds clips;                           // per scalar: clipped after its DAXPY (DNS_BOUNDS_LIMIT), and how many are
     int nclp = 0;
     bool relax = false;                           // tlab_deferred_relax_scal recorded straight after the RHS (time.f90:628-630)
     bool sources = false;                         // tlab_deferred_sources_flow came straight before the RHS, same driver and arrays (time.f90:610-612)
@@ -124,21 +121,15 @@ bool zeros_are_the_tendencies(const Pending &p) {
     return true;
 }
 
-// the substep the record describes: its bounds are the recorded clips and nothing else (a driver's own bounds do not belong to RHS + DAXPY), put in
-// place for this one call and taken back
-int run_substep(Pending &p, double kco, int scale) {
-    ScalarBounds b;
-    if (p.nclp) { b.on = p.clp; b.lo = p.clo; b.hi = p.chi; }
-    p.drv.bounds->swap(b);
-    // ... and the scalar buffer zones of the driver act in it only when the record holds the relaxation: RHS + DAXPY alone does not relax the scalars
-    const bool was = p.drv.scal_zones ? p.drv.scal_zones(p.relax) : true;
-    // ... and the body forces only when it holds the sources marker
-    const bool forces_were = tlab_internal_dns_forces_in_substep(p.sources);
-    const int rc = p.drv.substep(p.dte, kco, scale);
-    (void)tlab_internal_dns_forces_in_substep(forces_were);
-    if (p.drv.scal_zones) (void)p.drv.scal_zones(was);
-    p.drv.bounds->swap(b);
-    return rc;
+// the substep the record describes: its bounds are the recorded clips and nothing else (a driver's own bounds do not belong to RHS + DAXPY), the
+// scalar buffer zones of the driver act in it only when the record holds the relaxation, the body forces only when it holds the sources marker
+int run_substep(const Pending &p, double kco, int scale) {
+    SubstepTail tail{kco, scale, p.nclp ? &p.clips : nullptr, p.relax, p.sources};
+    if (!p.drv.dns) {                // a decomposed driver: neither marker can be recorded for it
+        tail.scal_zones = true;      // the scalar blocks act in every replay
+        tail.forces = false;         // the body forces in none
+    }
+    return p.drv.substep(p.dte, tail);
 }
 
 // a new record: driver, step and the fields (tendency, state) the BLAS calls that follow are matched against; the zero fills recorded so far stay
@@ -153,7 +144,7 @@ void record(Driver drv, double dte, int ns, long long n, double *const *q, doubl
     for (int i = 0; i < ns; ++i) { p.x.push_back(hs[i]); p.y.push_back(s[i]); }
     p.upd.assign(p.nf, 0); p.scl.assign(p.nf, 0);
     p.nupd = p.nscl = 0;
-    p.clp.assign(ns, 0); p.clo.assign(ns, 0.0); p.chi.assign(ns, 0.0);
+    p.clips.on.assign(ns, 0); p.clips.lo.assign(ns, 0.0); p.clips.hi.assign(ns, 0.0);
     p.nclp = 0;
     p.relax = false;
     p.sources = false;
@@ -190,7 +181,7 @@ int flush_impl(bool whole_ok = true) {
         }
     }
     if (rc != TLAB_OK) return rc;
-    if (whole_ok && p.nupd == p.nf && (p.nscl == 0 || p.nscl == p.nf)) {      // the whole substep, as the patched host would have called it
+    if (fused) {      // the whole substep, as the patched host would have called it
         ++g_stat[0];
         if (p.nclp) ++g_clip_stat[0];
         if (p.relax) ++g_relax_stat[0];
@@ -210,7 +201,7 @@ int flush_impl(bool whole_ok = true) {
     for (int f = 0; f < p.nf && rc == TLAB_OK; ++f)
         if (p.upd[f]) rc = tlab_pw_rk_update(p.y[f], p.x[f], p.dte, 1.0, 0, p.n);
     for (int is = 0; is + 3 < p.nf && rc == TLAB_OK; ++is)          // (a clip was recorded after the DAXPY of its field only)
-        if (p.clp[is]) { ++g_clip_stat[1]; rc = tlab_pw_clip(p.y[3 + is], p.clo[is], p.chi[is], p.n); }
+        if (p.clips.on[is]) { ++g_clip_stat[1]; rc = tlab_pw_clip(p.y[3 + is], p.clips.lo[is], p.clips.hi[is], p.n); }
     return rc;
 }
 }      // namespace
@@ -343,14 +334,12 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
     drv.rhs = [=](double dte_) {
         return tlab_rhs_global_incompressible_1(d, dte_, Q.data(), ns ? S.data() : nullptr, HQ.data(), ns ? HS.data() : nullptr, T.data());
     };
-    drv.substep = [=](double dte_, double kco, int scale) {
-        return tlab_time_substep_incompressible_explicit(d, dte_, kco, scale, Q.data(), ns ? S.data() : nullptr, HQ.data(), ns ? HS.data() : nullptr,
-                                                         T.data());
+    drv.substep = [=](double dte_, const SubstepTail &tail) {
+        return catch_fail([&] { tlab_internal_dns_substep(d, dte_, Q.data(), ns ? S.data() : nullptr, HQ.data(), ns ? HS.data() : nullptr, T.data(), tail); }, TLAB_EINVAL);
     };
-    drv.bounds = tlab_internal_dns_bounds(d);
+    drv.has_bounds = tlab_internal_dns_has_bounds(d);
     drv.dns = d;
     drv.relax_scal = [=] { return tlab_dns_buffer_relax_scal(d, ns ? S.data() : nullptr, ns ? HS.data() : nullptr); };
-    drv.scal_zones = [d](bool on) { return tlab_internal_dns_scal_zones_in_substep(d, on); };
     g_last = drv;
     if (!g_on) return drv.rhs(dte);
     record(std::move(drv), dte, ns, tlab_internal_dns_points(d), q, s, hq, hs);
@@ -370,7 +359,7 @@ static int deferred_decomposed(Driver drv, bool bound, const tlab_bound_fields &
         const int rc = flush_impl();
         if (rc != TLAB_OK) return rc;
     }
-    drv.bounds = b.bounds;
+    drv.has_bounds = b.has_bounds;
     record(std::move(drv), dte, b.nscal, b.n, b.q, b.s, b.hq, b.hs);
     return TLAB_OK;
 }
@@ -379,14 +368,16 @@ int tlab_deferred_slab_rhs(tlab_slab_dns_t d, double dte) {
     tlab_bound_fields b{};
     const bool bound = tlab_internal_slab_bound(d, &b);
     return deferred_decomposed({[d] { return tlab_slab_dns_begin_step(d); }, [d](double dte_) { return tlab_slab_dns_rhs(d, dte_); },
-                                [d](double dte_, double kco, int scale) { return tlab_slab_dns_substep(d, dte_, kco, scale); }}, bound, b, dte);
+                                [d](double dte_, const SubstepTail &tail) { return guarded([&] { tlab_internal_slab_substep(d, dte_, tail); }); }},
+                               bound, b, dte);
 }
 int tlab_deferred_pencil_rhs(tlab_pencil_dns_t d, double dte) {
     if (!d) { tlab_set_error("tlab_deferred_pencil_rhs: null handle"); return TLAB_EINVAL; }
     tlab_bound_fields b{};
     const bool bound = tlab_internal_pencil_bound(d, &b);
     return deferred_decomposed({[d] { return tlab_pencil_dns_begin_step(d); }, [d](double dte_) { return tlab_pencil_dns_rhs(d, dte_); },
-                                [d](double dte_, double kco, int scale) { return tlab_pencil_dns_substep(d, dte_, kco, scale); }}, bound, b, dte);
+                                [d](double dte_, const SubstepTail &tail) { return guarded([&] { tlab_internal_pencil_substep(d, dte_, tail); }); }},
+                               bound, b, dte);
 }
 
 int tlab_deferred_axpy(long long n, double a, const double *x, double *y) {
@@ -437,11 +428,11 @@ int tlab_deferred_clip(long long n, double lo, double hi, double *x) {
         tlab_set_error("tlab_deferred_clip: null array, n < 0, NaN bounds or lo > hi");
         return TLAB_EINVAL;
     }
-    if (g_on && g_p.rhs && g_p.nscl == 0 && n == g_p.n && !g_p.drv.bounds->any()) {
+    if (g_on && g_p.rhs && g_p.nscl == 0 && n == g_p.n && !g_p.drv.has_bounds) {
         for (int is = 0; is + 3 < g_p.nf; ++is)
             if (g_p.y[3 + is] == x) {
-                if (!g_p.upd[3 + is] || g_p.clp[is]) break;       // before its DAXPY, or a second clip: literal
-                g_p.clp[is] = 1; g_p.clo[is] = lo; g_p.chi[is] = hi; ++g_p.nclp;
+                if (!g_p.upd[3 + is] || g_p.clips.on[is]) break;       // before its DAXPY, or a second clip: literal
+                g_p.clips.on[is] = 1; g_p.clips.lo[is] = lo; g_p.clips.hi[is] = hi; ++g_p.nclp;
                 return TLAB_OK;
             }
     }

@@ -63,12 +63,11 @@ struct ScalarBounds {
     std::vector<double> lo, hi;
     bool any() const { return !on.empty(); }
     bool active(int is) const { return !on.empty() && on[is]; }
-    void swap(ScalarBounds &o) { on.swap(o.on); lo.swap(o.lo); hi.swap(o.hi); }
     // false (nothing changed, the reason in tlab_last_error()): see tlab_internal_check_bounds
     bool set(const char *who, int nscal, int n, const int *active_, const double *lo_, const double *hi_) {
         ScalarBounds b;
         if (!tlab_internal_check_bounds(who, nscal, n, active_, lo_, hi_, b.on, b.lo, b.hi)) return false;
-        swap(b);
+        *this = std::move(b);
         return true;
     }
 };
@@ -79,6 +78,18 @@ int set_scalar_bounds(const char *who, D *d, int n, const int *active, const dou
     if (!d) { tlab_set_error(std::string(who) + ": null handle"); return TLAB_EINVAL; }
     return d->bounds.set(who, d->nscal, n, active, lo, hi) ? TLAB_OK : TLAB_EINVAL;
 }
+
+// What the tail of ONE Runge-Kutta substep does beyond the RHS (TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT, time.f90:559-664), handed as a value to the substep
+// entry of each driver (internal.hpp): the public entries pass the driver's own settings, {kco, scale, &d->bounds, true, true}, the deferred tail what
+// its record holds.  The RHS on its own is a call without a tail (a null pointer inside the drivers): no update, no scalar zones, no forces.
+struct SubstepTail {
+    double kco;                       // hq, hs *= kco after the update ...
+    int scale;                        // ... unless 0
+    const ScalarBounds *bounds;       // DNS_BOUNDS_LIMIT after the update; null or empty: none
+    bool scal_zones;                  // BOUNDARY_BUFFER_RELAX_SCAL: the scalar buffer blocks the driver holds act
+    bool forces;                      // TLab_Sources_Flow: the body forces the driver holds act
+    bool clips(int is) const { return bounds && bounds->active(is); }
+};
 
 // BcsFlowJmin/Jmax%type of u, v, w and BcsScalJmin/Jmax%type of the scalars (TLAB_DNS_BCS_*)
 struct WallBcs {
@@ -121,8 +132,19 @@ void bind_arrays(const std::string &who, int nscal, R &rank, double *const *q, d
 template <class D>
 bool bound_fields(D *d, tlab_bound_fields *out) {
     if (!d || d->rk.size() != 1 || !d->rk[0].bound) return false;
-    *out = {d->rk[0].q.data(), d->rk[0].s.data(), d->rk[0].hq.data(), d->rk[0].hs.data(), d->nscal, d->n, &d->bounds};
+    *out = {d->rk[0].q.data(), d->rk[0].s.data(), d->rk[0].hq.data(), d->rk[0].hs.data(), d->nscal, d->n, d->bounds.any()};
     return true;
+}
+
+// tlab_{slab,pencil}_dns_set_coriolis / _set_buoyancy of a decomposed driver D: y is never split, so the forces of a local rank live in its
+// single-domain handle (handle(d, R), made on first use) and every one takes the same setting -- set(h) is the single-domain entry `what` on h
+template <class D, class H, class F>
+int set_on_ranks(D *d, H handle, const char *what, F set) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) ok(set(nullptr), what);      // (the argument checks come first, as there)
+        for (auto &R : d->rk) ok(set(handle(d, R)), what);
+    }, TLAB_EINVAL);
 }
 
 // time.f90:523-538, explicit RK: the smaller of the advective and the diffusive limit of pmax (TIME_COURANT); 0 without a CFL number

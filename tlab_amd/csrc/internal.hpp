@@ -10,7 +10,7 @@
 #include "../../include/tlab_amd.h"
 
 namespace tlab {
-struct ScalarBounds;      // driver_common.hpp
+struct SubstepTail;      // driver_common.hpp
 }
 
 // ---- capi.cpp ----
@@ -87,21 +87,21 @@ int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, co
 // ---- rhs.cpp ----
 long long tlab_internal_dns_points(tlab_dns_t d);      // deferred.cpp
 int tlab_internal_dns_nscal(tlab_dns_t d);
-tlab::ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d);      // deferred.cpp: the driver's own scalar bounds (tlab_dns_set_scalar_bounds)
-// deferred.cpp: does the driver hold scalar buffer zones, and the switch that makes its substep apply them (returns the old setting)
-bool tlab_internal_dns_has_flow_zones(tlab_dns_t d);      // slab.cpp: the zones of a rank live in its single-domain handle
+// what the driver holds (deferred.cpp; slab.cpp, pencil.cpp: the zones and forces of a rank live in its single-domain handle)
+bool tlab_internal_dns_has_bounds(tlab_dns_t d);
+bool tlab_internal_dns_has_flow_zones(tlab_dns_t d);
 bool tlab_internal_dns_has_scal_zones(tlab_dns_t d);
-bool tlab_internal_dns_scal_zones_in_substep(tlab_dns_t d, bool on);
-// deferred.cpp: the switch that makes the substeps of the three drivers apply the body forces (returns the old setting; one for the process, it is
-// held only around the one replayed call); slab.cpp, pencil.cpp: the forces of a rank live in its single-domain handle -- set, and the switch on?
-bool tlab_internal_dns_forces_in_substep(bool on);
-bool tlab_internal_dns_forces_active(tlab_dns_t d);
+bool tlab_internal_dns_has_forces(tlab_dns_t d);
 // shared by the three drivers: n entries (<= nscal) of active / lo / hi checked, the bounds of the active ones returned (on[is] = 0 otherwise)
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi);
 // q += dte h, q = min(max(q, lo), hi), h *= kco: the scalar update of the decomposed drivers with their bounds (pencil.cpp)
 int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi);
 extern "C" {
+// the substep with the tail the caller hands over (driver_common.hpp: SubstepTail), behind tlab_time_substep_incompressible_explicit -- which passes
+// the driver's own settings -- and the replay of a record (deferred.cpp); throws tlab::Fail
+void tlab_internal_dns_substep(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
+                               const tlab::SubstepTail &tail);
 // the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
 int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff,
                               double *pmax);
@@ -110,13 +110,16 @@ int tlab_internal_dns_neumann_weights(tlab_dns_t d, int ibc, const double **w, i
 }
 
 // ---- slab.cpp, pencil.cpp ----
-// deferred.cpp: the arrays a decomposed driver is bound to (the ONE local rank of a Fortran / MPI host) and the driver's own scalar bounds
+// deferred.cpp: the arrays a decomposed driver is bound to (the ONE local rank of a Fortran / MPI host) and whether it holds scalar bounds of its own
 // (tlab_*_set_scalar_bounds); false: not bound, or several local ranks -- loopback runs -- which have no single DAXPY partner
 struct tlab_bound_fields {
     double *const *q, *const *s, *const *hq, *const *hs;
     int nscal;
     long long n;
-    tlab::ScalarBounds *bounds;
+    bool has_bounds;
 };
 bool tlab_internal_slab_bound(tlab_slab_dns_t d, tlab_bound_fields *out);
 bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, tlab_bound_fields *out);
+// the substep with the tail the caller hands over, behind tlab_slab_dns_substep / tlab_pencil_dns_substep and the replay of a record; throw tlab::Fail
+void tlab_internal_slab_substep(tlab_slab_dns_t d, double dte, const tlab::SubstepTail &tail);
+void tlab_internal_pencil_substep(tlab_pencil_dns_t d, double dte, const tlab::SubstepTail &tail);

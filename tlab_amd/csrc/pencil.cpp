@@ -108,10 +108,6 @@ struct tlab_pencil_dns {
     bool fresh = false;
     ScalarBounds bounds;
     bool overlap = true;              // rhs_overlapped (exchanges started ahead of independent launches) instead of the literal sequence; TLAB_PENCIL_OVERLAP=0
-    // tlab_pencil_dns_substep: the velocities are finished by ONE pass each behind the pressure gradient (h -= dp/dx_i, zero wall planes, q += dte h,
-    // h *= kco: k_final_update, the arithmetic of k_sub3 + k_set_wall_planes + k_rk_update in the same order) where all their walls are Dirichlet;
-    // TLAB_PENCIL_FINAL=0 keeps the three passes
-    struct { bool on = false, done = false; double dte = 0.0, kco = 1.0; int scale = 0; } fin;
     bool tracing = false;             // tlab_pencil_dns_trace: the order of exchange starts, launches and waits of the last RHS
     std::string trace;
     long long launches = 0;           // launches issued so far by the overlapped schedule (a wait looks whether any followed its start)
@@ -302,21 +298,21 @@ void need_bound(D *d) {
         if (!R.bound) throw Fail(TLAB_EINVAL, "tlab_pencil_dns: the arrays of every local rank must be bound first (tlab_pencil_dns_bind)");
 }
 
-// the tail of the velocities: sub3 + wall planes (+ Neumann planes) as the reference does it, or -- inside tlab_pencil_dns_substep with Dirichlet walls -- one
-// fused pass per component that also does the Runge-Kutta update (rhs_global_incompressible_1.f90:348-375, time.f90:645-664, :272-297)
-void finish_velocities(D *d) {
+// the tail of the velocities: sub3 + wall planes (+ Neumann planes) as the reference does it, or -- inside a substep (tail) where all their walls are
+// Dirichlet -- ONE pass per component behind the pressure gradient that also does the Runge-Kutta update (h -= dp/dx_i, zero wall planes, q += dte h,
+// h *= kco: k_final_update, the arithmetic of k_sub3 + k_set_wall_planes + k_rk_update in the same order; rhs_global_incompressible_1.f90:348-375,
+// time.f90:645-664, :272-297); TLAB_PENCIL_FINAL=0 keeps the three passes.  Returns whether the velocities were finished by the fused pass.
+bool finish_velocities(D *d, double dte, const SubstepTail *tail) {
     const int nx = d->imax, ny = d->ny, kmax = d->kmax;
     const long long n = d->n;
     static const bool fused_ok = [] { const char *e = getenv("TLAB_PENCIL_FINAL"); return !(e && atoi(e) == 0); }();
     bool dirichlet = true;
     for (int i = 0; i < 3; ++i) dirichlet = dirichlet && d->bcs.flow_jmin[i] != TLAB_DNS_BCS_NEUMANN && d->bcs.flow_jmax[i] != TLAB_DNS_BCS_NEUMANN;
-    d->fin.done = false;
-    if (d->fin.on && fused_ok && dirichlet) {
+    if (tail && fused_ok && dirichlet) {
         for (Rank &R : d->rk)
             for (int i = 0; i < 3; ++i)
-                ok(tlab_pw_final_update(R.q[i], R.hq[i], R.txc[1 + i], nullptr, nullptr, d->fin.dte, d->fin.kco, d->fin.scale, nx, ny, kmax), "tlab_pw_final_update");
-        d->fin.done = true;
-        return;
+                ok(tlab_pw_final_update(R.q[i], R.hq[i], R.txc[1 + i], nullptr, nullptr, dte, tail->kco, tail->scale, nx, ny, kmax), "tlab_pw_final_update");
+        return true;
     }
     for (Rank &R : d->rk) ok(tlab_pw_sub3(R.hq[0], R.hq[1], R.hq[2], R.txc[1], R.txc[2], R.txc[3], n), "tlab_pw_sub3");
     for (Rank &R : d->rk)
@@ -325,6 +321,7 @@ void finish_velocities(D *d) {
             if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, R.hq[i], R.hb, R.ht, R.txc[0]), "tlab_boundary_bcs_neumann_y");
             ok(tlab_pw_set_wall_planes(R.hq[i], (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
         }
+    return false;
 }
 
 // tools/dns/rhs_global_incompressible_1.f90:98-398
@@ -334,20 +331,17 @@ void relax_flow(D *d) {
     for (Rank &R : d->rk)
         if (R.dns && tlab_internal_dns_has_flow_zones(R.dns)) ok(tlab_dns_buffer_relax_flow(R.dns, R.q.data(), R.hq.data()), "tlab_dns_buffer_relax_flow");
 }
-void relax_scal(D *d) {
-    for (Rank &R : d->rk)
-        if (R.dns && tlab_internal_dns_has_scal_zones(R.dns)) ok(tlab_dns_buffer_relax_scal(R.dns, R.s.data(), R.hs.data()), "tlab_dns_buffer_relax_scal");
-}
 
-// TLab_Sources_Flow (time.f90:610; tlab_pencil_dns_set_coriolis / _set_buoyancy) of the substep under way: y is never split, so the launch of a rank
+// TLab_Sources_Flow (time.f90:610; tlab_pencil_dns_set_coriolis / _set_buoyancy) of a substep (tail): y is never split, so the launch of a rank
 // acts on its box with the global profile.  Called where every Burgers sum of hq is complete and before hq is read for the forcing.
-void body_forces(D *d) {
-    if (!d->fin.on) return;      // (the RHS on its own adds no force)
+void body_forces(D *d, const SubstepTail *tail) {
+    if (!tail || !tail->forces) return;      // (the RHS on its own adds no force)
     for (Rank &R : d->rk)
-        if (R.dns && tlab_internal_dns_forces_active(R.dns)) ok(tlab_dns_sources_flow(R.dns, R.q.data(), R.s.data(), R.hq.data()), "tlab_dns_sources_flow");
+        if (R.dns && tlab_internal_dns_has_forces(R.dns)) ok(tlab_dns_sources_flow(R.dns, R.q.data(), R.s.data(), R.hq.data()), "tlab_dns_sources_flow");
 }
 
-void rhs(D *d, double dte) {
+// tail: the substep this RHS is part of (SubstepTail), NULL: the RHS on its own; returns finish_velocities' answer
+bool rhs(D *d, double dte, const SubstepTail *tail) {
     need_bound(d);
     if (tlab_internal_anelastic() || tlab_internal_dealiasing())
         throw Fail(TLAB_EUNSUPPORTED, "tlab_pencil_dns_rhs: the anelastic formulation / dealiasing filters are not built into the decomposed drivers");
@@ -383,7 +377,7 @@ void rhs(D *d, double dte) {
         add3([i](Rank &R) { return R.hs[i]; }, 0, 1, 2);
     }
     relax_flow(d);                                                                // :170-172
-    body_forces(d);
+    body_forces(d, tail);
     // pressure (:188-260)
     for (Rank &R : d->rk)
         ok(tlab_pw_axpy3(R.txc[1], R.txc[2], R.txc[3], R.hq[1], R.hq[0], R.hq[2], R.q[1], R.q[0], R.q[2], 1.0 / dte, n), "tlab_pw_axpy3");
@@ -396,7 +390,7 @@ void rhs(D *d, double dte) {
     partial_t(d, 1, 0, 1);                                                        // :319
     partial_t(d, 3, 0, 3);                                                        // :320
     // boundary conditions (:360-398); y is never split, BOUNDARY_BCS_NEUMANN_Y needs no communication
-    finish_velocities(d);
+    const bool finished = finish_velocities(d, dte, tail);
     for (Rank &R : d->rk) {
         auto walls = [&](double *h, int tmin, int tmax) {
             const int ibc = (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
@@ -405,6 +399,7 @@ void rhs(D *d, double dte) {
         };
         for (int i = 0; i < ns; ++i) walls(R.hs[i], d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]);
     }
+    return finished;
 }
 
 // ---- the same RHS with the transpositions started AHEAD of independent launches (missing 2; the reference's analogue:
@@ -574,7 +569,7 @@ void run_pipeline(D *d, std::vector<TOp> &ops, std::vector<LocalOp> &local) {
     for (LocalOp &l : local) if (!l.done) throw Fail(TLAB_EINVAL, "internal: pencil schedule left a launch behind");
 }
 
-void rhs_overlapped(D *d, double dte) {
+bool rhs_overlapped(D *d, double dte, const SubstepTail *tail) {
     need_bound(d);
     if (tlab_internal_anelastic() || tlab_internal_dealiasing())
         throw Fail(TLAB_EUNSUPPORTED, "tlab_pencil_dns_rhs: the anelastic formulation / dealiasing filters are not built into the decomposed drivers");
@@ -640,7 +635,7 @@ void rhs_overlapped(D *d, double dte) {
     // sum of an earlier equation standing before the y term of a later one that reuses its set)
     run_pipeline(d, ops, local);
     relax_flow(d);                                                                // :170-172
-    body_forces(d);
+    body_forces(d, tail);
     // pressure (:188-260)
     for (Rank &R : d->rk)
         ok(tlab_pw_axpy3(R.txc[1], R.txc[2], R.txc[3], R.hq[1], R.hq[0], R.hq[2], R.q[1], R.q[0], R.q[2], 1.0 / dte, n), "tlab_pw_axpy3");
@@ -674,7 +669,7 @@ void rhs_overlapped(D *d, double dte) {
             }});
         run_pipeline(d, po, pl);
     }
-    finish_velocities(d);
+    return finish_velocities(d, dte, tail);
 }
 
 // ---- monitors (TIME_COURANT, DNS_BOUNDS_CONTROL) ----
@@ -869,25 +864,14 @@ int tlab_pencil_dns_trace(tlab_pencil_dns_t d, int on, char *buf, int size) {
 int tlab_pencil_dns_rhs(tlab_pencil_dns_t d, double dte) {
     return guarded([&] {
         if (!d || !(dte > 0.0)) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_rhs: bad arguments");
-        if (d->overlap) rhs_overlapped(d, dte); else rhs(d, dte);
+        (void)(d->overlap ? rhs_overlapped(d, dte, nullptr) : rhs(d, dte, nullptr));
     });
 }
 
 int tlab_pencil_dns_substep(tlab_pencil_dns_t d, double dte, double kco, int scale_tendencies) {
     return guarded([&] {
         if (!d || !(dte > 0.0)) throw Fail(TLAB_EINVAL, "tlab_pencil_dns_substep: bad arguments");
-        d->fin.on = true; d->fin.dte = dte; d->fin.kco = kco; d->fin.scale = scale_tendencies;
-        struct Off { D *d; ~Off() { d->fin.on = false; } } off{d};      // (also when the RHS throws)
-        if (d->overlap) rhs_overlapped(d, dte); else rhs(d, dte);
-        relax_scal(d);               // time.f90:628-630: after the RHS with its wall BCs, before the update
-        for (Rank &R : d->rk) {      // time.f90:645-664, :272-297
-            for (int i = 0; i < 3 && !d->fin.done; ++i) ok(tlab_pw_rk_update(R.q[i], R.hq[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
-            for (int i = 0; i < d->nscal; ++i) {      // (+ DNS_BOUNDS_LIMIT, dns_local.f90:67-90, in the same pass where the scalar is limited)
-                if (d->bounds.active(i))
-                    ok(tlab_internal_pw_rk_update_clip(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n, d->bounds.lo[i], d->bounds.hi[i]), "tlab_pw_rk_update (bounds)");
-                else ok(tlab_pw_rk_update(R.s[i], R.hs[i], dte, kco, scale_tendencies, d->n), "tlab_pw_rk_update");
-            }
-        }
+        tlab_internal_pencil_substep(d, dte, {kco, scale_tendencies, &d->bounds, true, true});
     });
 }
 
@@ -939,21 +923,13 @@ int tlab_pencil_dns_set_buffer_zone(tlab_pencil_dns_t d, int l, int end, int gro
 }
 
 int tlab_pencil_dns_set_coriolis(tlab_pencil_dns_t d, int type, const double *vector, const double *parameters) {
-    (void)tlab_internal_deferred_flush();
-    return catch_fail([&] {
-        if (!d) ok(tlab_dns_set_coriolis(nullptr, type, vector, parameters), "tlab_dns_set_coriolis");      // (the argument checks come first, as there)
-        for (Rank &R : d->rk) ok(tlab_dns_set_coriolis(dns_handle(d, R), type, vector, parameters), "tlab_dns_set_coriolis");
-    }, TLAB_EINVAL);
+    return set_on_ranks(d, dns_handle, "tlab_dns_set_coriolis", [&](tlab_dns_t h) { return tlab_dns_set_coriolis(h, type, vector, parameters); });
 }
 
 int tlab_pencil_dns_set_buoyancy(tlab_pencil_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters,
                                  int inb_scal_array, const double *bbackground) {
-    (void)tlab_internal_deferred_flush();
-    return catch_fail([&] {
-        if (!d) ok(tlab_dns_set_buoyancy(nullptr, type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
-        for (Rank &R : d->rk)
-            ok(tlab_dns_set_buoyancy(dns_handle(d, R), type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
-    }, TLAB_EINVAL);
+    return set_on_ranks(d, dns_handle, "tlab_dns_set_buoyancy",
+                        [&](tlab_dns_t h) { return tlab_dns_set_buoyancy(h, type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground); });
 }
 
 int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *active, const double *lo, const double *hi) {
@@ -963,3 +939,17 @@ int tlab_pencil_dns_set_scalar_bounds(tlab_pencil_dns_t d, int n, const int *act
 }  // extern "C"
 
 bool tlab_internal_pencil_bound(tlab_pencil_dns_t d, tlab_bound_fields *out) { return bound_fields(d, out); }
+void tlab_internal_pencil_substep(tlab_pencil_dns_t d, double dte, const SubstepTail &tail) {
+    const bool finished = d->overlap ? rhs_overlapped(d, dte, &tail) : rhs(d, dte, &tail);
+    if (tail.scal_zones)      // BOUNDARY_BUFFER_RELAX_SCAL (time.f90:628-630): after the RHS with its wall BCs, before the update
+        for (Rank &R : d->rk)
+            if (R.dns && tlab_internal_dns_has_scal_zones(R.dns)) ok(tlab_dns_buffer_relax_scal(R.dns, R.s.data(), R.hs.data()), "tlab_dns_buffer_relax_scal");
+    for (Rank &R : d->rk) {                  // time.f90:645-664, :272-297
+        for (int i = 0; i < 3 && !finished; ++i) ok(tlab_pw_rk_update(R.q[i], R.hq[i], dte, tail.kco, tail.scale, d->n), "tlab_pw_rk_update");
+        for (int i = 0; i < d->nscal; ++i) {      // (+ DNS_BOUNDS_LIMIT, dns_local.f90:67-90, in the same pass where the scalar is limited)
+            if (tail.clips(i))
+                ok(tlab_internal_pw_rk_update_clip(R.s[i], R.hs[i], dte, tail.kco, tail.scale, d->n, tail.bounds->lo[i], tail.bounds->hi[i]), "tlab_pw_rk_update (bounds)");
+            else ok(tlab_pw_rk_update(R.s[i], R.hs[i], dte, tail.kco, tail.scale, d->n), "tlab_pw_rk_update");
+        }
+    }
+}

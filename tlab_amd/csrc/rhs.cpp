@@ -36,7 +36,6 @@ struct tlab_dns {
     bool fresh = false;                            // one-shot: hq, hs count as zero on entry of the next substep (tlab_dns_begin_step)
     WallBcs bcs;
     ScalarBounds bounds;                           // [Control] ScalLimit
-    std::vector<tlab::ClipBounds> clip_b;          // ... of the substep under way, as the kernels take them (rhs_impl)
     // dynamic surface model of the scalars (BcsScalJmin/Jmax%SfcType = DNS_SFC_LINEAR, %cpl; boundary_bcs.f90:29-31, 49-50, 478-546)
     std::vector<int> sfc_jmin, sfc_jmax;
     std::vector<double> cpl_jmin, cpl_jmax;
@@ -57,9 +56,6 @@ struct tlab_dns {
     // [BufferZone] Type = relaxation: BuffFlowJmin/Jmax, BuffScalJmin/Jmax (boundary_buffer.f90) -- buff[group][end], group 0 flow / 1 scalars,
     // end 0 Jmin / 1 Jmax; size 0: that block is off.  tau (size, nf) and ref (nx, size, nz, nf) are device memory the driver owns.
     struct BufferBlock { int size = 0, offset = 0, nf = 0; double *tau = nullptr, *ref = nullptr; } buff[2][2];
-    // the substep applies the scalar blocks (BOUNDARY_BUFFER_RELAX_SCAL, time.f90:628-630); the deferred tail switches this off for the replay of a
-    // record that holds no tlab_deferred_relax_scal: RHS + DAXPY does not relax the scalars, whichever way it is replayed
-    bool scal_zones_in_substep = true;
     // [Rotation] and [BodyForce] (tlab_dns_set_coriolis / _set_buoyancy): TLab_Sources_Flow as the one launch of k_body_force; bprof: the ny values
     // the buoyancy function subtracts (or starts from), made from bbackground when it is set
     tlab::BodyForce force;
@@ -156,16 +152,10 @@ bool neumann_weights(tlab_dns *d, int ibc) {
 
 long long tlab_internal_dns_points(tlab_dns_t d) { return d ? (long long)d->nx * d->ny * d->nz : 0; }
 int tlab_internal_dns_nscal(tlab_dns_t d) { return d ? d->nscal : 0; }
-ScalarBounds *tlab_internal_dns_bounds(tlab_dns_t d) { return &d->bounds; }
+bool tlab_internal_dns_has_bounds(tlab_dns_t d) { return d && d->bounds.any(); }
 bool tlab_internal_dns_has_flow_zones(tlab_dns_t d) { return d && (d->buff[0][0].size > 0 || d->buff[0][1].size > 0); }
 bool tlab_internal_dns_has_scal_zones(tlab_dns_t d) { return d && d->nscal > 0 && (d->buff[1][0].size > 0 || d->buff[1][1].size > 0); }
-bool tlab_internal_dns_scal_zones_in_substep(tlab_dns_t d, bool on) { const bool was = d->scal_zones_in_substep; d->scal_zones_in_substep = on; return was; }
-// the substeps of the three drivers apply the body forces (time.f90:610); the deferred tail switches this off for the replay of a record that holds no
-// tlab_deferred_sources_flow: RHS + DAXPY alone adds no force, whichever way it is replayed
-static bool g_forces_in_substep = true;
-bool tlab_internal_dns_forces_in_substep(bool on) { const bool was = g_forces_in_substep; g_forces_in_substep = on; return was; }
-bool tlab_internal_dns_forces_active(tlab_dns_t d) { return d && g_forces_in_substep && d->force.any(); }
-
+bool tlab_internal_dns_has_forces(tlab_dns_t d) { return d && d->force.any(); }
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi) {
     on.clear(); blo.clear(); bhi.clear();
@@ -299,9 +289,6 @@ static void burgers_into(tlab_dns_t d, int dir, double nu, const double *s, cons
     pending_add = true;
 }
 
-// bounds of scalar is, or NULL when it is not limited
-static const tlab::ClipBounds *clip_of(tlab_dns_t d, int is) { return d->bounds.active(is) ? &d->clip_b[is] : nullptr; }
-
 // RELAX_BLOCK of the blocks of one group (0: BOUNDARY_BUFFER_RELAX_FLOW on q, hq; 1: BOUNDARY_BUFFER_RELAX_SCAL on s, hs), Jmin before Jmax, four fields a launch
 static bool buffer_any(tlab_dns_t d, int group) { return d->buff[group][0].size > 0 || d->buff[group][1].size > 0; }
 static void buffer_relax(tlab_dns_t d, int group, double *const *a, double *const *h, hipStream_t st) {
@@ -319,14 +306,20 @@ static void body_force(tlab_dns_t d, double *const *q, double *const *s, double 
     hk(launch_body_force(d->force, hq, q, s, d->bprof, d->nx, d->ny, d->nz, st), "body force");
 }
 
+// tail: what follows the RHS in this substep (SubstepTail); NULL: the RHS on its own -- no update, no scalar zones, no forces
 static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs,
-                     double *const *txc, bool tail_update, double kco, int scale_tendencies) {
+                     double *const *txc, const SubstepTail *tail) {
     const int nx = d->nx, ny = d->ny, nz = d->nz;
     const long long n = (long long)nx * ny * nz;
     hipStream_t st = tlab_current_stream();
     follow_anelastic(d);
-    d->clip_b.resize(d->bounds.on.size());
-    for (size_t is = 0; is < d->clip_b.size(); ++is) d->clip_b[is] = {d->bounds.lo[is], d->bounds.hi[is]};
+    const double kco = tail ? tail->kco : 1.0;
+    const int scale_tendencies = tail ? tail->scale : 0;
+    // the bounds of the tail as the kernels take them; clip_of: those of scalar is, or NULL when it is not limited
+    std::vector<tlab::ClipBounds> tail_clip;
+    if (tail && tail->bounds)
+        for (size_t is = 0; is < tail->bounds->on.size(); ++is) tail_clip.push_back({tail->bounds->lo[is], tail->bounds->hi[is]});
+    auto clip_of = [&](int is) -> const tlab::ClipBounds * { return tail && tail->clips(is) ? &tail_clip[is] : nullptr; };
     double *u = q[0], *v = q[1], *w = q[2];
     double *tmp1 = txc[0], *tmp2 = txc[1], *tmp3 = txc[2], *tmp4 = txc[3], *tmp7 = txc[6], *tmp8 = txc[7], *tmp9 = txc[8];
     tlab_fdm_plan_t gx = d->g[0], gy = d->g[1], gz = d->g[2];
@@ -381,9 +374,9 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // y/z tile kernels do not, measured).  The directions then run z, y, x instead of x, y, z: the terms are summed in another order, rounding only.
     static const bool finish_off = [] { const char *e = getenv("TLAB_SCALAR_FINISH"); return e && atoi(e) == 0; }();
     // TLab_Sources_Flow runs before the RHS in the substep (time.f90:610-612), never in the RHS on its own
-    const bool forces = tail_update && tlab_internal_dns_forces_active(d);
-    const bool zone_flow = buffer_any(d, 0), zone_scal = tail_update && d->nscal > 0 && d->scal_zones_in_substep && buffer_any(d, 1);
-    bool finish_scal = !finish_off && batched && !literal && tail_update && d->nscal > 0 && tlab_internal_burgers_can_finish(1, gx, nx, ny, nz);
+    const bool forces = tail && tail->forces && d->force.any();
+    const bool zone_flow = buffer_any(d, 0), zone_scal = tail && tail->scal_zones && d->nscal > 0 && buffer_any(d, 1);
+    bool finish_scal = !finish_off && batched && !literal && tail && d->nscal > 0 && tlab_internal_burgers_can_finish(1, gx, nx, ny, nz);
     // Neumann scalars can ride too where the fused Neumann tail below applies: the epilogue finishes their interior with zero wall tendencies, and the
     // wall planes follow from weighted sums over the stored tendencies next to the walls (neumann_weights; k_wall_fix) instead of a derivative pass
     // over the field (TLAB_NEUMANN_PLANES=0: that pass, k_rtile<P1+neumann final>)
@@ -395,7 +388,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         for (int is = 0; is < d->nscal; ++is) scal_neu = scal_neu || ibc_of(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]) != 0;
         any_neu = any_neu || scal_neu;
         const char *npe = getenv("TLAB_NEUMANN_PLANES");
-        const bool tail_fast = any_neu && tail_update && d->fuse && !literal && nz > 1 && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && !any_surface &&
+        const bool tail_fast = any_neu && tail && d->fuse && !literal && nz > 1 && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && !any_surface &&
                                tlab_internal_poisson_can_v_final(d->poisson) && tlab_internal_neumann_final_ok(gy, nx, ny, nz) &&
                                tlab_internal_partial_p1_fusable(1, gx, nx, ny, nz) && tlab_internal_partial_p1_fusable(3, gz, nx, ny, nz);      // = neu_fast below
         if (finish_scal && scal_neu && tail_fast && !(npe && atoi(npe) == 0)) {
@@ -425,7 +418,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // scalar bounds in the epilogue that finishes scalar is: on every line, or -- Neumann walls on the wall-plane route -- on the interior lines, k_wall_fix
     // clipping the wall planes once they are set
     auto clip_into = [&](int is, int &mode, double &lo, double &hi) {
-        const tlab::ClipBounds *c = clip_of(d, is);
+        const tlab::ClipBounds *c = clip_of(is);
         if (!c) return;
         const bool neu = d->bcs.scal_jmin[is] == TLAB_DNS_BCS_NEUMANN || d->bcs.scal_jmax[is] == TLAB_DNS_BCS_NEUMANN;
         mode = (scal_neumann_planes && neu) ? 2 : 1;
@@ -531,7 +524,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     // the tail of the scalars under a buffer zone, once the wall planes of hs hold their BC values: BOUNDARY_BUFFER_RELAX_SCAL, s += dte hs, bounds, hs *= kco
     auto zone_scal_tail = [&] {
         buffer_relax(d, 1, s, hs, st);
-        for (int is = 0; is < d->nscal; ++is) hk(launch_rk_update(s[is], hs[is], dte, kco, scale_tendencies, n, st, clip_of(d, is)), "rk update");
+        for (int is = 0; is < d->nscal; ++is) hk(launch_rk_update(s[is], hs[is], dte, kco, scale_tendencies, n, st, clip_of(is)), "rk update");
     };
     if (zone_epi) {      // the wall planes inside the zones, after the epilogue that finished the rest (nothing below reads s or hs)
         for (int end = 0; end < 2; ++end) {
@@ -540,7 +533,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             const long long zone = (long long)nx * b.size * nz;
             for (int f0 = 0; f0 < b.nf; f0 += 4) {
                 const tlab::ClipBounds *cl[4] = {nullptr, nullptr, nullptr, nullptr};
-                for (int f = f0; f < std::min(b.nf, f0 + 4); ++f) cl[f - f0] = clip_of(d, f);
+                for (int f = f0; f < std::min(b.nf, f0 + 4); ++f) cl[f - f0] = clip_of(f);
                 // the wall plane the block starts from, and the opposite one where the block spans the whole height (tau need not vanish there: sigma = 0).
                 // (zone_epi excludes a wall plane that BOTH blocks hold: the plane form restarts from the BC value, so it runs once per plane)
                 for (int wall = 0; wall < 2; ++wall) {
@@ -617,10 +610,10 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     bool any_neumann = false;
     for (int iq = 0; iq < 3; ++iq) any_neumann = any_neumann || ibc_y(d->bcs.flow_jmin[iq], d->bcs.flow_jmax[iq]) != 0;
     for (int is = 0; is < d->nscal; ++is) any_neumann = any_neumann || ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]) != 0;
-    const bool neu_fast = any_neumann && tail_update && d->fuse && !literal && nz > 1 && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && !any_surface &&
+    const bool neu_fast = any_neumann && tail && d->fuse && !literal && nz > 1 && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && !any_surface &&
                           tlab_internal_poisson_can_v_final(d->poisson) && tlab_internal_neumann_final_ok(gy, nx, ny, nz) &&
                           tlab_internal_partial_p1_fusable(1, gx, nx, ny, nz) && tlab_internal_partial_p1_fusable(3, gz, nx, ny, nz);
-    if (tail_update && d->fuse && !literal && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && (walls_dirichlet || neu_fast) &&
+    if (tail && d->fuse && !literal && !d->pfilter[0] && !d->pfilter[1] && !d->pfilter[2] && (walls_dirichlet || neu_fast) &&
         tlab_internal_poisson_can_v_final(d->poisson)) {
         tlab_internal_poisson_arm_v_final(d->poisson, q[1], hq[1], dte, kco, scale_tendencies);
         v_final = true;
@@ -666,11 +659,11 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         if (zone_tail) zone_scal_tail();
         for (int is = 0; is < d->nscal && !finish_scal && !zone_tail; ++is) {
             const int ibc = ibc_y(d->bcs.scal_jmin[is], d->bcs.scal_jmax[is]);
-            if (ibc == 0) hk(launch_final_update(s[is], hs[is], nullptr, nullptr, nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)),
+            if (ibc == 0) hk(launch_final_update(s[is], hs[is], nullptr, nullptr, nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(is)),
                              "final update");
             else if (!tlab_internal_neumann_final(gy, nx, ny, nz, ibc, hs[is], s[is], dte, kco, scale_tendencies))
                 throw Fail(TLAB_EINVAL, "internal: inconsistent fused Neumann tail");
-            else if (const tlab::ClipBounds *c = clip_of(d, is))      // (the y-line tail kernel has no bounds epilogue: a pass of its own)
+            else if (const tlab::ClipBounds *c = clip_of(is))      // (the y-line tail kernel has no bounds epilogue: a pass of its own)
                 hk(launch_clip(s[is], c->lo, c->hi, n, st), "clip");
         }
         for (int is = 0; is < d->nscal && finish_scal && scal_neumann_planes; ++is) {      // finished by the x Burgers launch but for their wall planes
@@ -681,15 +674,15 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             if (!d->wall_planes) hk(hipMalloc((void **)&d->wall_planes, 6 * np * sizeof(double)), "hipMalloc");
             double *Sb = d->wall_planes, *St = Sb + np;
             hk(launch_wall_weighted(hs[is], nullptr, W.w, W.w + W.K, W.K, Sb, St, nullptr, nullptr, nx, ny, nz, st), "wall planes");
-            hk(launch_wall_fix(s[is], hs[is], (ibc & 1) ? Sb : nullptr, (ibc & 2) ? St : nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, clip_of(d, is)),
+            hk(launch_wall_fix(s[is], hs[is], (ibc & 1) ? Sb : nullptr, (ibc & 2) ? St : nullptr, dte, kco, scale_tendencies, nx, ny, nz, st, clip_of(is)),
                "wall planes");
         }
         return;
     }
-    // ---- pressure gradient (:319-320).  With Dirichlet walls and the RK update folded in (tail_update), the x- and z-gradient kernels
+    // ---- pressure gradient (:319-320).  With Dirichlet walls and the RK update folded in (tail), the x- and z-gradient kernels
     // finish u and w themselves: hq -= dp/dx; wall planes; q += dte hq; hq *= kco (no gradient array is written or re-read) ----
     bool grad_final = false, grad_sub = false;
-    if (tail_update && d->fuse && nz > 1 && !literal) {
+    if (tail && d->fuse && nz > 1 && !literal) {
         bool dirichlet = true;
         for (int iq = 0; iq < 3; ++iq) dirichlet = dirichlet && d->bcs.flow_jmin[iq] == TLAB_DNS_BCS_DIRICHLET && d->bcs.flow_jmax[iq] == TLAB_DNS_BCS_DIRICHLET;
         if (dirichlet && tlab_internal_partial_p1_fusable(1, gx, nx, ny, nz) && tlab_internal_partial_p1_fusable(3, gz, nx, ny, nz)) {
@@ -755,11 +748,11 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     if (anel) {
         double *gt[3] = {tmp2, tmp3, tmp4};
         for (int iq = 0; iq < 3; ++iq) {
-            gw_defer[iq] = tail_update && d->fuse && ibc_q[iq] == 0;
+            gw_defer[iq] = tail && d->fuse && ibc_q[iq] == 0;
             if (!gw_defer[iq]) hk(launch_weight_y(hq[iq], gt[iq], d->rib, nx, ny, n, 1, st), "weight");
         }
     }
-    if (tail_update) {
+    if (tail) {
         // hq -= grad p (:348-352), wall planes (:373-375), q += dte hq (time.f90:645-664), hq *= kco (:272-297) in one pass per field
         double *gp[3] = {tmp2, tmp3, tmp4};
         if (anel || grad_sub) gp[0] = gp[1] = gp[2] = nullptr;      // subtracted above (anelastic: with the density weight)
@@ -781,7 +774,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
         for (int is = 0; is < d->nscal && !finish_scal; ++is) {      // (finish_scal: done in the epilogue of the x Burgers launch)
             scal_planes(is, pb, pt);
             if (zone_tail) hk(launch_set_wall_planes(hs[is], pb, pt, nx, ny, nz, st), "wall planes");
-            else hk(launch_final_update(s[is], hs[is], nullptr, pb, pt, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(d, is)), "final update");
+            else hk(launch_final_update(s[is], hs[is], nullptr, pb, pt, dte, kco, scale_tendencies, nx, ny, nz, st, nullptr, clip_of(is)), "final update");
         }
         if (zone_tail) zone_scal_tail();
     } else {
@@ -801,15 +794,18 @@ int tlab_rhs_global_incompressible_1(tlab_dns_t d, double dte, double *const *q,
                                      double *const *hs, double *const *txc) {
     return catch_fail([&] {
         if (!d || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs)) || dte <= 0.0) throw Fail(TLAB_EINVAL, "tlab_rhs_global_incompressible_1: bad arguments");
-        rhs_impl(d, dte, q, s, hq, hs, txc, false, 1.0, 0);
+        rhs_impl(d, dte, q, s, hq, hs, txc, nullptr);
     }, TLAB_EINVAL);
 }
+
+void tlab_internal_dns_substep(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
+                               const SubstepTail &tail) { rhs_impl(d, dte, q, s, hq, hs, txc, &tail); }
 
 int tlab_time_substep_incompressible_explicit(tlab_dns_t d, double dte, double kco, int scale_tendencies, double *const *q,
                                               double *const *s, double *const *hq, double *const *hs, double *const *txc) {
     return catch_fail([&] {
         if (!d || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs)) || dte <= 0.0) throw Fail(TLAB_EINVAL, "tlab_time_substep_incompressible_explicit: bad arguments");
-        rhs_impl(d, dte, q, s, hq, hs, txc, true, kco, scale_tendencies);
+        tlab_internal_dns_substep(d, dte, q, s, hq, hs, txc, {kco, scale_tendencies, &d->bounds, true, true});
     }, TLAB_EINVAL);
 }
 
@@ -1031,13 +1027,14 @@ struct PlaceTimer {
     }
     double step(double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc, bool first_touch) {
         const double kdt[3] = {1.0 / 3.0, 15.0 / 16.0, 8.0 / 15.0}, kco[3] = {-5.0 / 9.0, -153.0 / 128.0, 1.0};
+        SubstepTail own{kco[0], 1, &d->bounds, true, true};      // the driver's own settings, as tlab_time_substep_incompressible_explicit passes them
         if (first_touch) {
             d->fresh = true;
-            rhs_impl(d, dtime * kdt[0], q, s, hq, hs, txc, true, kco[0], 1);
+            rhs_impl(d, dtime * kdt[0], q, s, hq, hs, txc, &own);
         }
         hk(hipEventRecord(e0, st), "hipEventRecord");
         d->fresh = true;
-        for (int k = 0; k < 3; ++k) rhs_impl(d, dtime * kdt[k], q, s, hq, hs, txc, true, kco[k], k < 2);
+        for (int k = 0; k < 3; ++k) { own.kco = kco[k]; own.scale = k < 2; rhs_impl(d, dtime * kdt[k], q, s, hq, hs, txc, &own); }
         hk(hipEventRecord(e1, st), "hipEventRecord");
         hk(hipEventSynchronize(e1), "hipEventSynchronize");
         float ms = 0.0f;

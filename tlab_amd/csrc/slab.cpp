@@ -428,8 +428,10 @@ void poisson_pencil(D *d) {
 }
 
 // Same terms as rhs.cpp / rhs_global_incompressible_1.f90:98-398; the z-terms are added last in every equation (the reference's order differs in
-// the third equation: rounding only).  tail: fold the RK update into the last pass of every field (TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT).
-void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
+// the third equation: rounding only).  tail (NULL: the RHS on its own): fold the RK update into the last pass of every field, SubstepTail.
+void rhs_halo(D *d, double dte, const SubstepTail *tail) {
+    const double tdte = tail ? dte : 0.0, kco = tail ? tail->kco : 1.0;
+    const int scale = tail ? tail->scale : 0;
     need_bound(d);
     refuse_unsupported_state("tlab_slab_dns_rhs");
     const int nx = d->nx, ny = d->ny, kmax = d->kmax, ns = d->nscal;
@@ -485,7 +487,7 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     bool zone_flow = false, zone_scal = false;
     for (Rank &R : d->rk) {
         zone_flow = zone_flow || (R.dns && tlab_internal_dns_has_flow_zones(R.dns));
-        zone_scal = zone_scal || (tail && R.dns && tlab_internal_dns_has_scal_zones(R.dns));
+        zone_scal = zone_scal || (tail && tail->scal_zones && R.dns && tlab_internal_dns_has_scal_zones(R.dns));
     }
     std::vector<int> zfin((size_t)(3 + ns), 0);
     for (int i = 0; i < ns; ++i)
@@ -498,9 +500,9 @@ void rhs_halo(D *d, double dte, bool tail, double tdte, double kco, int scale) {
     for (Rank &R : d->rk) badd_all(d, R, 1, fresh);
     // TLab_Sources_Flow (time.f90:610; tlab_slab_dns_set_coriolis / _set_buoyancy): y is never split, so the launch of a rank acts on its box with the
     // global profile.  Every tendency holds its first term now, and q, s are untouched until the second z pass finishes the scalars.
-    if (tail)
+    if (tail && tail->forces)
         for (Rank &R : d->rk)
-            if (R.dns && tlab_internal_dns_forces_active(R.dns)) ok(tlab_dns_sources_flow(R.dns, R.q.data(), R.s.data(), R.hq.data()), "tlab_dns_sources_flow");
+            if (R.dns && tlab_internal_dns_has_forces(R.dns)) ok(tlab_dns_sources_flow(R.dns, R.q.data(), R.s.data(), R.hq.data()), "tlab_dns_sources_flow");
     twait(d, w);
     for (Rank &R : d->rk) zburgers_all(d, R, 1);
     w = msg_start(d, 2 * (3 + ns));
@@ -808,18 +810,14 @@ int tlab_slab_dns_begin_step(tlab_slab_dns_t d) {
 int tlab_slab_dns_rhs(tlab_slab_dns_t d, double dte) {
     return guarded([&] {
         if (!d || !(dte > 0.0)) throw Fail(TLAB_EINVAL, "tlab_slab_dns_rhs: bad arguments");
-        rhs_halo(d, dte, false, 0.0, 1.0, 0);
+        rhs_halo(d, dte, nullptr);
     });
 }
 
 int tlab_slab_dns_substep(tlab_slab_dns_t d, double dte, double kco, int scale_tendencies) {
     return guarded([&] {
         if (!d || !(dte > 0.0)) throw Fail(TLAB_EINVAL, "tlab_slab_dns_substep: bad arguments");
-        rhs_halo(d, dte, true, dte, kco, scale_tendencies);
-        // DNS_BOUNDS_LIMIT (dns_local.f90:67-90) on the updated scalars: a pass of its own per field (the z pass that finishes them has no bounds epilogue)
-        for (int i = 0; i < (int)d->bounds.on.size(); ++i)
-            if (d->bounds.on[i])
-                for (Rank &R : d->rk) ok(tlab_pw_clip(R.s[i], d->bounds.lo[i], d->bounds.hi[i], d->n), "tlab_pw_clip");
+        tlab_internal_slab_substep(d, dte, {kco, scale_tendencies, &d->bounds, true, true});
     });
 }
 
@@ -919,21 +917,13 @@ int tlab_slab_dns_set_buffer_zone(tlab_slab_dns_t d, int l, int end, int group, 
 }
 
 int tlab_slab_dns_set_coriolis(tlab_slab_dns_t d, int type, const double *vector, const double *parameters) {
-    (void)tlab_internal_deferred_flush();
-    return catch_fail([&] {
-        if (!d) ok(tlab_dns_set_coriolis(nullptr, type, vector, parameters), "tlab_dns_set_coriolis");      // (the argument checks come first, as there)
-        for (Rank &R : d->rk) ok(tlab_dns_set_coriolis(dns_handle(d, R), type, vector, parameters), "tlab_dns_set_coriolis");
-    }, TLAB_EINVAL);
+    return set_on_ranks(d, dns_handle, "tlab_dns_set_coriolis", [&](tlab_dns_t h) { return tlab_dns_set_coriolis(h, type, vector, parameters); });
 }
 
 int tlab_slab_dns_set_buoyancy(tlab_slab_dns_t d, int type, const double *vector, int nscalars, const double *parameters, int nparameters,
                                int inb_scal_array, const double *bbackground) {
-    (void)tlab_internal_deferred_flush();
-    return catch_fail([&] {
-        if (!d) ok(tlab_dns_set_buoyancy(nullptr, type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
-        for (Rank &R : d->rk)
-            ok(tlab_dns_set_buoyancy(dns_handle(d, R), type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground), "tlab_dns_set_buoyancy");
-    }, TLAB_EINVAL);
+    return set_on_ranks(d, dns_handle, "tlab_dns_set_buoyancy",
+                        [&](tlab_dns_t h) { return tlab_dns_set_buoyancy(h, type, vector, nscalars, parameters, nparameters, inb_scal_array, bbackground); });
 }
 
 int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active, const double *lo, const double *hi) {
@@ -943,3 +933,10 @@ int tlab_slab_dns_set_scalar_bounds(tlab_slab_dns_t d, int n, const int *active,
 }  // extern "C"
 
 bool tlab_internal_slab_bound(tlab_slab_dns_t d, tlab_bound_fields *out) { return bound_fields(d, out); }
+void tlab_internal_slab_substep(tlab_slab_dns_t d, double dte, const SubstepTail &tail) {
+    rhs_halo(d, dte, &tail);
+    // DNS_BOUNDS_LIMIT (dns_local.f90:67-90) on the updated scalars: a pass of its own per field (the z pass that finishes them has no bounds epilogue)
+    for (int i = 0; i < d->nscal; ++i)
+        if (tail.clips(i))
+            for (Rank &R : d->rk) ok(tlab_pw_clip(R.s[i], tail.bounds->lo[i], tail.bounds->hi[i], d->n), "tlab_pw_clip");
+}
