@@ -68,6 +68,74 @@ def test_poisson_vs_oracle(T, nx, ny, nz, stretch):
         T.OPR_Poisson(plan, nx, ny, nz, T.BCS_ND, p2, t1, t2, dev(hb), dev(ht), None)
 
 
+ROUTES = {"default": {}, "fused 2-D": {"TLAB_FFTZ": "0"}, "rocFFT 1-D z": {"TLAB_FFTZ": "0", "TLAB_FFT2D": "0"}, "rocFFT forward x": {"TLAB_FFTX": "0"}}
+_ROUTE_REFS = {}
+
+
+def _route_case(T, op, nx, ny, nz, stretch):
+    """Inputs, device-side plan arguments and the oracle's answer of one (operator, shape) of test_transform_routes_vs_oracle: computed once, shared
+    by the four routes, never modified.  Returns (plans, kwargs, f, hb, ht, refs, bounds)."""
+    key = (op, nx, ny, nz)
+    if key in _ROUTE_REFS:
+        return _ROUTE_REFS[key]
+    from oracle import tlab_oracle as O, tlab_oracle_poisson as OP
+    if op == "direct":      # built like tests/test_gpu_poisson_direct.py builds it
+        import test_gpu_poisson_direct as D
+        (ogx, ogy, ogz), gp, f, hb, ht = D._setup(T, nx, ny, nz, ny + 3)
+        oplan = OP.PoissonDirectPlan(ogx, ogy, ogz, nx, ny, nz)
+        (p_ref, d_ref), (_, sc_d) = scatter_of(lambda f_, hb_, ht_: OP.opr_poisson_fxz_direct(oplan, f_, hb_, ht_, 3), [f, hb, ht], nsamples=2)
+        # p: the bound of the chunked kernel in test_marching_and_chunked_direct_solvers_agree; dp/dy = OPR_Partial_Y(p): max(1e-12, 2 x oracle scatter)
+        out = (gp, {"gy_elliptic": gp[1]}, f, hb.ravel(), ht.ravel(), (p_ref, d_ref), (1e-12, sc_d))
+    else:
+        x, y, z = setup(nx, ny, nz, stretch)
+        go = [O.FdmPlan(x, True, True), O.FdmPlan(y, False, not stretch), O.FdmPlan(z, True, True)]
+        gp = [T.FdmPlan(x, True, True), T.FdmPlan(y, False, not stretch), T.FdmPlan(z, True, True)]
+        rng = np.random.default_rng(nx + ny + nz + len(op))
+        N = nx * ny * nz
+        i = np.arange(N)
+        f = np.sin(0.3 * (i % nx)) * np.cos(0.07 * (i // nx)) + 0.2 * rng.uniform(-1, 1, N)
+        hb, ht = rng.uniform(-1, 1, nx * nz), rng.uniform(-1, 1, nx * nz)
+        plan_o = OP.PoissonPlan(go[0], go[1], go[2], nx, ny, nz)
+        if op == "helmholtz":
+            refs = (OP.opr_helmholtz_fxz_factorize(plan_o, f, hb.reshape(nz, nx), ht.reshape(nz, nx), O.BCS_NN, -7.5), None)
+        else:
+            refs = OP.opr_poisson_fxz(plan_o, f, hb.reshape(nz, nx), ht.reshape(nz, nx), ibc=O.BCS_NN if op == "NN" else O.BCS_DD)
+        out = (gp, {}, f, hb, ht, refs, (TOL, None))
+    _ROUTE_REFS[key] = out
+    return out
+
+
+@pytest.mark.parametrize("nx,ny,nz,stretch", [(32, 40, 16, True), (16, 33, 8, False)])      # chunked with low and four singular modes; marching
+@pytest.mark.parametrize("op", ["NN", "DD", "helmholtz", "direct"])
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_transform_routes_vs_oracle(T, route, op, nx, ny, nz, stretch, monkeypatch):
+    """Every transform route a plan can take (read at plan creation: the own z transform, the fused 2-D rocFFT plans where it is off, rocFFT's 1-D z
+    transform where both are off, rocFFT's forward x) under OPR_Poisson BCS_NN / BCS_DD with dp/dy, OPR_Helmholtz BCS_NN (alpha = -7.5) and a direct
+    plan's OPR_Poisson (ibc = 3, dp/dy), against the numpy oracle with the bounds of the neighbouring tests.  The other tests' nz all take the own z
+    transform.  Errors of the commit before the solver's source was split: profiles/r12/poisson_split.txt."""
+    import torch
+    for k in ("TLAB_FFTZ", "TLAB_FFT2D", "TLAB_FFTX"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in ROUTES[route].items():
+        monkeypatch.setenv(k, v)
+    gp, kw, f, hb, ht, (p_ref, d_ref), (tol_p, sc_d) = _route_case(T, op, nx, ny, nz, stretch)
+    plan = T.PoissonPlan(gp[0], gp[1], gp[2], nx, ny, nz, **kw)
+    assert bool(plan.direct) == (op == "direct")
+    p = dev(f)
+    t1 = torch.empty(plan.isize_txc_field, dtype=torch.float64, device="cuda")
+    t2 = torch.empty_like(t1)
+    dpdy = torch.full((nx * ny * nz,), float("nan"), dtype=torch.float64, device="cuda")
+    if op == "helmholtz":
+        T.OPR_Helmholtz(plan, nx, ny, nz, T.BCS_NN, -7.5, p, t1, t2, dev(hb), dev(ht))
+    else:
+        T.OPR_Poisson(plan, nx, ny, nz, {"NN": T.BCS_NN, "DD": T.BCS_DD, "direct": 3}[op], p, t1, t2, dev(hb), dev(ht), dpdy)
+    ep = rel_err(p.cpu().numpy(), p_ref)
+    ed = rel_err(dpdy.cpu().numpy(), d_ref) if d_ref is not None else 0.0
+    print("route %-16s %-9s %2dx%2dx%2d  p %.2e  dpdy %.2e" % (route, op, nx, ny, nz, ep, ed))
+    assert ep <= tol_p, ep
+    assert ed <= (TOL if sc_d is None else bound(sc_d)), (ed, sc_d)
+
+
 def test_chunked_and_marching_ode_kernels_agree(T, monkeypatch):
     """ny % 8 == 0 runs the register-chunked k_ode_nn; TLAB_ODE_CHUNKED=0 (read at plan creation) keeps the marching k_int1 kernels.
     Same discrete equations, same pivots: the two must agree to round-off on a large-lambda-range case."""

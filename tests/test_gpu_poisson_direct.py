@@ -27,6 +27,11 @@ def _tab(ny):
         tab = {k[len("tab_"):]: g[k] for k in g.files if k.startswith("tab_")}
         tab["nodes"] = g["y"]
         return tab, 17
+    if ny == 33:      # CompactDirect6 on uniform nodes (tests/golden/poisson_routes_y33.npz): the marching shape of test_gpu_poisson.py's route test
+        g = np.load(golden_files("poisson_routes_y33")[0])
+        tab = {k[len("tab_"):]: g[k] for k in g.files if k.startswith("tab_")}
+        tab["nodes"] = g["y"]
+        return tab, 16
     g = np.load(golden_files("direct_y")[0])
     return {k[len("ny%d_" % ny):]: g[k] for k in g.files if k.startswith("ny%d_" % ny)}, 16
 

@@ -5,7 +5,7 @@
 // (fdm/fdm_integral.f90:58-87 FDM_Int1_Initialize, :91-214 FDM_Int1_CreateSystem; fdm/fdm_base.f90:304-391 FDM_Bcs_Reduce; utils/linear3.f90:29-51,
 // utils/linear7.f90:30-93).  No example selects these schemes together with the factorized solver: correctness first.  The systems of ALL modes are
 // built and factorized HERE, on the host, at plan creation, operation by operation as the reference does it (no fused multiply-adds: the solution of
-// the Neumann problem is sensitive to the last bit of the factors), and the device kernel (poisson.hip: k_int1g) only substitutes.
+// the Neumann problem is sensitive to the last bit of the factors), and the device kernel (poisson_int1.hip: k_int1g) only substitutes.
 // Memory: (nd + 2) x n doubles per mode and system -- 4.2 GB for the 7-diagonal systems of a 512^3 box, of the 288 GB.
 #include "int1_generic.hpp"
 

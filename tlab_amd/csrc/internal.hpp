@@ -1,6 +1,7 @@
 // What the translation units of libtlab_amd.so call in each other and include/tlab_amd.h does not declare: every such function is declared HERE and
 // nowhere else.  The defining file includes this header too, so the compiler holds each definition against the one declaration the callers see
-// (the library is linked with -z defs: a call without a definition fails the build).  Grouped by defining file.
+// (the library is linked with -z defs: a call without a definition fails the build).  Grouped by defining file.  What the files of the Poisson solver
+// (poisson*.hip) call in each other, with their plan object, is declared in poisson_plan.hpp instead.
 #pragma once
 #include <hip/hip_runtime.h>
 

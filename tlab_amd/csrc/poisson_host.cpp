@@ -5,7 +5,7 @@
 // computes per Fourier mode that is LINEAR in the mode's constant lambda is kept here as its operands (c0, c1) and the row
 // normalisation S: lhs(lambda) = (L0 + lambda * L1) * S is evaluated per mode on the device with the reference's roundings
 // (two per entry + one for S), as are the only non-linear step (the reduction of the opposite boundary, :203-211, which
-// divides by a lambda-dependent pivot) and the pentadiagonal LU (poisson.hip).
+// divides by a lambda-dependent pivot) and the pentadiagonal LU (poisson_int1.hip, poisson_ode.hip).
 #include "poisson_host.hpp"
 
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Reduced reproducer of the k_int1g miscompilation (tlab_amd/csrc/poisson.hip):
+// Reduced reproducer of the k_int1g miscompilation (tlab_amd/csrc/poisson_int1.hip):
 //     hipcc -O3 --offload-arch=gfx950 tools/repro/int1g_O3.hip -o /tmp/int1g_O3 && /tmp/int1g_O3      -> device differs from the host
 //     hipcc -O0 --offload-arch=gfx950 tools/repro/int1g_O3.hip -o /tmp/int1g_O0 && /tmp/int1g_O0      -> device equals the host bit for bit
 // The SAME function body (HEPTADSS-style substitution of a 7-diagonal system + the MatMul_5d right-hand side with a unit forcing, one thread per
