@@ -372,7 +372,8 @@ int tlab_dns_buffer_relax_scal(tlab_dns_t d, double *const *s, double *const *hs
  *     (:279-291) otherwise (at most 6 scalars with a factor above small_wp: more is TLAB_EUNSUPPORTED); _BILINEAR b = ((c0 s1 + c1 s2) + (c2 s1) s2) - ref(j); _QUADRATIC
  *     b = (c0 s1)(s1 - c1) - ref(j), c0 = -p1 / (p2/2)^2.
  *   TLAB_EUNSUPPORTED, nothing stored: _EXPLICIT (Thermo_Anelastic_BUOYANCY), _NORMALIZEDMEAN and _SUBTRACTMEAN (they need the plane means FI_DIAGNOSTIC
- *     refreshes every substep), nscalars > nscal (diagnostic arrays such as liquid water are not held on the device).
+ *     refreshes every substep), nscalars > nscal on a driver without a mixture (no diagnostic array is held then), nscalars > nscal + 1 with one
+ *     (tlab_dns_set_mixture below: the liquid is entry nscal of s, and a linear buoyancy may carry a coefficient for it).
  *   TLAB_EINVAL: an unknown type, NaN or infinite values, a null handle, a type that reads scalars on a driver without them.  The arguments are
  *     checked before the handle.  Type 0 switches the term off; with both off, or all vectors zero, the driver launches the kernels of a run without
  *     forces, the results bit for bit.
@@ -380,7 +381,8 @@ int tlab_dns_buffer_relax_scal(tlab_dns_t d, double *const *s, double *const *hs
  * partial sum, none is finished; q and s are those from before the update), on the literal routes after the Burgers sums; always before the pressure
  * forcing and the wall planes of hq2 that become the Neumann data of the Poisson solver, so the force is projected.  Against the reference the terms
  * are summed in another order: rounding only.  tlab_rhs_global_incompressible_1 does not apply them (the reference's RHS does not either).
- * Not built: subsidence, SpecialForcing, TLab_Sources_Scal (radiation, sedimentation, chemistry), Gravity_Buoyancy_Source, the statistics' buoyancy. */
+ * Not built: subsidence, SpecialForcing, Gravity_Buoyancy_Source, the statistics' buoyancy; of TLab_Sources_Scal the gray-liquid infrared term is
+ * built (tlab_dns_set_infrared below), gray and band infrared, sedimentation and chemistry are not. */
 #define TLAB_COR_NONE 0
 #define TLAB_COR_EXPLICIT 4
 #define TLAB_COR_NORMALIZED 12
@@ -398,7 +400,47 @@ int tlab_dns_set_buoyancy(tlab_dns_t d, int type, const double *vector, int nsca
 /* TLab_Sources_Flow on its own: hq += the terms above and nothing else.  HOST arrays of DEVICE pointers q[3], s[nscal], hq[3]; a component no force
  * touches is neither read nor written, a velocity or scalar no active term needs is not read.  At most 2^31 - 1 points. */
 int tlab_dns_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq);
-long long tlab_dns_info(tlab_dns_t d, int what);      /* 0 nx, 1 ny, 2 nz, 3 nscal, 4 points of a field; -1: null handle or unknown code */
+/* Cloud-top physics of the single-domain driver: [Thermodynamics] Type = Linear, Mixture = AirWaterLinear, and [Infrared] Type = Bulk1dLocal
+ * (which the reference maps to grayliquid) -- examples/Case16-21, 54, 55.
+ *   Mixture: TLAB_MIXT_NONE or TLAB_MIXT_AIRWATERLINEAR (the reference's MIXT_TYPE_AIRWATER_LINEAR) with thermo_param(1:nparam), HOST values,
+ *     nparam >= nscal + 1.  With a mixture the driver has inb_scal_array = nscal + 1: EVERY entry point that takes s then reads nscal + 1 device
+ *     pointers, the last the liquid -- the host's contiguous s(isize_field, inb_scal_array); hs stays at nscal.  Other mixtures: TLAB_EUNSUPPORTED;
+ *     a driver without scalars, NaN / infinite parameters, nparam < nscal + 1: TLAB_EINVAL.  TLAB_MIXT_NONE also switches the infrared term off, and
+ *     is TLAB_EINVAL while a buoyancy that reads the liquid is set.
+ *   tlab_dns_diagnostic = FI_DIAGNOSTIC (physics/fi_diagnostic.f90:44-47): the liquid from the prognostic scalars, THERMO_AIRWATER_LINEAR
+ *     (thermodynamics/thermo_airwater.f90:483-516) in one pointwise launch (k_airwater_linear): xi = 1 + p1 s1 [+ p2 s2]; l = max(xi, 0) when
+ *     |p(nscal+1)| < small_wp, else l = d log(exp(xi (1/d)) + 1), d = p(nscal+1); the reference's operation order, unfused, and nothing beyond its
+ *     expression: where exp overflows (xi / d > 709.78) l is infinite, as in the reference.  No mixture: nothing is launched.
+ *     tlab_time_substep_incompressible_explicit refreshes the liquid once at its end, after s += dte hs (time.f90:248); the caller makes it valid before
+ *     the first substep.  tlab_rhs_global_incompressible_1 does not refresh it (the reference's RHS does not either).  The reference computes the liquid
+ *     from the unclipped scalars and clips afterwards (time.f90:248-250), the fused epilogues here clip first: a substep with a mixture AND active scalar
+ *     bounds returns TLAB_EUNSUPPORTED.  tlab_dns_place_arrays / _place_blocks place nscal scalar arrays and refuse a driver with a mixture.
+ *   Infrared: type TLAB_IR_NONE (switches the term off) or TLAB_IR_GRAY_LIQUID, with the values Radiation_Initialize leaves: scalar = the 1-based
+ *     equation the term acts on (infraredProps%active), kappa = kappa(1,1), flux_top = auxiliar(1), flux_bottom = auxiliar(2).  The absorbing field is
+ *     always the liquid (infraredProps%scalar(1) = inb_scal_array).  TLAB_EUNSUPPORTED, nothing stored: types 2, 3 (gray, band: they need a temperature
+ *     the reference derives for anelastic runs only), an anelastic driver, a y plan whose first-order integral is not the pentadiagonal system of
+ *     CompactJacobian6.  TLAB_EINVAL, nothing stored: no mixture (the reference stops there), scalar outside 1..nscal, NaN / infinite values.
+ *   tlab_dns_sources_scal = TLab_Sources_Scal (physics/tlab_sources.f90:152-168) on its own: hs[scalar-1] += source and nothing else; s is only read;
+ *     txc[0] is scratch, and txc[1] as well when flux_bottom != 0 (no other txc array is touched).  Radiation_Infrared_Y, TYPE_IR_GRAY_LIQUID
+ *     (physics/radiation.f90:265-283) with IR_RTE1_OnlyLiquid (:401-444), per (i, k) column in the reference's operation order: a = kappa l;
+ *     tau = FDM_Int1_Solve(fdm_Int0(BCS_MAX)) of a with tau(ny) = 0; f = exp(tau); source = a f flux_top, or a (f flux_top + f(1) / f flux_bottom) when
+ *     |flux_bottom| > 0.  One launch (k_infrared_y, csrc/radiation.hip), one thread per column: a 2-D run (nz = 1) has few columns and runs slowly but
+ *     correctly.
+ *   tlab_time_substep_incompressible_explicit applies the source once, from the s of before the update, where the body forces go: hs[scalar-1] holds a
+ *     valid partial sum and the launch that finishes that scalar has not run (fused routes), after the Burgers sums (literal routes).  Against the
+ *     reference, which adds it before the RHS (tools/dns/time.f90:611), the terms are summed in another order: rounding only.  With the term off there
+ *     is no launch and the results are those of a run without it, bit for bit.  tlab_rhs_global_incompressible_1 applies no source.
+ * Single-domain driver only: the slab and pencil drivers have no such setters, and no record of the deferred tail carries the source (a host with
+ * [Infrared] keeps tlab_deferred_enable off). */
+#define TLAB_MIXT_NONE 0
+#define TLAB_MIXT_AIRWATERLINEAR 12
+#define TLAB_IR_NONE 0
+#define TLAB_IR_GRAY_LIQUID 1
+int tlab_dns_set_mixture(tlab_dns_t d, int mixture, const double *thermo_param, int nparam);
+int tlab_dns_diagnostic(tlab_dns_t d, double *const *s);
+int tlab_dns_set_infrared(tlab_dns_t d, int type, int scalar, double kappa, double flux_top, double flux_bottom);
+int tlab_dns_sources_scal(tlab_dns_t d, double *const *s, double *const *hs, double *const *txc);
+long long tlab_dns_info(tlab_dns_t d, int what);      /* 0 nx, 1 ny, 2 nz, 3 nscal, 4 points of a field, 5 inb_scal_array (arrays in s); -1: null handle or unknown code */
 /* Start of a Runge-Kutta step: TIME_RUNGEKUTTA sets hq = 0, hs = 0 there (tools/dns/time.f90:212-216).  Instead of filling the arrays,
  * tell the driver: the next tlab_rhs_global_incompressible_1 / tlab_time_substep_incompressible_explicit treats them as zero (its first
  * operator launch overwrites instead of accumulating), whatever they contain. */

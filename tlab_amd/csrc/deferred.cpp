@@ -291,7 +291,7 @@ int tlab_deferred_sources_stats(long long *counts) {
 int tlab_deferred_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq) {
     if (!g_on) return tlab_dns_sources_flow(d, q, s, hq);
     if (!d || !q || !hq) { tlab_set_error("tlab_deferred_sources_flow: bad arguments"); return TLAB_EINVAL; }
-    const int ns = tlab_internal_dns_nscal(d);
+    const int ns = tlab_internal_dns_scal_arrays(d);      // (with a mixture s carries the liquid behind the prognostic scalars)
     if (ns > 0 && !s) { tlab_set_error("tlab_deferred_sources_flow: bad arguments"); return TLAB_EINVAL; }
     if (g_p.rhs || g_src.on) {         // (a marker nothing followed runs literally, after the zero fills that came before it)
         const int rc = flush_impl();
@@ -328,7 +328,8 @@ int tlab_deferred_rhs(tlab_dns_t d, double dte, double *const *q, double *const 
         if (rc != TLAB_OK) return rc;
     }
     // the arrays stay with the record: this driver takes them with every call
-    const std::vector<double *> Q(q, q + 3), S(s, s + ns), HQ(hq, hq + 3), HS(hs, hs + ns), T(txc, txc + 9);
+    const int na = tlab_internal_dns_scal_arrays(d);      // (with a mixture s carries the liquid behind the prognostic scalars)
+    const std::vector<double *> Q(q, q + 3), S(s, s + na), HQ(hq, hq + 3), HS(hs, hs + ns), T(txc, txc + 9);
     Driver drv;
     drv.begin_step = [d] { return tlab_dns_begin_step(d); };
     drv.rhs = [=](double dte_) {

@@ -80,14 +80,15 @@ int set_scalar_bounds(const char *who, D *d, int n, const int *active, const dou
 }
 
 // What the tail of ONE Runge-Kutta substep does beyond the RHS (TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT, time.f90:559-664), handed as a value to the substep
-// entry of each driver (internal.hpp): the public entries pass the driver's own settings, {kco, scale, &d->bounds, true, true}, the deferred tail what
-// its record holds.  The RHS on its own is a call without a tail (a null pointer inside the drivers): no update, no scalar zones, no forces.
+// entry of each driver (internal.hpp): the public entries pass the driver's own settings, {kco, scale, &d->bounds, true, true, true}, the deferred tail what
+// its record holds.  The RHS on its own is a call without a tail (a null pointer inside the drivers): no update, no scalar zones, no forces, no scalar sources.
 struct SubstepTail {
     double kco;                       // hq, hs *= kco after the update ...
     int scale;                        // ... unless 0
     const ScalarBounds *bounds;       // DNS_BOUNDS_LIMIT after the update; null or empty: none
     bool scal_zones;                  // BOUNDARY_BUFFER_RELAX_SCAL: the scalar buffer blocks the driver holds act
     bool forces;                      // TLab_Sources_Flow: the body forces the driver holds act
+    bool scal_sources = false;        // TLab_Sources_Scal: the infrared term the single-domain driver holds acts (no record of the deferred tail carries it)
     bool clips(int is) const { return bounds && bounds->active(is); }
 };
 

@@ -88,6 +88,7 @@ int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, co
 // ---- rhs.cpp ----
 long long tlab_internal_dns_points(tlab_dns_t d);      // deferred.cpp
 int tlab_internal_dns_nscal(tlab_dns_t d);
+int tlab_internal_dns_scal_arrays(tlab_dns_t d);      // inb_scal_array: nscal, + 1 (the liquid) with a mixture -- the arrays every s of the entry points holds
 // what the driver holds (deferred.cpp; slab.cpp, pencil.cpp: the zones and forces of a rank live in its single-domain handle)
 bool tlab_internal_dns_has_bounds(tlab_dns_t d);
 bool tlab_internal_dns_has_flow_zones(tlab_dns_t d);

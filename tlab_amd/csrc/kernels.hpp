@@ -207,6 +207,20 @@ struct BodyForce {
 };
 hipError_t launch_body_force(const BodyForce &F, double *const *hq, const double *const *q, const double *const *s, const double *prof, int nx, int ny,
                              int nz, hipStream_t st);
+// THERMO_AIRWATER_LINEAR (thermo_airwater.f90:483-516), what FI_DIAGNOSTIC calls for imixture = MIXT_TYPE_AIRWATER_LINEAR: the normalized liquid
+// l from xi = 1 + p1 s1 [+ p2 s2] (two scalars whenever ns > 1, as the reference), l = max(xi, 0) when |pd| < small_wp, else l = pd log(exp(xi / pd) + 1)
+// with 1 / pd formed first and multiplied, unfused.  s2 may be NULL when ns = 1.  At most 2^31 - 1 points.
+hipError_t launch_airwater_linear(double *l, const double *s1, const double *s2, int ns, double p1, double p2, double pd, long long n, hipStream_t st);
+
+// radiation.hip: Radiation_Infrared_Y, gray liquid, added to hs (k_infrared_y).  The coefficients every column shares: InfraredCoef by value (the
+// boundary rows of the right-hand side, the closure of row 1) and tab, [ny][8] device doubles (infrared_build_tables gives the host copy).
+// scr1: one field of scratch; scr2: a second one, read only when flux_bottom != 0.  l, hs and the scratch fields must not alias.
+struct InfraredCoef { double rb[3][4], rt[2][4], l0[3]; };
+struct DerTables;
+void infrared_build_tables(const DerTables &g, std::vector<double> &tab, InfraredCoef &C);
+hipError_t launch_infrared_y(const double *l, double *hs, double *scr1, double *scr2, const double *tab, const InfraredCoef &C, double kappa,
+                             double flux_top, double flux_bottom, int nx, int ny, int nz, hipStream_t st);
+
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 
 #include "kernels.hpp"
@@ -732,6 +733,49 @@ hipError_t launch_body_force(const BodyForce &F, double *const *hq, const double
     ProfScope ps("k_body_force", st, 8.0 * (double)n * (nread + 2 * nh));
     if (vec) body_force_launch<2>(cor, bod, A, (unsigned)(nx / 2), (unsigned)ny, (unsigned)(n / 2), st);
     else body_force_launch<1>(cor, bod, A, (unsigned)nx, (unsigned)ny, (unsigned)n, st);
+    return CHECK_LAUNCH();
+}
+
+// THERMO_AIRWATER_LINEAR (src/thermodynamics/thermo_airwater.f90:483-516), the diagnostic liquid of FI_DIAGNOSTIC (physics/fi_diagnostic.f90:44-47):
+// xi = 1 + p1 s1 [+ p2 s2]; SMOOTH = false (|pd| < small_wp): l = max(xi, 0); SMOOTH: l = pd log(exp(rd xi) + 1) with rd = 1 / pd formed first
+// (the reference's dummy2).  Unfused multiplies and adds in the reference's order; nothing beyond the reference's expression: exp overflows to
+// infinity where the reference's does (xi / pd > 709.78), and l is then infinite as there.  V as k_body_force.
+template <int V, bool TWO, bool SMOOTH>
+__global__ void __launch_bounds__(256) k_airwater_linear(double *__restrict__ l, const double *__restrict__ s1, const double *__restrict__ s2, double p1,
+                                                         double p2, double pd, double rd, unsigned npts) {
+    const unsigned stride = gridDim.x * blockDim.x;
+    for (unsigned p = blockIdx.x * blockDim.x + threadIdx.x; p < npts; p += stride) {
+        const BfVec<V> a = bf_load<V>(s1, p);
+        BfVec<V> xi;
+        for (int v = 0; v < V; ++v) xi.v[v] = bf_add(1.0, bf_mul(p1, a.v[v]));
+        if constexpr (TWO) {
+            const BfVec<V> b = bf_load<V>(s2, p);
+            for (int v = 0; v < V; ++v) xi.v[v] = bf_add(xi.v[v], bf_mul(p2, b.v[v]));
+        }
+        for (int v = 0; v < V; ++v) {
+            if constexpr (SMOOTH) xi.v[v] = bf_mul(pd, log(bf_add(exp(bf_mul(rd, xi.v[v])), 1.0)));
+            else xi.v[v] = fmax(xi.v[v], 0.0);
+        }
+        bf_store<V>(l, p, xi);
+    }
+}
+template <int V>
+static void airwater_launch(bool two, bool smooth, double *l, const double *s1, const double *s2, double p1, double p2, double pd, unsigned npts,
+                            hipStream_t st) {
+    const dim3 grid(pw_grid(npts)), block(256);
+    const double rd = smooth ? 1.0 / pd : 0.0;
+    if (two && smooth) hipLaunchKernelGGL((k_airwater_linear<V, true, true>), grid, block, 0, st, l, s1, s2, p1, p2, pd, rd, npts);
+    else if (two) hipLaunchKernelGGL((k_airwater_linear<V, true, false>), grid, block, 0, st, l, s1, s2, p1, p2, pd, rd, npts);
+    else if (smooth) hipLaunchKernelGGL((k_airwater_linear<V, false, true>), grid, block, 0, st, l, s1, s2, p1, p2, pd, rd, npts);
+    else hipLaunchKernelGGL((k_airwater_linear<V, false, false>), grid, block, 0, st, l, s1, s2, p1, p2, pd, rd, npts);
+}
+hipError_t launch_airwater_linear(double *l, const double *s1, const double *s2, int ns, double p1, double p2, double pd, long long n, hipStream_t st) {
+    if (!l || !s1 || ns < 1 || (ns > 1 && !s2) || n < 1 || n > 0x7fffffffLL) return hipErrorInvalidValue;
+    const bool two = ns > 1, smooth = !(std::fabs(pd) < 1.0e-20);      // small_wp
+    const bool vec = (n & 1) == 0 && ((uintptr_t)l & 15) == 0 && ((uintptr_t)s1 & 15) == 0 && (!two || ((uintptr_t)s2 & 15) == 0);
+    ProfScope ps("k_airwater_linear", st, 8.0 * (double)n * (two ? 3 : 2));
+    if (vec) airwater_launch<2>(two, smooth, l, s1, s2, p1, p2, pd, (unsigned)(n / 2), st);
+    else airwater_launch<1>(two, smooth, l, s1, s2, p1, p2, pd, (unsigned)n, st);
     return CHECK_LAUNCH();
 }
 

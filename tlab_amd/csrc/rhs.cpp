@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "driver_common.hpp"
+#include "int1_generic.hpp"
 #include "kernels.hpp"
 #include "monitor.hpp"
 #include "plan.hpp"
@@ -60,6 +61,13 @@ struct tlab_dns {
     // the buoyancy function subtracts (or starts from), made from bbackground when it is set
     tlab::BodyForce force;
     double *bprof = nullptr;
+    // [Thermodynamics] Mixture (tlab_dns_set_mixture): with one set, s carries inb_scal_array = nscal + 1 arrays, the last the diagnostic liquid
+    int mixture = TLAB_MIXT_NONE;
+    std::vector<double> thermo_param;
+    // [Infrared] (tlab_dns_set_infrared): the gray-liquid heating of TLab_Sources_Scal on scalar ir.scalar (1-based); tab: the shared coefficients of
+    // the lambda = 0 integral system of the y plan on the device, built when the term is first switched on
+    struct Infrared { int type = TLAB_IR_NONE, scalar = 0; double kappa = 0.0, flux_top = 0.0, flux_bottom = 0.0; double *tab = nullptr; tlab::InfraredCoef C{}; } ir;
+    int scal_arrays() const { return nscal + (mixture != TLAB_MIXT_NONE ? 1 : 0); }
     unsigned long anel_version = 0;                // change counter of the operator state these mirror (follow_anelastic)
     bool anel_owner = false;                       // this driver switched the operator state on (tlab_dns_set_anelastic): it goes with the driver
     ~tlab_dns() {
@@ -76,6 +84,7 @@ struct tlab_dns {
         for (NeuW &n : neuw) if (n.w) (void)hipFree(n.w);
         if (wall_planes) (void)hipFree(wall_planes);
         if (bprof) (void)hipFree(bprof);
+        if (ir.tab) (void)hipFree(ir.tab);
         for (auto &g : buff)
             for (BufferBlock &b : g) free_block(b, false);
     }
@@ -152,6 +161,7 @@ bool neumann_weights(tlab_dns *d, int ibc) {
 
 long long tlab_internal_dns_points(tlab_dns_t d) { return d ? (long long)d->nx * d->ny * d->nz : 0; }
 int tlab_internal_dns_nscal(tlab_dns_t d) { return d ? d->nscal : 0; }
+int tlab_internal_dns_scal_arrays(tlab_dns_t d) { return d ? d->scal_arrays() : 0; }
 bool tlab_internal_dns_has_bounds(tlab_dns_t d) { return d && d->bounds.any(); }
 bool tlab_internal_dns_has_flow_zones(tlab_dns_t d) { return d && (d->buff[0][0].size > 0 || d->buff[0][1].size > 0); }
 bool tlab_internal_dns_has_scal_zones(tlab_dns_t d) { return d && d->nscal > 0 && (d->buff[1][0].size > 0 || d->buff[1][1].size > 0); }
@@ -306,6 +316,26 @@ static void body_force(tlab_dns_t d, double *const *q, double *const *s, double 
     hk(launch_body_force(d->force, hq, q, s, d->bprof, d->nx, d->ny, d->nz, st), "body force");
 }
 
+// FI_DIAGNOSTIC (physics/fi_diagnostic.f90:44-47), linear thermodynamics: the liquid s[nscal] from the prognostic scalars
+static void diagnostic(tlab_dns_t d, double *const *s, hipStream_t st) {
+    if (d->mixture != TLAB_MIXT_AIRWATERLINEAR) return;
+    const int ns = d->nscal;
+    if (!s[ns] || !s[0] || (ns > 1 && !s[1])) throw Fail(TLAB_EINVAL, "FI_DIAGNOSTIC: null array (with a mixture s holds nscal + 1 arrays, the last the liquid)");
+    hk(launch_airwater_linear(s[ns], s[0], ns > 1 ? s[1] : nullptr, ns, d->thermo_param[0], ns > 1 ? d->thermo_param[1] : 0.0, d->thermo_param[ns],
+                              (long long)d->nx * d->ny * d->nz, st), "liquid");
+}
+
+// TLab_Sources_Scal (tlab_sources.f90:152-168) on (s, hs): the infrared heating of the liquid s[nscal] added to hs[scalar-1]; scr1, scr2: scratch fields
+static bool infrared_on(tlab_dns_t d) { return d->ir.type == TLAB_IR_GRAY_LIQUID && d->mixture != TLAB_MIXT_NONE; }
+static void sources_scal(tlab_dns_t d, double *const *s, double *const *hs, double *scr1, double *scr2, hipStream_t st) {
+    if (!infrared_on(d)) return;
+    if (d->rb) throw Fail(TLAB_EUNSUPPORTED, "[Infrared] in an anelastic run (Thermo_Anelastic_WEIGHT_INPLACE / _ADD of the source) is not built on the device");
+    const int is = d->ir.scalar - 1;
+    if (!s[d->nscal] || !hs[is] || !scr1 || !scr2) throw Fail(TLAB_EINVAL, "TLab_Sources_Scal: null array (liquid, tendency or scratch)");
+    hk(launch_infrared_y(s[d->nscal], hs[is], scr1, scr2, d->ir.tab, d->ir.C, d->ir.kappa, d->ir.flux_top, d->ir.flux_bottom, d->nx, d->ny, d->nz, st),
+       "infrared");
+}
+
 // tail: what follows the RHS in this substep (SubstepTail); NULL: the RHS on its own -- no update, no scalar zones, no forces
 static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs,
                      double *const *txc, const SubstepTail *tail) {
@@ -375,6 +405,9 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     static const bool finish_off = [] { const char *e = getenv("TLAB_SCALAR_FINISH"); return e && atoi(e) == 0; }();
     // TLab_Sources_Flow runs before the RHS in the substep (time.f90:610-612), never in the RHS on its own
     const bool forces = tail && tail->forces && d->force.any();
+    // ... and so does TLab_Sources_Scal (:611): the launch goes where hs holds a valid partial sum and the scalars are not finished yet, which is the
+    // slot of the body forces on every route; tmp8, tmp9 are free there (the literal Burgers sums are done, the pressure step has not begun)
+    const bool scal_src = tail && tail->scal_sources && infrared_on(d);
     const bool zone_flow = buffer_any(d, 0), zone_scal = tail && tail->scal_zones && d->nscal > 0 && buffer_any(d, 1);
     bool finish_scal = !finish_off && batched && !literal && tail && d->nscal > 0 && tlab_internal_burgers_can_finish(1, gx, nx, ny, nz);
     // Neumann scalars can ride too where the fused Neumann tail below applies: the epilogue finishes their interior with zero wall tendencies, and the
@@ -474,6 +507,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             // the body forces share the slot: every tendency holds a valid partial sum, q and s are those from before the update, and the forcing
             // of the pressure and the wall planes of hq2 are formed later, so the force is projected.  Summed in another order: rounding only.
             if (forces && &L == &plan[1]) body_force(d, q, s, hq, st);
+            if (scal_src && &L == &plan[1]) sources_scal(d, s, hs, tmp8, tmp9, st);
         }
     } else if (batched) {
         const int order_xyz[3] = {1, 2, 3}, order_zyx[3] = {3, 2, 1};
@@ -501,6 +535,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
             if (zone_flow && k == 0) buffer_relax(d, 0, q, hq, st);      // after the first launch (it may overwrite), before the last (it may differentiate)
             if (zone_epi && k == 0) buffer_relax(d, 1, s, hs, st);
             if (forces && k == 0) body_force(d, q, s, hq, st);
+            if (scal_src && k == 0) sources_scal(d, s, hs, tmp8, tmp9, st);
         }
     }
     for (size_t e = 0; e < eqs.size() && !batched; ++e) {
@@ -521,6 +556,7 @@ static void rhs_impl(tlab_dns_t d, double dte, double *const *q, double *const *
     }
     if (zone_flow && !batched) buffer_relax(d, 0, q, hq, st);      // BOUNDARY_BUFFER_RELAX_FLOW in the reference's place (:170-172)
     if (forces && !batched) body_force(d, q, s, hq, st);           // (the tendencies were zeroed or accumulated above; the forcing follows)
+    if (scal_src && !batched) sources_scal(d, s, hs, tmp8, tmp9, st);
     // the tail of the scalars under a buffer zone, once the wall planes of hs hold their BC values: BOUNDARY_BUFFER_RELAX_SCAL, s += dte hs, bounds, hs *= kco
     auto zone_scal_tail = [&] {
         buffer_relax(d, 1, s, hs, st);
@@ -799,13 +835,19 @@ int tlab_rhs_global_incompressible_1(tlab_dns_t d, double dte, double *const *q,
 }
 
 void tlab_internal_dns_substep(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
-                               const SubstepTail &tail) { rhs_impl(d, dte, q, s, hq, hs, txc, &tail); }
+                               const SubstepTail &tail) {
+    // the reference computes the liquid from the unclipped scalars and clips afterwards (time.f90:248-250); the epilogues here clip first
+    if (d->mixture != TLAB_MIXT_NONE && tail.bounds && tail.bounds->any())
+        throw Fail(TLAB_EUNSUPPORTED, "a mixture (diagnostic liquid) together with active scalar bounds: FI_DIAGNOSTIC would see the clipped scalars, the reference's sees the unclipped ones");
+    rhs_impl(d, dte, q, s, hq, hs, txc, &tail);
+    diagnostic(d, s, tlab_current_stream());      // FI_DIAGNOSTIC after s += dte hs (time.f90:248)
+}
 
 int tlab_time_substep_incompressible_explicit(tlab_dns_t d, double dte, double kco, int scale_tendencies, double *const *q,
                                               double *const *s, double *const *hq, double *const *hs, double *const *txc) {
     return catch_fail([&] {
         if (!d || !q || !hq || !txc || (d->nscal > 0 && (!s || !hs)) || dte <= 0.0) throw Fail(TLAB_EINVAL, "tlab_time_substep_incompressible_explicit: bad arguments");
-        tlab_internal_dns_substep(d, dte, q, s, hq, hs, txc, {kco, scale_tendencies, &d->bounds, true, true});
+        tlab_internal_dns_substep(d, dte, q, s, hq, hs, txc, {kco, scale_tendencies, &d->bounds, true, true, true});
     }, TLAB_EINVAL);
 }
 
@@ -1068,6 +1110,7 @@ int tlab_dns_place_arrays(tlab_dns_t d, int npool, double *const *pool, const do
                           int *assignment, double *report) {
     return catch_fail([&] {
         if (!d || !pool || !assignment || dtime <= 0.0 || random_trials < 0) throw Fail(TLAB_EINVAL, "tlab_dns_place_arrays: bad arguments");
+        if (d->mixture != TLAB_MIXT_NONE) throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_place_arrays: the search places nscal scalar arrays; a driver with a mixture holds the liquid as well");
         const int ns = d->nscal, nroles = 2 * (3 + ns) + 9;
         if (npool < nroles) throw Fail(TLAB_EINVAL, "tlab_dns_place_arrays: the pool must hold at least 2 (3 + nscal) + 9 arrays");
         for (int i = 0; i < npool; ++i) {
@@ -1146,6 +1189,7 @@ int tlab_dns_place_blocks(tlab_dns_t d, int ncand, double *const *cand_q, double
     return catch_fail([&] {
         if (!d || ncand < 1 || !cand_q || !cand_hq || !cand_txc || !choice || dtime <= 0.0 || random_trials < 0)
             throw Fail(TLAB_EINVAL, "tlab_dns_place_blocks: bad arguments");
+        if (d->mixture != TLAB_MIXT_NONE) throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_place_blocks: the search places blocks of nscal scalar arrays; a driver with a mixture holds the liquid as well");
         const int ns = d->nscal;
         const long long n = (long long)d->nx * d->ny * d->nz;
         if (ns > 0 && (!cand_s || !cand_hs)) throw Fail(TLAB_EINVAL, "tlab_dns_place_blocks: candidates for s, hs are missing");
@@ -1369,8 +1413,10 @@ int tlab_dns_set_buoyancy(tlab_dns_t d, int type, const double *vector, int nsca
             if (type == TLAB_BOD_HOMOGENEOUS) {
                 F.bod = 1; F.c[0] = par(0);
             } else if (type == TLAB_BOD_LINEAR) {
-                if (nscalars > d->nscal)
+                if (d->mixture == TLAB_MIXT_NONE && nscalars > d->nscal)
                     throw Fail(TLAB_EUNSUPPORTED, "[BodyForce] linear: the buoyancy reads scalar arrays beyond the prognostic scalars (diagnostic arrays are not held on the device)");
+                if (nscalars > d->scal_arrays())
+                    throw Fail(TLAB_EUNSUPPORTED, "[BodyForce] linear: the buoyancy reads scalar arrays beyond the liquid (inb_scal_array = nscal + 1)");
                 const double c0 = par(inb_scal_array);
                 if (nscalars >= 1 && nscalars <= 3) {      // gravity.f90:255-277
                     F.bod = 2; F.ns = nscalars;
@@ -1419,6 +1465,79 @@ int tlab_dns_sources_flow(tlab_dns_t d, double *const *q, double *const *s, doub
     });
 }
 
+// ---- [Thermodynamics] Mixture and [Infrared]: FI_DIAGNOSTIC and TLab_Sources_Scal ----
+int tlab_dns_set_mixture(tlab_dns_t d, int mixture, const double *thermo_param, int nparam) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (mixture != TLAB_MIXT_NONE && mixture != TLAB_MIXT_AIRWATERLINEAR)
+            throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_set_mixture: only AirWaterLinear (12) and none (0) are built on the device");
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_mixture: null handle");
+        if (mixture == TLAB_MIXT_NONE) {
+            if (d->force.bod == 2 || d->force.bod == 3)
+                for (int i = 0; i < d->force.ns; ++i)
+                    if (d->force.sidx[i] >= d->nscal) throw Fail(TLAB_EINVAL, "tlab_dns_set_mixture: the buoyancy set on this driver reads the liquid; switch it off first");
+            d->mixture = TLAB_MIXT_NONE;
+            d->thermo_param.clear();
+            d->ir.type = TLAB_IR_NONE;      // (the infrared term reads the liquid: it goes with the mixture)
+            return;
+        }
+        if (d->nscal < 1) throw Fail(TLAB_EINVAL, "tlab_dns_set_mixture: AirWaterLinear on a driver without scalars");
+        if (!thermo_param || nparam < d->nscal + 1) throw Fail(TLAB_EINVAL, "tlab_dns_set_mixture: thermo_param needs nscal + 1 values");
+        if (!all_finite(thermo_param, nparam)) throw Fail(TLAB_EINVAL, "tlab_dns_set_mixture: NaN / infinite values in thermo_param");
+        d->mixture = mixture;
+        d->thermo_param.assign(thermo_param, thermo_param + nparam);
+    }, TLAB_EINVAL);
+}
+
+int tlab_dns_diagnostic(tlab_dns_t d, double *const *s) {
+    return guarded([&] {
+        if (!d || (d->scal_arrays() > 0 && !s)) throw Fail(TLAB_EINVAL, "tlab_dns_diagnostic: bad arguments");
+        diagnostic(d, s, tlab_current_stream());
+    });
+}
+
+int tlab_dns_set_infrared(tlab_dns_t d, int type, int scalar, double kappa, double flux_top, double flux_bottom) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (type == 2 || type == 3)
+            throw Fail(TLAB_EUNSUPPORTED, "[Infrared] gray and band types need a temperature (the reference derives one for anelastic runs only): not built on the device");
+        if (type != TLAB_IR_NONE && type != TLAB_IR_GRAY_LIQUID) throw Fail(TLAB_EINVAL, "tlab_dns_set_infrared: unknown type");
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_infrared: null handle");
+        if (type == TLAB_IR_NONE) { d->ir.type = TLAB_IR_NONE; return; }
+        if (!std::isfinite(kappa) || !std::isfinite(flux_top) || !std::isfinite(flux_bottom)) throw Fail(TLAB_EINVAL, "tlab_dns_set_infrared: NaN / infinite values");
+        if (d->mixture == TLAB_MIXT_NONE) throw Fail(TLAB_EINVAL, "[Infrared] gray liquid needs a mixture with a liquid field (tlab_dns_set_mixture); the reference stops there");
+        if (scalar < 1 || scalar > d->nscal) throw Fail(TLAB_EINVAL, "tlab_dns_set_infrared: the term acts on one of the scalars 1..nscal");
+        follow_anelastic(d);
+        if (d->rb) throw Fail(TLAB_EUNSUPPORTED, "[Infrared] in an anelastic run (Thermo_Anelastic_WEIGHT_INPLACE / _ADD of the source) is not built on the device");
+        const tlab::DerTables &g = d->g[1]->t.der1;
+        if (tlab::int1_generic_applies(g) || g.ndl != 3 || g.ndr != 5 || g.periodic)
+            throw Fail(TLAB_EUNSUPPORTED, "[Infrared]: the first-order integral of this y plan is not the pentadiagonal system of CompactJacobian6");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
+        if (!d->ir.tab) {
+            std::vector<double> tab;
+            tlab::InfraredCoef C;
+            try {
+                tlab::infrared_build_tables(g, tab, C);
+            } catch (const std::exception &e) {
+                throw Fail(TLAB_EUNSUPPORTED, std::string("[Infrared]: ") + e.what());
+            }
+            double *p = nullptr;
+            hk(hipMalloc((void **)&p, tab.size() * sizeof(double)), "hipMalloc");
+            if (hipMemcpy(p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); throw Fail(TLAB_EHIP, "hipMemcpy"); }
+            d->ir.tab = p;
+            d->ir.C = C;
+        }
+        d->ir.type = type; d->ir.scalar = scalar; d->ir.kappa = kappa; d->ir.flux_top = flux_top; d->ir.flux_bottom = flux_bottom;
+    }, TLAB_EINVAL);
+}
+
+int tlab_dns_sources_scal(tlab_dns_t d, double *const *s, double *const *hs, double *const *txc) {
+    return guarded([&] {
+        if (!d || !txc || (d->nscal > 0 && (!s || !hs))) throw Fail(TLAB_EINVAL, "tlab_dns_sources_scal: bad arguments");
+        sources_scal(d, s, hs, txc[0], txc[1], tlab_current_stream());
+    });
+}
+
 long long tlab_dns_info(tlab_dns_t d, int what) {
     if (!d) return -1;
     switch (what) {
@@ -1427,6 +1546,7 @@ long long tlab_dns_info(tlab_dns_t d, int what) {
     case 2: return d->nz;
     case 3: return d->nscal;
     case 4: return (long long)d->nx * d->ny * d->nz;
+    case 5: return d->scal_arrays();
     default: return -1;
     }
 }

@@ -106,6 +106,10 @@ CORIOLIS_TYPES = {"none": 0, "explicit": 4, "normalized": 12}
 BUOYANCY_TYPES = {"none": 0, "explicit": 4, "homogeneous": 5, "linear": 6, "bilinear": 7, "quadratic": 8, "normalizedmean": 9, "subtractmean": 10}
 
 
+MIXTURES = {"none": 0, "airwaterlinear": 12}                                   # MIXT_TYPE_* of the reference
+INFRARED_TYPES = {"none": 0, "grayliquid": 1, "bulk1dlocal": 1, "gray": 2, "band": 3}
+
+
 def body_force_args(nscal, coriolis, buoyancy):
     """The arguments of tlab_*_set_coriolis and tlab_*_set_buoyancy (after the handle) from the small dicts or tuples of set_body_forces."""
     dp = ctypes.POINTER(ctypes.c_double)
@@ -204,6 +208,7 @@ class Dns:
                                      self.nx, self.ny, self.nz, self.nscal, self.visc,
                                      sc.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "tlab_dns_create")
         self._ptrs = None
+        self.liquid = None                                              # the diagnostic array s(:, inb_scal_array) of a mixture (set_mixture)
 
     def set_bcs(self, velocity_jmin="noslip", velocity_jmax="noslip", scalar_jmin="dirichlet", scalar_jmax="dirichlet"):
         """Wall boundary conditions in y by the reference's dns.ini keywords ([BoundaryConditions], boundary_bcs.f90:102-190)."""
@@ -333,6 +338,39 @@ class Dns:
         q, s, hq, _, _ = self._arrays()
         check(load().tlab_dns_sources_flow(self._h, q, s, hq), "tlab_dns_sources_flow")
 
+    def set_mixture(self, name="airwaterlinear", parameters=()):
+        """[Thermodynamics] Type = Linear, Mixture = AirWaterLinear with thermo_param = parameters (at least nscal + 1 values), or "none".  With a
+        mixture the driver holds the diagnostic liquid as Dns.liquid (inb_scal_array = nscal + 1; Dns.s keeps its nscal tensors): call
+        FI_DIAGNOSTIC() once the scalars are loaded, every substep refreshes it after its update.  Other mixtures are refused by the library."""
+        import torch
+        code = MIXTURES.get(name.strip().lower()) if isinstance(name, str) else int(name)
+        if code is None:
+            raise TlabError("Thermodynamics.Mixture: one of %s" % ", ".join(MIXTURES))
+        par = np.ascontiguousarray(parameters, dtype=np.float64).reshape(-1)
+        dp = ctypes.POINTER(ctypes.c_double)
+        check(load().tlab_dns_set_mixture(self._h, code, par.ctypes.data_as(dp) if len(par) else None, len(par)), "tlab_dns_set_mixture")
+        self.liquid = torch.zeros(self.n, dtype=torch.float64, device=self.q[0].device) if code != 0 else None
+        self._ptrs = None
+
+    def FI_DIAGNOSTIC(self):
+        """physics/fi_diagnostic.f90:44-47: the liquid from the prognostic scalars (THERMO_AIRWATER_LINEAR)."""
+        _use_torch_stream()
+        check(load().tlab_dns_diagnostic(self._h, self._arrays()[1]), "tlab_dns_diagnostic")
+
+    def set_infrared(self, type="grayliquid", scalar=1, kappa=0.0, flux_top=0.0, flux_bottom=0.0):
+        """[Infrared] as Radiation_Initialize leaves it: type "none" | "grayliquid" ("bulk1dlocal" is the same), the 1-based scalar the heating acts
+        on, kappa(1,1), auxiliar(1) (downward flux at the top), auxiliar(2) (upward flux at the bottom).  The absorbing field is the liquid."""
+        code = INFRARED_TYPES.get(type.strip().lower()) if isinstance(type, str) else int(type)
+        if code is None:
+            raise TlabError("Infrared.Type: one of %s" % ", ".join(INFRARED_TYPES))
+        check(load().tlab_dns_set_infrared(self._h, code, int(scalar), float(kappa), float(flux_top), float(flux_bottom)), "tlab_dns_set_infrared")
+
+    def sources_scal(self):
+        """TLab_Sources_Scal on (s, hs) as an operator of its own: hs[scalar-1] += the infrared heating; txc[0], txc[1] are scratch."""
+        _use_torch_stream()
+        _, s, _, hs, txc = self._arrays()
+        check(load().tlab_dns_sources_scal(self._h, s, hs, txc), "tlab_dns_sources_scal")
+
     def set_fusion(self, on):
         """on (default): pointwise sums folded into the operator kernels; off: the reference's literal sequence."""
         check(load().tlab_dns_set_fusion(self._h, int(bool(on))), "tlab_dns_set_fusion")
@@ -344,7 +382,8 @@ class Dns:
                 for i, t in enumerate(ts):
                     a[i] = t.data_ptr()
                 return a
-            self._ptrs = tuple(arr(t) for t in (self.q, self.s, self.hq, self.hs, self.txc))
+            s = self.s + ([self.liquid] if self.liquid is not None else [])      # s(isize_field, inb_scal_array): the liquid behind the scalars
+            self._ptrs = tuple(arr(t) for t in (self.q, s, self.hq, self.hs, self.txc))
         return self._ptrs
 
     def RHS_GLOBAL_INCOMPRESSIBLE_1(self, dte):

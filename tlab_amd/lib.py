@@ -89,6 +89,10 @@ SIGNATURES = {
     "tlab_dns_set_coriolis": (c_int, [c_vp, c_int, _dp, _dp]),
     "tlab_dns_set_buoyancy": (c_int, [c_vp, c_int, _dp, c_int, _dp, c_int, c_int, _dp]),
     "tlab_dns_sources_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
+    "tlab_dns_set_mixture": (c_int, [c_vp, c_int, _dp, c_int]),
+    "tlab_dns_diagnostic": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "tlab_dns_set_infrared": (c_int, [c_vp, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "tlab_dns_sources_scal": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "tlab_dns_info": (ctypes.c_longlong, [c_vp, c_int]),
     "tlab_deferred_sources_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "tlab_deferred_sources_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
