@@ -441,6 +441,61 @@ int tlab_dns_diagnostic(tlab_dns_t d, double *const *s);
 int tlab_dns_set_infrared(tlab_dns_t d, int type, int scalar, double kappa, double flux_top, double flux_bottom);
 int tlab_dns_sources_scal(tlab_dns_t d, double *const *s, double *const *hs, double *const *txc);
 long long tlab_dns_info(tlab_dns_t d, int what);      /* 0 nx, 1 ny, 2 nz, 3 nscal, 4 points of a field, 5 inb_scal_array (arrays in s); -1: null handle or unknown code */
+/* Lagrangian particles of the single-domain driver: [Particles] Type = Tracer | Inertia (examples/Case51-53; Case54, 55 use BilinearCloudFour, which is refused), as the serial branch of the reference
+ * does them.  The host's particle arrays live in DEVICE memory: l_q and l_hq are HOST arrays of inb_part DEVICE pointers, the columns
+ * l_q(isize_part, is) as q and s are passed (inb_part = 3 for tracers: position; 6 for inertial particles: position, velocity); nodes is
+ * l_g%nodes (32-bit, 1-based: the y node below the particle), tags is l_g%tags (64-bit).  np is l_g%np, at most 2^31 - 1.  Every entry runs on the
+ * library's stream, after a recorded deferred substep.
+ *   tlab_dns_set_particles: type TLAB_PART_* (part%type), bcs TLAB_PART_BCS_* (part_bcs; bcs < 0: the reference's default for the type, none for
+ *     tracers, specular for inertial particles, particle_procs.f90:65-67), stokes and settling of [Parameters].  TLAB_PART_NONE takes the particles
+ *     off the driver again and reads nothing else.  The nodes of the driver's y plan go into a device table here.  TLAB_EUNSUPPORTED, nothing stored:
+ *     types 4, 5, 6 (the bilinear cloud droplets need Laplacians, FI_GRADIENT and the radiation at the particle) and an anelastic driver.
+ *     TLAB_EINVAL, nothing stored: unknown codes, inertial particles with stokes <= 0, NaN or infinite values, a null handle, plans without nodes.
+ *     The arguments are checked before the handle.  A driver on which it was never called launches exactly the kernels of before.
+ *   tlab_dns_particle_locate = LOCATE_Y (utils/locate_y.f90) on its own: nodes(p) from y_part(p) (DEVICE arrays) by the reference's own bisection,
+ *     which decides the answer for a particle on a node or outside the grid; always 1 <= nodes(p) <= ny - 1.  The host calls it once after
+ *     Particle_Initialize_Fields or a restart.
+ *   tlab_dns_substep_particle = TIME_SUBSTEP_PARTICLE (tools/dns/time.f90:906-1070, serial branch) and the scaling of l_hq (:300-304) in ONE launch
+ *     (k_particle_substep, csrc/particles.hip), one thread per particle:
+ *       1. u, v, w at the particle (FIELD_TO_PARTICLE, particle_interpolate.f90:186-332): trilinear from the eight corners of the cell
+ *          (floor(x nx / scale_x), nodes(p), floor(z nz / scale_z)), the reference's expression left to right.  The last cell of a periodic direction
+ *          takes index 1 as its upper corner (no halo arrays, no particle sorting: same values); a particle exactly at x = scale takes f(nx) with
+ *          fraction 0, as in the reference.  nz = 1: the bilinear branch, z is neither interpolated nor wrapped.
+ *       2. RHS_PART_1 (rhs_part_1.f90): tracers l_hq(1:3) += (u, v, w); inertial particles l_hq(1:3) += l_q(4:6), l_hq(4:6) += (1/stokes)
+ *          ((u, v, w) - l_q(4:6)), l_hq(5) -= settling/stokes (the reference's l_txc is three registers).
+ *       3. l_q(is) += dte l_hq(is), is = 1..inb_part.
+ *       4. periodic wraps in x and z: > x(1) + scale subtracts scale, < x(1) adds it, one wrap at most.
+ *       5. the walls in y: none; stick (y is set onto the wall); specular (y is reflected and l_q(5) changes sign -- a tracer has no fifth
+ *          column, so specular only reflects its position).
+ *       6. nodes(p) = LOCATE_Y of the new y.
+ *       7. l_hq(is) *= kco when scale_tendencies != 0 (every substep but the last).
+ *     Unfused multiplies and adds in the reference's order: the numpy restatement (tests/particles_oracle.py) gives the same bits.  It reads q (HOST
+ *     array of the 3 DEVICE velocity pointers) and writes no field: call it BEFORE the flow substep of the same stage, as time.f90:231-233 does.
+ *     Positions the host hands over are trusted to lie in the box, but no position or node number can take a load outside the fields (the cell
+ *     indices are clamped).  TLAB_EINVAL: a driver without particles, np < 0 or > 2^31 - 1, null pointers with np > 0, NaN dte or kco.  np = 0
+ *     succeeds without a launch.
+ *   tlab_dns_particle_sort: permutes l_q, l_hq, nodes and tags together so that particles are ordered by the cell that holds them, key
+ *     (k0 ny + j0) nx + i0 of the current positions and nodes (the whole cell number: the 64 particles of a wave then lie along an x row, whose
+ *     corners are contiguous, and a 32-bit key costs the radix sort no more passes coarse than fine); equal keys keep their order.  The reference
+ *     itself permutes its particles every substep (particle_interpolate.f90:337-411) and carries tags for identity: order is not part of the state,
+ *     and a substep after the sort gives every particle (by tag) the bits it would have got unsorted.  rocPRIM device radix sort of (key, index)
+ *     pairs, then one gather per array through the scratch.  scratch: DEVICE memory on a 256-byte boundary.  The size query is a call with
+ *     scratch = NULL: *scratch_needed receives the bytes for np particles and nothing is sorted (scratch_needed may be NULL otherwise).  Scratch that
+ *     is too small or misaligned: TLAB_EINVAL, the arrays untouched.  The substep never sorts on its own: the host calls this every so many steps.
+ * Not built: the slab and pencil drivers (migration between ranks), particle restart files (io_particle.f90: IO stays on the host),
+ * PARTICLE_TO_FIELD, the particle pdfs and trajectories, residence times. */
+#define TLAB_PART_NONE 0      /* PART_TYPE_*: particle_vars.f90:8-14 */
+#define TLAB_PART_TRACER 1
+#define TLAB_PART_INERTIA 2
+#define TLAB_PART_BCS_NONE 0  /* PART_BCS_*: particle_vars.f90:28-30 */
+#define TLAB_PART_BCS_STICK 1
+#define TLAB_PART_BCS_SPECULAR 2
+int tlab_dns_set_particles(tlab_dns_t d, int type, int bcs, double stokes, double settling);
+int tlab_dns_particle_locate(tlab_dns_t d, long long np, const double *y_part, int *nodes);
+int tlab_dns_substep_particle(tlab_dns_t d, double dte, double kco, int scale_tendencies, long long np, double *const *q, double *const *l_q,
+                              double *const *l_hq, int *nodes);
+int tlab_dns_particle_sort(tlab_dns_t d, long long np, double *const *l_q, double *const *l_hq, int *nodes, long long *tags, void *scratch,
+                           long long scratch_bytes, long long *scratch_needed);
 /* Start of a Runge-Kutta step: TIME_RUNGEKUTTA sets hq = 0, hs = 0 there (tools/dns/time.f90:212-216).  Instead of filling the arrays,
  * tell the driver: the next tlab_rhs_global_incompressible_1 / tlab_time_substep_incompressible_explicit treats them as zero (its first
  * operator launch overwrites instead of accumulating), whatever they contain. */

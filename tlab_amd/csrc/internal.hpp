@@ -12,6 +12,7 @@
 
 namespace tlab {
 struct SubstepTail;      // driver_common.hpp
+struct ParticleState;    // particles.hip
 }
 
 // ---- capi.cpp ----
@@ -110,6 +111,19 @@ int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, co
 // the wall-plane weights of a Neumann variant for the other drivers of the library (slab.cpp): 1 and (w = [2][K] device weights, K) when available
 int tlab_internal_dns_neumann_weights(tlab_dns_t d, int ibc, const double **w, int *K);
 }
+
+// particles.hip: the box, the plans and the equations of a driver, and the slot in which the driver keeps the particle state particles.hip makes
+// (the driver frees it through tlab_internal_particles_free); throws tlab::Fail where the anelastic profiles of the operators do not fit the driver
+struct tlab_dns_grid {
+    int nx, ny, nz;
+    tlab_fdm_plan_t g[3];
+    bool anelastic;
+    tlab::ParticleState **particles;
+};
+void tlab_internal_dns_grid(tlab_dns_t d, tlab_dns_grid *out);
+
+// ---- particles.hip ----
+void tlab_internal_particles_free(tlab::ParticleState *p);
 
 // ---- slab.cpp, pencil.cpp ----
 // deferred.cpp: the arrays a decomposed driver is bound to (the ONE local rank of a Fortran / MPI host) and whether it holds scalar bounds of its own

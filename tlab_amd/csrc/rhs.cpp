@@ -67,6 +67,8 @@ struct tlab_dns {
     // [Infrared] (tlab_dns_set_infrared): the gray-liquid heating of TLab_Sources_Scal on scalar ir.scalar (1-based); tab: the shared coefficients of
     // the lambda = 0 integral system of the y plan on the device, built when the term is first switched on
     struct Infrared { int type = TLAB_IR_NONE, scalar = 0; double kappa = 0.0, flux_top = 0.0, flux_bottom = 0.0; double *tab = nullptr; tlab::InfraredCoef C{}; } ir;
+    // [Particles] (tlab_dns_set_particles): made and read by particles.hip, null without particles; no launch of the flow substep depends on it
+    tlab::ParticleState *particles = nullptr;
     int scal_arrays() const { return nscal + (mixture != TLAB_MIXT_NONE ? 1 : 0); }
     unsigned long anel_version = 0;                // change counter of the operator state these mirror (follow_anelastic)
     bool anel_owner = false;                       // this driver switched the operator state on (tlab_dns_set_anelastic): it goes with the driver
@@ -85,6 +87,7 @@ struct tlab_dns {
         if (wall_planes) (void)hipFree(wall_planes);
         if (bprof) (void)hipFree(bprof);
         if (ir.tab) (void)hipFree(ir.tab);
+        tlab_internal_particles_free(particles);
         for (auto &g : buff)
             for (BufferBlock &b : g) free_block(b, false);
     }
@@ -1590,6 +1593,11 @@ int tlab_pw_fill_wall_planes(double *f, double vb, double vt, int nx, int ny, in
 int tlab_pw_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz) { PW_GUARD(launch_set_wall_planes(f, pb, pt, nx, ny, nz, tlab_current_stream())) }
 
 }  // extern "C"
+
+void tlab_internal_dns_grid(tlab_dns_t d, tlab_dns_grid *out) {
+    follow_anelastic(d);
+    *out = {d->nx, d->ny, d->nz, {d->g[0], d->g[1], d->g[2]}, d->rb != nullptr, &d->particles};
+}
 
 int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi) {
     const tlab::ClipBounds c{lo, hi};

@@ -108,6 +108,8 @@ BUOYANCY_TYPES = {"none": 0, "explicit": 4, "homogeneous": 5, "linear": 6, "bili
 
 MIXTURES = {"none": 0, "airwaterlinear": 12}                                   # MIXT_TYPE_* of the reference
 INFRARED_TYPES = {"none": 0, "grayliquid": 1, "bulk1dlocal": 1, "gray": 2, "band": 3}
+PART_TYPES = {"none": 0, "tracer": 1, "inertia": 2, "bilinearcloudthree": 4, "bilinearcloudfour": 5, "tiniaone": 6}      # PART_TYPE_* of the reference
+PART_BCS = {"none": 0, "stick": 1, "specular": 2}
 
 
 def body_force_args(nscal, coriolis, buoyancy):
@@ -209,6 +211,10 @@ class Dns:
                                      sc.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "tlab_dns_create")
         self._ptrs = None
         self.liquid = None                                              # the diagnostic array s(:, inb_scal_array) of a mixture (set_mixture)
+        # [Particles] (set_particles): l_q, l_hq lists of device tensors (the columns), l_g%nodes (int32), l_g%tags (int64)
+        self.l_q = self.l_hq = self.l_nodes = self.l_tags = None
+        self.part_type, self.np = PART_TYPES["none"], 0
+        self._part_ptrs = self._part_scratch = None
 
     def set_bcs(self, velocity_jmin="noslip", velocity_jmax="noslip", scalar_jmin="dirichlet", scalar_jmax="dirichlet"):
         """Wall boundary conditions in y by the reference's dns.ini keywords ([BoundaryConditions], boundary_bcs.f90:102-190)."""
@@ -371,6 +377,64 @@ class Dns:
         _, s, _, hs, txc = self._arrays()
         check(load().tlab_dns_sources_scal(self._h, s, hs, txc), "tlab_dns_sources_scal")
 
+    def set_particles(self, type="tracer", number=0, bcs=None, stokes=0.0, settling=0.0):
+        """[Particles] Type = tracer | inertia with `number` particles (l_g%np), BoundaryCondition bcs = None (the reference's default for the type) |
+        "none" | "stick" | "specular", and stokes / settling of [Parameters].  Allocates l_q, l_hq (lists of inb_part device tensors, zero), l_nodes
+        (int32) and l_tags (int64, 1..np); the caller fills the positions (and velocities) and calls locate_particles() once.  "none" takes them away."""
+        import torch
+        code = PART_TYPES.get(type.strip().lower()) if isinstance(type, str) else int(type)
+        wall = -1 if bcs is None else (PART_BCS.get(bcs.strip().lower()) if isinstance(bcs, str) else int(bcs))
+        if code is None or wall is None:
+            raise TlabError("Particles.Type: one of %s; BoundaryCondition: one of %s" % (", ".join(PART_TYPES), ", ".join(PART_BCS)))
+        if int(number) < 0:
+            raise TlabError("set_particles: number < 0")
+        check(load().tlab_dns_set_particles(self._h, code, wall, float(stokes), float(settling)), "tlab_dns_set_particles")
+        self.part_type, self.np = code, int(number) if code else 0
+        self._part_ptrs = self._part_scratch = None
+        if code == 0:
+            self.l_q = self.l_hq = self.l_nodes = self.l_tags = None
+            return
+        dev, ncol = self.q[0].device, 6 if code == PART_TYPES["inertia"] else 3
+        m = max(self.np, 1)
+        self.l_q = [torch.zeros(m, dtype=torch.float64, device=dev)[:self.np] for _ in range(ncol)]
+        self.l_hq = [torch.zeros(m, dtype=torch.float64, device=dev)[:self.np] for _ in range(ncol)]
+        self.l_nodes = torch.ones(m, dtype=torch.int32, device=dev)[:self.np]
+        self.l_tags = torch.arange(1, m + 1, dtype=torch.int64, device=dev)[:self.np]
+
+    def _particle_arrays(self):
+        if self.l_q is None:
+            raise TlabError("no particles are set on this driver (set_particles)")
+        if self._part_ptrs is None:
+            arr = lambda ts: (c_vp * len(ts))(*[t.data_ptr() for t in ts])      # noqa: E731
+            self._part_ptrs = (arr(self.l_q), arr(self.l_hq))
+        return self._part_ptrs
+
+    def locate_particles(self):
+        """LOCATE_Y: l_nodes from the y positions l_q[1]."""
+        _use_torch_stream()
+        self._particle_arrays()
+        check(load().tlab_dns_particle_locate(self._h, self.np, self.l_q[1].data_ptr(), self.l_nodes.data_ptr()), "tlab_dns_particle_locate")
+
+    def TIME_SUBSTEP_PARTICLE(self, dte, kco=1.0, scale_tendencies=False):
+        """tools/dns/time.f90:906-1070 with the scaling of l_hq (:300-304); reads q, so it goes before the flow substep of the same stage."""
+        _use_torch_stream()
+        lq, lhq = self._particle_arrays()
+        check(load().tlab_dns_substep_particle(self._h, float(dte), float(kco), int(scale_tendencies), self.np, self._arrays()[0], lq, lhq,
+                                               self.l_nodes.data_ptr()), "tlab_dns_substep_particle")
+
+    def sort_particles(self):
+        """tlab_dns_particle_sort: l_q, l_hq, l_nodes, l_tags permuted together by cell (the scratch is kept for the next call)."""
+        import torch
+        _use_torch_stream()
+        lq, lhq = self._particle_arrays()
+        L = load()
+        need = ctypes.c_longlong(0)
+        check(L.tlab_dns_particle_sort(self._h, self.np, lq, lhq, None, None, None, 0, ctypes.byref(need)), "tlab_dns_particle_sort")
+        if self._part_scratch is None or self._part_scratch.numel() < need.value:
+            self._part_scratch = torch.empty(max(need.value, 1), dtype=torch.uint8, device=self.q[0].device)
+        check(L.tlab_dns_particle_sort(self._h, self.np, lq, lhq, self.l_nodes.data_ptr(), self.l_tags.data_ptr(), self._part_scratch.data_ptr(),
+                                       self._part_scratch.numel(), None), "tlab_dns_particle_sort")
+
     def set_fusion(self, on):
         """on (default): pointwise sums folded into the operator kernels; off: the reference's literal sequence."""
         check(load().tlab_dns_set_fusion(self._h, int(bool(on))), "tlab_dns_set_fusion")
@@ -455,6 +519,10 @@ class Dns:
     def begin_step(self):
         """hq = hs = 0 of TIME_RUNGEKUTTA (time.f90:212-216) without touching the arrays: the next substep overwrites them."""
         check(load().tlab_dns_begin_step(self._h), "tlab_dns_begin_step")
+        if self.l_hq is not None and self.np > 0:      # l_hq = 0 (time.f90:215): the particle substep accumulates onto it
+            _use_torch_stream()
+            for t in self.l_hq:
+                check(load().tlab_pw_fill(t.data_ptr(), 0.0, self.np), "tlab_pw_fill")
 
     def place_arrays(self, pool=40, random_trials=16, dtime=1e-3, seed=0):
         """tlab_dns_place_arrays: q, s, hq, hs, txc move to the allocations (out of a pool of `pool` fresh ones of the txc size) on which the substep runs
@@ -521,10 +589,13 @@ class Dns:
                 "seconds": time.perf_counter() - t0}
 
     def TIME_RUNGEKUTTA(self, dtime):
-        """One time step: hq = hs = 0, then rkm_endstep substeps (time.f90:212-298)."""
+        """One time step: hq = hs = 0 (and l_hq = 0), then rkm_endstep substeps, each with the particle substep first when particles are set
+        (time.f90:212-304)."""
         self.begin_step()
         for k in range(self.rkm_endstep):
             last = k == self.rkm_endstep - 1
+            if self.l_q is not None:
+                self.TIME_SUBSTEP_PARTICLE(dtime * self.kdt[k], 1.0 if last else self.kco[k], not last)
             self.TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT(dtime * self.kdt[k], 1.0 if last else self.kco[k], not last)
 
     def __del__(self):

@@ -94,6 +94,11 @@ SIGNATURES = {
     "tlab_dns_set_infrared": (c_int, [c_vp, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "tlab_dns_sources_scal": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "tlab_dns_info": (ctypes.c_longlong, [c_vp, c_int]),
+    "tlab_dns_set_particles": (c_int, [c_vp, c_int, c_int, c_dbl, c_dbl]),
+    "tlab_dns_particle_locate": (c_int, [c_vp, ctypes.c_longlong, c_vp, c_vp]),
+    "tlab_dns_substep_particle": (c_int, [c_vp, c_dbl, c_dbl, c_int, ctypes.c_longlong, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "tlab_dns_particle_sort": (c_int, [c_vp, ctypes.c_longlong, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, ctypes.c_longlong,
+                               ctypes.POINTER(ctypes.c_longlong)]),
     "tlab_deferred_sources_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "tlab_deferred_sources_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "tlab_slab_dns_set_coriolis": (c_int, [c_vp, c_int, _dp, _dp]),
