@@ -482,8 +482,8 @@ long long tlab_dns_info(tlab_dns_t d, int what);      /* 0 nx, 1 ny, 2 nz, 3 nsc
  *     pairs, then one gather per array through the scratch.  scratch: DEVICE memory on a 256-byte boundary.  The size query is a call with
  *     scratch = NULL: *scratch_needed receives the bytes for np particles and nothing is sorted (scratch_needed may be NULL otherwise).  Scratch that
  *     is too small or misaligned: TLAB_EINVAL, the arrays untouched.  The substep never sorts on its own: the host calls this every so many steps.
- * Not built: the slab and pencil drivers (migration between ranks), particle restart files (io_particle.f90: IO stays on the host),
- * PARTICLE_TO_FIELD, the particle pdfs and trajectories, residence times. */
+ * Not built: the slab and pencil drivers (migration between ranks), particle and trajectory files (io_particle.f90, ParticleTrajectories_Write:
+ * IO stays on the host), the particle pdfs and residence times (they read the cloud droplets' columns), an order-independent deposit. */
 #define TLAB_PART_NONE 0      /* PART_TYPE_*: particle_vars.f90:8-14 */
 #define TLAB_PART_TRACER 1
 #define TLAB_PART_INERTIA 2
@@ -496,6 +496,45 @@ int tlab_dns_substep_particle(tlab_dns_t d, double dte, double kco, int scale_te
                               double *const *l_hq, int *nodes);
 int tlab_dns_particle_sort(tlab_dns_t d, long long np, double *const *l_q, double *const *l_hq, int *nodes, long long *tags, void *scratch,
                            long long scratch_bytes, long long *scratch_needed);
+/* Transfers between the particles and the grid (csrc/particles.hip), for a driver with particles (tlab_dns_set_particles); l_q, nodes, tags and np as
+ * above (the positions are the first three columns of l_q), one thread per particle, the weights and corners of step 1 of the substep: the seam
+ * cell's upper corner is index 1, a particle at x = scale lies in cell nx with fraction 0, and no position (NaN included) or node number can take a
+ * load or a store outside the arrays.  Every entry runs on the library's stream, after a recorded deferred substep, and writes no state of the
+ * driver.  TLAB_EINVAL, nothing written: a driver without particles, np < 0 or > 2^31 - 1, null pointers with np > 0, and what each entry lists.
+ * np = 0 succeeds without a launch.
+ *   tlab_dns_field_to_particle = FIELD_TO_PARTICLE (particle_interpolate.f90:186-332) of nvar >= 1 fields: fields and out are HOST arrays of nvar
+ *     DEVICE pointers (fields of nx ny nz, particle arrays of np).  Additive as in the reference, out[v](p) = out[v](p) + A (+ B) in the operation
+ *     order of the substep's interpolation (bit for bit tests/particles_oracle.py's interpolate), the weights formed once per particle
+ *     (k_particle_sample, 8 fields per launch).  TLAB_EINVAL also: nvar < 1.
+ *   tlab_dns_set_trajectories: the ntraj tags to be tracked (l_traj_tags, HOST array; distinct, >= 1), kept on the device as a table of (tag, row j)
+ *     sorted by tag.  ntraj = 0 removes the table; taking the particles off the driver removes it too.  The reference's default list (TrajFileName =
+ *     void: 1 + (j - 1) (isize_part_total / isize_traj), particle_trajectories.f90:114-122) is the caller's to build.  TLAB_EINVAL, the old table
+ *     kept: ntraj < 0, a tag below 1 or listed twice.
+ *   tlab_dns_trajectories_accumulate = ParticleTrajectories_Accumulate (particle_trajectories.f90:156-230) for column `counter` (1-based, <= nsave)
+ *     of l_traj(ntraj + 1, nsave, inb_part + nvar), fp32, column-major, DEVICE memory: row 1 of every variable gets SNGL(rtime); row 1 + j gets
+ *     SNGL(l_q(i, iv)) of the particle i that carries tag j for the inb_part prognostic columns, and behind them the value at that particle of each
+ *     of the nvar >= 0 fields (HOST array of DEVICE pointers; TRAJ_TYPE_EULERIAN with q and s; for TRAJ_TYPE_VORTICITY the caller makes the
+ *     curl with the operators), interpolated onto a zero target.  Each particle looks its tag up by bisection in the table, and only those that
+ *     find it interpolate and store (k_particle_trajectories): the tags may be in any order, e.g. after tlab_dns_particle_sort.  The fp32 values are
+ *     the round-to-nearest conversions of the oracle's doubles.  A tracked tag that no particle carries leaves its row untouched, and so is every
+ *     other column of l_traj.  TLAB_EINVAL also: no table, nvar < 0, counter outside 1 .. nsave, NaN rtime.
+ *   tlab_dns_particle_to_field = PARTICLE_TO_FIELD (particle_to_field.f90:12-154): field (DEVICE, nx ny nz) is zero-filled (also for np = 0) and
+ *     every particle adds property(p) cube length, the products of :131-147 in that order, to the eight corners of its cell (nz = 1: four).
+ *     property: DEVICE array of np, or NULL for 1.0 (the particle number density).  periodic != 0: what falls on the upper corners of the seam cells
+ *     is added to index 1 of that direction, which is what the decomposed reference does (it sends column imax + 1 and plane kmax + 1 to the
+ *     neighbour) and what conserves sum(property); periodic = 0: it is dropped, as the serial reference does when it copies (1:imax, 1:kmax) out
+ *     of its extended array.  The sums are no-return fp64 atomic adds at agent scope (k_particle_deposit; field must be ordinary device memory, as
+ *     all arrays of this library are), after the particles of adjacent lanes in the same cell have been summed in the wave.  THE ORDER OF THE ADDS
+ *     IS THE ORDER OF ARRIVAL: a node that receives more than one contribution differs from the reference's particle-ordered loop, and from
+ *     another call on the same input, in rounding only, |difference| <= 2 (cnt - 1) 2^-53 sum |contribution| for cnt contributions; a node that
+ *     receives one has the reference's bits.  TLAB_EINVAL also: field NULL. */
+int tlab_dns_field_to_particle(tlab_dns_t d, int nvar, const double *const *fields, long long np, double *const *l_q, const int *nodes,
+                               double *const *out);
+int tlab_dns_set_trajectories(tlab_dns_t d, long long ntraj, const long long *tags);
+int tlab_dns_trajectories_accumulate(tlab_dns_t d, double rtime, long long counter, long long nsave, long long np, double *const *l_q,
+                                     const int *nodes, const long long *tags, int nvar, const double *const *fields, float *l_traj);
+int tlab_dns_particle_to_field(tlab_dns_t d, long long np, double *const *l_q, const int *nodes, const double *property, int periodic,
+                               double *field);
 /* Start of a Runge-Kutta step: TIME_RUNGEKUTTA sets hq = 0, hs = 0 there (tools/dns/time.f90:212-216).  Instead of filling the arrays,
  * tell the driver: the next tlab_rhs_global_incompressible_1 / tlab_time_substep_incompressible_explicit treats them as zero (its first
  * operator launch overwrites instead of accumulating), whatever they contain. */

@@ -2,7 +2,9 @@
 // (tools/dns/rhs_part_1.f90:43-54, :112-123), FIELD_TO_PARTICLE / Interpolate_Inside_Zones (particles/particle_interpolate.f90:186-332), LOCATE_Y
 // (utils/locate_y.f90) and the low-storage scaling of l_hq (time.f90:300-304) as ONE launch per substep, one thread per particle, everything of a
 // particle in registers (k_particle_substep); and a permutation of the particle arrays by cell that keeps the gathers of a wave on few cache lines
-// (tlab_dns_particle_sort).  Tracers and inertial particles; the bilinear cloud droplets are refused.
+// (tlab_dns_particle_sort).  Tracers and inertial particles; the bilinear cloud droplets are refused.  With the same weights and corners: the
+// sample of any fields (k_particle_sample), the trajectories of the tracked tags (k_particle_trajectories) and the deposit of a particle property
+// onto the grid (PARTICLE_TO_FIELD, particles/particle_to_field.f90; k_particle_deposit).
 //
 // What differs from the reference, and why the values do not:
 //   * no halo zones, no Sort_Into_Grid / Sort_Into_Halos: those exist to reach f(1) from the last cell of a periodic direction; here the upper corner
@@ -24,6 +26,8 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "driver_common.hpp"
 #include "particles_host.hpp"
@@ -35,12 +39,22 @@
 namespace tlab {
 
 // [Particles] of one driver (tlab_dns_set_particles); y: the nodes of the driver's y plan on the device, written when the particles are set
+// traj_tags, traj_slot: the tracked tags sorted, and the row j (1-based) of each in l_traj (tlab_dns_set_trajectories)
 struct ParticleState {
     int type = TLAB_PART_NONE, bcs = TLAB_PART_BCS_NONE;
     double stokes = 0.0, settling = 0.0;
     double *y = nullptr;
+    long long *traj_tags = nullptr;
+    int *traj_slot = nullptr;
+    int ntraj = 0;
+    void drop_trajectories() {
+        if (traj_tags) (void)hipFree(traj_tags);
+        if (traj_slot) (void)hipFree(traj_slot);
+        traj_tags = nullptr; traj_slot = nullptr; ntraj = 0;
+    }
     ~ParticleState() {
         if (y) (void)hipFree(y);
+        drop_trajectories();
     }
 };
 
@@ -99,6 +113,34 @@ __device__ __forceinline__ double interpolate(const double *f, const Corners &c,
     }
 }
 
+// the weights and corners of a particle at (xp, yp, zp) with the node below it (particle_interpolate.f90:239-269; particle_to_field.f90:91-123 forms
+// the same numbers); o00 is the number of the cell.  xseam / zseam: the upper corners in x / z are the wrapped ones (index 0).
+struct Seam {
+    bool x, z;
+};
+template <bool D3>
+__device__ __forceinline__ Seam corners_of(const ParticleGrid &G, double xp, double yp, double zp, int node, Corners &c) {
+    double l1, l5 = 0.0;
+    const int i0 = cell_of(xp, G.dxi, G.nx, l1);
+    const int i1 = i0 + 1 == G.nx ? 0 : i0 + 1;
+    const double l2 = 1.0 - l1;
+    int k0 = 0, k1 = 0;
+    if constexpr (D3) {
+        k0 = cell_of(zp, G.dzi, G.nz, l5);
+        k1 = k0 + 1 == G.nz ? 0 : k0 + 1;
+    }
+    c.l5 = l5;
+    c.l6 = 1.0 - l5;
+    int j0 = node - 1;
+    j0 = j0 < 0 ? 0 : (j0 > G.ny - 2 ? G.ny - 2 : j0);
+    const double l3 = (yp - G.y[j0]) / (G.y[j0 + 1] - G.y[j0]), l4 = 1.0 - l3;
+    c.c1 = l1 * l3; c.c2 = l1 * l4; c.c3 = l4 * l2; c.c4 = l2 * l3;
+    const unsigned row0 = ((unsigned)k0 * G.ny + j0) * G.nx, row1 = row0 + G.nx;
+    c.o00 = row0 + i0; c.o01 = row1 + i0; c.o11 = row1 + i1; c.o10 = row0 + i1;
+    c.dk = ((unsigned)k1 - (unsigned)k0) * ((unsigned)G.ny * G.nx);
+    return Seam{i1 == 0, D3 && k1 == 0};
+}
+
 // TYPE: TLAB_PART_TRACER / _INERTIA; BCS: TLAB_PART_BCS_*; D3: nz > 1.  Steps 1-7 of the header's list, one particle per thread.
 template <int TYPE, int BCS, bool D3>
 __global__ void __launch_bounds__(256) k_particle_substep(ParticleArgs A) {
@@ -111,24 +153,7 @@ __global__ void __launch_bounds__(256) k_particle_substep(ParticleArgs A) {
 
     // 1. the weights and corners (particle_interpolate.f90:239-269)
     Corners c;
-    double l1, l5 = 0.0;
-    const int i0 = cell_of(lq[0], G.dxi, G.nx, l1);
-    const int i1 = i0 + 1 == G.nx ? 0 : i0 + 1;
-    const double l2 = 1.0 - l1;
-    int k0 = 0, k1 = 0;
-    if constexpr (D3) {
-        k0 = cell_of(lq[2], G.dzi, G.nz, l5);
-        k1 = k0 + 1 == G.nz ? 0 : k0 + 1;
-    }
-    c.l5 = l5;
-    c.l6 = 1.0 - l5;
-    int j0 = A.nodes[p] - 1;
-    j0 = j0 < 0 ? 0 : (j0 > G.ny - 2 ? G.ny - 2 : j0);
-    const double l3 = (lq[1] - G.y[j0]) / (G.y[j0 + 1] - G.y[j0]), l4 = 1.0 - l3;
-    c.c1 = l1 * l3; c.c2 = l1 * l4; c.c3 = l4 * l2; c.c4 = l2 * l3;
-    const unsigned row0 = ((unsigned)k0 * G.ny + j0) * G.nx, row1 = row0 + G.nx;
-    c.o00 = row0 + i0; c.o01 = row1 + i0; c.o11 = row1 + i1; c.o10 = row0 + i1;
-    c.dk = ((unsigned)k1 - (unsigned)k0) * ((unsigned)G.ny * G.nx);
+    (void)corners_of<D3>(G, lq[0], lq[1], lq[2], A.nodes[p], c);
 
     // 2. the equations (rhs_part_1.f90:43-54, :112-123)
     if constexpr (TYPE == TLAB_PART_TRACER) {
@@ -202,6 +227,131 @@ __global__ void __launch_bounds__(256) k_particle_gather(const T *a, const unsig
     if (p < np) out[p] = a[idx[p]];
 }
 
+// ---- the transfers between particles and fields: FIELD_TO_PARTICLE of any fields, ParticleTrajectories_Accumulate, PARTICLE_TO_FIELD ----
+// what the three kernels share: the grid, the position columns, the nodes
+struct TransferArgs {
+    ParticleGrid g;
+    const double *x, *y, *z;
+    const int *nodes;
+    unsigned np;
+};
+struct FieldList {
+    const double *f[PARTICLE_FIELDS_PER_LAUNCH];
+    int n;
+};
+struct TargetList {
+    double *o[PARTICLE_FIELDS_PER_LAUNCH];
+};
+
+// FIELD_TO_PARTICLE (particle_interpolate.f90:186-332) of F.n fields: out = out + A (+ B), the weights formed once per particle
+template <bool D3>
+__global__ void __launch_bounds__(256) k_particle_sample(TransferArgs A, FieldList F, TargetList O) {
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.np) return;
+    Corners c;
+    (void)corners_of<D3>(A.g, A.x[p], A.y[p], A.z[p], A.nodes[p], c);
+    for (int v = 0; v < F.n; ++v) O.o[v][p] = interpolate<D3>(F.f[v], c, O.o[v][p]);
+}
+
+// ParticleTrajectories_Accumulate (particle_trajectories.f90:205-227) for column `col` of l_traj(rows, nsave, *): the time in row 1, and for a
+// particle whose tag is tracked the nq prognostic columns (variables 0 .. nq - 1) and the F.n fields at the particle (variables ivf ..), in fp32.
+// The reference's double loop over particles and tags is a bisection in the sorted table; only the lanes that find their tag interpolate.
+struct TrajArgs {
+    const double *lq[6];
+    const long long *tags, *ttags;
+    const int *tslot;
+    float *traj;
+    size_t rows, nsave, col;
+    float rtime;
+    int nq, ivf, ntraj;
+};
+template <bool D3>
+__global__ void __launch_bounds__(256) k_particle_trajectories(TransferArgs A, TrajArgs R, FieldList F) {
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    auto at = [&](size_t row, int iv) -> float & { return R.traj[row + R.rows * (R.col + R.nsave * (size_t)iv)]; };
+    if (blockIdx.x == 0 && (int)threadIdx.x < R.nq + F.n) {
+        const int t = (int)threadIdx.x;
+        at(0, t < R.nq ? t : R.ivf + (t - R.nq)) = R.rtime;
+    }
+    if (p >= A.np) return;
+    const long long tag = R.tags[p];
+    int lo = 0, hi = R.ntraj;
+    while (lo < hi) {
+        const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+        if (R.ttags[mid] < tag) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= R.ntraj || R.ttags[lo] != tag) return;
+    const size_t row = (size_t)R.tslot[lo];
+    for (int is = 0; is < R.nq; ++is) at(row, is) = (float)R.lq[is][p];
+    if (F.n > 0) {
+        Corners c;
+        (void)corners_of<D3>(A.g, A.x[p], A.y[p], A.z[p], A.nodes[p], c);
+        for (int v = 0; v < F.n; ++v) at(row, R.ivf + v) = (float)interpolate<D3>(F.f[v], c, 0.0);
+    }
+}
+
+// PARTICLE_TO_FIELD_INTERPOLATE (particle_to_field.f90:89-151): property cube length, the products of :131-147 in that order, added to the eight
+// (nz == 1: four) corners by no-return fp64 atomic adds at agent scope (global_atomic_add_f64: the fields are plain device allocations).  The
+// reference's array has a column nx + 1 and a plane nz + 1 for the upper corners of the seam cells; here those go to index 0 (periodic) or nowhere.
+// Particles of adjacent lanes in the same cell (what tlab_dns_particle_sort leaves) are summed in the wave first, a segmented sum by lane shuffles
+// over runs of equal cell numbers, and the first lane of a run issues the run's adds.  This reorders the sum, as the atomics do.  Measured against
+// the kernel without it (512^3, sorted tracers): 3.7 / 6.0 / 6.6 ms against 4.1 / 11.2 / 25.6 ms at np = 2^24 / 2^26 / 2^27,
+// the same time unsorted (a wave without a run of two skips the shuffles).
+template <bool D3>
+__global__ void __launch_bounds__(256) k_particle_deposit(TransferArgs A, const double *prop, int periodic, double *field) {
+    constexpr int NW = D3 ? 8 : 4;
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = p < A.np;
+    Corners c = {};
+    Seam s = {false, false};
+    double w[NW] = {};
+    unsigned key = 0xffffffffu;      // (no cell has this number: at most 2^31 - 1 points)
+    if (live) {
+        s = corners_of<D3>(A.g, A.x[p], A.y[p], A.z[p], A.nodes[p], c);
+        const double pr = prop ? prop[p] : 1.0;
+        if constexpr (D3) {
+            w[0] = pr * c.c3 * c.l6; w[1] = pr * c.c4 * c.l6; w[2] = pr * c.c1 * c.l6; w[3] = pr * c.c2 * c.l6;
+            w[4] = pr * c.c3 * c.l5; w[5] = pr * c.c4 * c.l5; w[6] = pr * c.c1 * c.l5; w[7] = pr * c.c2 * c.l5;
+        } else {
+            w[0] = pr * c.c3; w[1] = pr * c.c4; w[2] = pr * c.c1; w[3] = pr * c.c2;
+        }
+        key = c.o00;
+    }
+    bool issue = live;
+    {      // every lane of the wave takes part in the shuffles: nobody has left yet
+        const unsigned lane = __lane_id();
+        const unsigned before = __shfl_up(key, 1);
+        const bool head = lane == 0 || before != key;
+        const unsigned long long heads = __ballot(head);
+        if (heads != ~0ull) {      // (wave-uniform) some run is longer than one lane
+            const unsigned long long above = (((heads >> lane) >> 1) << lane) << 1;      // the heads of the runs after mine
+            const unsigned end = above ? (unsigned)__builtin_ctzll(above) - 1u : 63u;    // the last lane of my run
+            for (unsigned d = 1; d < 64; d <<= 1) {
+                const bool take = lane + d <= end;
+                for (int i = 0; i < NW; ++i) {
+                    const double o = __shfl_down(w[i], d);
+                    if (take) w[i] = w[i] + o;
+                }
+            }
+            issue = live && head;
+        }
+    }
+    if (!issue) return;
+    auto add = [&](unsigned o, double v) { (void)__hip_atomic_fetch_add(field + o, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    const bool xs = periodic || !s.x, zs = periodic || !s.z;
+    add(c.o00, w[0]);
+    add(c.o01, w[1]);
+    if (xs) { add(c.o11, w[2]); add(c.o10, w[3]); }
+    if constexpr (D3) {
+        if (zs) {
+            add(c.o00 + c.dk, w[4]);
+            add(c.o01 + c.dk, w[5]);
+            if (xs) { add(c.o11 + c.dk, w[6]); add(c.o10 + c.dk, w[7]); }
+        }
+    }
+}
+
 // g%scale of FDM_CreatePlan (fdm/fdm.f90:162-167)
 double plan_scale(const FdmTables &t) {
     if (t.n <= 1) return 1.0;
@@ -253,6 +403,21 @@ void launch_substep_b(int bcs, bool d3, const ParticleArgs &A, hipStream_t st) {
 
 void refuse(int rc, const std::string &why) {
     if (rc != TLAB_OK) throw Fail(rc, why);
+}
+
+// a driver with particles, or a null state for the checks to refuse
+Driver transfer_driver(tlab_dns_t d, const char *who) {
+    Driver D = driver_of(d, who);
+    if ((long long)D.g.nx * D.g.ny * D.g.nz > 0x7fffffffLL) throw Fail(TLAB_EINVAL, std::string(who) + ": more than 2^31 - 1 points");
+    return D;
+}
+TransferArgs transfer_args(const Driver &D, double *const *l_q, const int *nodes, long long np) {
+    TransferArgs A;
+    A.g = grid_of(D);
+    A.x = l_q[0]; A.y = l_q[1]; A.z = l_q[2];
+    A.nodes = nodes;
+    A.np = (unsigned)np;
+    return A;
 }
 
 }  // namespace
@@ -381,6 +546,109 @@ int tlab_dns_particle_sort(tlab_dns_t d, long long np, double *const *l_q, doubl
         for (int is = 0; is < nc; ++is) { permute(l_q[is]); permute(l_hq[is]); }
         permute(nodes);
         permute(tags);
+    });
+}
+
+int tlab_dns_field_to_particle(tlab_dns_t d, int nvar, const double *const *fields, long long np, double *const *l_q, const int *nodes,
+                               double *const *out) {
+    return guarded([&] {
+        const char *who = "tlab_dns_field_to_particle";
+        Driver D = transfer_driver(d, who);
+        std::string why;
+        refuse(particle_check_sample(D.ps != nullptr, nvar, fields, np, l_q, nodes, out, why), why);
+        if (np == 0) return;
+        const TransferArgs A = transfer_args(D, l_q, nodes, np);
+        const double npts = (double)D.g.nx * D.g.ny * D.g.nz;
+        hipStream_t st = tlab_current_stream();
+        for (int v0 = 0; v0 < nvar; v0 += PARTICLE_FIELDS_PER_LAUNCH) {
+            FieldList F = {};
+            TargetList O = {};
+            F.n = nvar - v0 < PARTICLE_FIELDS_PER_LAUNCH ? nvar - v0 : PARTICLE_FIELDS_PER_LAUNCH;
+            for (int v = 0; v < F.n; ++v) { F.f[v] = fields[v0 + v]; O.o[v] = out[v0 + v]; }
+            // algorithmic bytes: positions and nodes read, the targets read and written, one pass over the fields
+            ProfScope ps("k_particle_sample", st, (double)np * (28.0 + 16.0 * F.n) + 8.0 * F.n * npts);
+            if (D.g.nz > 1) hipLaunchKernelGGL((k_particle_sample<true>), blocks(np), dim3(256), 0, st, A, F, O);
+            else hipLaunchKernelGGL((k_particle_sample<false>), blocks(np), dim3(256), 0, st, A, F, O);
+            hk(hipGetLastError(), "k_particle_sample");
+        }
+    });
+}
+
+int tlab_dns_set_trajectories(tlab_dns_t d, long long ntraj, const long long *tags) {
+    (void)tlab_internal_deferred_flush();
+    return guarded([&] {
+        const char *who = "tlab_dns_set_trajectories";
+        Driver D = driver_of(d, who);
+        std::string why;
+        std::vector<std::pair<long long, int>> table;
+        refuse(particle_trajectory_table(D.ps != nullptr, ntraj, tags, &table, why), why);
+        std::vector<long long> tt(table.size());
+        std::vector<int> ts(table.size());
+        for (size_t j = 0; j < table.size(); ++j) { tt[j] = table[j].first; ts[j] = table[j].second; }
+        hk(hipStreamSynchronize(tlab_current_stream()), "sync");      // a launch that reads the old table may be in flight
+        D.ps->drop_trajectories();
+        if (ntraj == 0) return;
+        hk(hipMalloc((void **)&D.ps->traj_tags, tt.size() * sizeof(long long)), "hipMalloc");
+        hk(hipMalloc((void **)&D.ps->traj_slot, ts.size() * sizeof(int)), "hipMalloc");
+        hk(hipMemcpy(D.ps->traj_tags, tt.data(), tt.size() * sizeof(long long), hipMemcpyHostToDevice), "hipMemcpy");
+        hk(hipMemcpy(D.ps->traj_slot, ts.data(), ts.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy");
+        D.ps->ntraj = (int)ntraj;
+    });
+}
+
+int tlab_dns_trajectories_accumulate(tlab_dns_t d, double rtime, long long counter, long long nsave, long long np, double *const *l_q,
+                                     const int *nodes, const long long *tags, int nvar, const double *const *fields, float *l_traj) {
+    return guarded([&] {
+        const char *who = "tlab_dns_trajectories_accumulate";
+        Driver D = transfer_driver(d, who);
+        const int nc = D.ps ? particle_columns(D.ps->type) : 0;
+        std::string why;
+        refuse(particle_check_trajectories(D.ps != nullptr, nc, D.ps ? D.ps->ntraj : 0, rtime, counter, nsave, np, l_q, nodes, tags, nvar, fields,
+                                           l_traj, why), why);
+        if (np == 0) return;
+        const TransferArgs A = transfer_args(D, l_q, nodes, np);
+        TrajArgs R = {};
+        for (int i = 0; i < nc; ++i) R.lq[i] = l_q[i];
+        R.tags = tags; R.ttags = D.ps->traj_tags; R.tslot = D.ps->traj_slot; R.ntraj = D.ps->ntraj;
+        R.traj = l_traj;
+        R.rows = (size_t)D.ps->ntraj + 1; R.nsave = (size_t)nsave; R.col = (size_t)(counter - 1);
+        R.rtime = (float)rtime;
+        hipStream_t st = tlab_current_stream();
+        int v0 = 0;
+        do {      // (once without fields: the prognostic columns alone)
+            FieldList F = {};
+            F.n = nvar - v0 < PARTICLE_FIELDS_PER_LAUNCH ? nvar - v0 : PARTICLE_FIELDS_PER_LAUNCH;
+            for (int v = 0; v < F.n; ++v) F.f[v] = fields[v0 + v];
+            R.nq = v0 == 0 ? nc : 0;
+            R.ivf = nc + v0;
+            // algorithmic bytes: every tag read; per tracked particle its columns, position, node and eight corners of each field, and the row written
+            ProfScope ps("k_particle_trajectories", st, 8.0 * (double)np + (double)D.ps->ntraj * (12.0 * R.nq + 28.0 + 68.0 * F.n));
+            if (D.g.nz > 1) hipLaunchKernelGGL((k_particle_trajectories<true>), blocks(np), dim3(256), 0, st, A, R, F);
+            else hipLaunchKernelGGL((k_particle_trajectories<false>), blocks(np), dim3(256), 0, st, A, R, F);
+            hk(hipGetLastError(), "k_particle_trajectories");
+            v0 += PARTICLE_FIELDS_PER_LAUNCH;
+        } while (v0 < nvar);
+    });
+}
+
+int tlab_dns_particle_to_field(tlab_dns_t d, long long np, double *const *l_q, const int *nodes, const double *property, int periodic,
+                               double *field) {
+    return guarded([&] {
+        const char *who = "tlab_dns_particle_to_field";
+        Driver D = transfer_driver(d, who);
+        std::string why;
+        refuse(particle_check_deposit(D.ps != nullptr, np, l_q, nodes, field, why), why);
+        const size_t npts = (size_t)D.g.nx * D.g.ny * D.g.nz;
+        hipStream_t st = tlab_current_stream();
+        hk(hipMemsetAsync(field, 0, npts * sizeof(double), st), "hipMemsetAsync");      // wrk3d = 0 (particle_to_field.f90:33)
+        if (np == 0) return;
+        const TransferArgs A = transfer_args(D, l_q, nodes, np);
+        const int per = periodic ? 1 : 0;
+        // algorithmic bytes: positions, nodes and the property read, eight 8-byte adds per particle
+        ProfScope ps("k_particle_deposit", st, (double)np * (28.0 + (property ? 8.0 : 0.0) + (D.g.nz > 1 ? 64.0 : 32.0)));
+        if (D.g.nz > 1) hipLaunchKernelGGL((k_particle_deposit<true>), blocks(np), dim3(256), 0, st, A, property, per, field);
+        else hipLaunchKernelGGL((k_particle_deposit<false>), blocks(np), dim3(256), 0, st, A, property, per, field);
+        hk(hipGetLastError(), "k_particle_deposit");
     });
 }
 

@@ -2,9 +2,12 @@
 // sort's scratch array.  Plain C++ without a HIP header, so that a stand-alone program can include it and run under the host sanitizers
 // (tools/particles_host_check.cpp).  Every function returns a TLAB_* code and leaves the reason in `why`; none touches memory it is not handed.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/tlab_amd.h"
 
@@ -38,7 +41,8 @@ inline int particle_check_count(const char *who, long long np, std::string &why)
 }
 
 // an array of ncol device pointers, none null (checked only when there are particles)
-inline int particle_check_columns(const char *who, const char *name, double *const *cols, int ncol, std::string &why) {
+template <class T>
+inline int particle_check_columns(const char *who, const char *name, T *const *cols, int ncol, std::string &why) {
     if (!cols) { why = std::string(who) + ": " + name + " is null"; return TLAB_EINVAL; }
     for (int i = 0; i < ncol; ++i)
         if (!cols[i]) { why = std::string(who) + ": a column of " + name + " is null"; return TLAB_EINVAL; }
@@ -57,6 +61,78 @@ inline int particle_check_substep(bool has_particles, int ncol, double dte, doub
     if (int rc = particle_check_columns(who, "l_q", l_q, ncol, why)) return rc;
     if (int rc = particle_check_columns(who, "l_hq", l_hq, ncol, why)) return rc;
     if (!nodes) { why = std::string(who) + ": nodes is null"; return TLAB_EINVAL; }
+    return TLAB_OK;
+}
+
+// ---- the transfers between particles and fields (k_particle_sample, k_particle_trajectories, k_particle_deposit) ----
+// the fields of one launch of the sample and of the trajectories: longer lists go in groups of this many
+constexpr int PARTICLE_FIELDS_PER_LAUNCH = 8;
+
+// tlab_dns_field_to_particle: the positions are the first three columns of l_q whatever the type
+inline int particle_check_sample(bool has_particles, int nvar, const double *const *fields, long long np, double *const *l_q, const int *nodes,
+                                 double *const *out, std::string &why) {
+    const char *who = "tlab_dns_field_to_particle";
+    if (!has_particles) { why = std::string(who) + ": no particles are set on this driver (tlab_dns_set_particles)"; return TLAB_EINVAL; }
+    if (int rc = particle_check_count(who, np, why)) return rc;
+    if (nvar < 1) { why = std::string(who) + ": nvar < 1"; return TLAB_EINVAL; }
+    if (np == 0) return TLAB_OK;
+    if (int rc = particle_check_columns(who, "fields", fields, nvar, why)) return rc;
+    if (int rc = particle_check_columns(who, "l_q", l_q, 3, why)) return rc;
+    if (int rc = particle_check_columns(who, "out", out, nvar, why)) return rc;
+    if (!nodes) { why = std::string(who) + ": nodes is null"; return TLAB_EINVAL; }
+    return TLAB_OK;
+}
+
+// tlab_dns_particle_to_field: the field is zero-filled even without particles, so it is never null
+inline int particle_check_deposit(bool has_particles, long long np, double *const *l_q, const int *nodes, const double *field, std::string &why) {
+    const char *who = "tlab_dns_particle_to_field";
+    if (!has_particles) { why = std::string(who) + ": no particles are set on this driver (tlab_dns_set_particles)"; return TLAB_EINVAL; }
+    if (int rc = particle_check_count(who, np, why)) return rc;
+    if (!field) { why = std::string(who) + ": field is null"; return TLAB_EINVAL; }
+    if (np == 0) return TLAB_OK;
+    if (int rc = particle_check_columns(who, "l_q", l_q, 3, why)) return rc;
+    if (!nodes) { why = std::string(who) + ": nodes is null"; return TLAB_EINVAL; }
+    return TLAB_OK;
+}
+
+// tlab_dns_set_trajectories: the table of (tag, slot j) sorted by tag, slot 1-based as l_traj_tags(j).  Tags are distinct and >= 1 (the
+// reference's tags are 1 .. isize_part_total); nothing is stored in `table` unless the list is good.
+constexpr long long PARTICLE_NTRAJ_MAX = 0x7ffffffeLL;      // ntraj + 1 rows are indexed with 32 bits
+inline int particle_trajectory_table(bool has_particles, long long ntraj, const long long *tags, std::vector<std::pair<long long, int>> *table,
+                                     std::string &why) {
+    const char *who = "tlab_dns_set_trajectories";
+    if (!has_particles) { why = std::string(who) + ": no particles are set on this driver (tlab_dns_set_particles)"; return TLAB_EINVAL; }
+    if (ntraj < 0) { why = std::string(who) + ": ntraj < 0"; return TLAB_EINVAL; }
+    if (ntraj > PARTICLE_NTRAJ_MAX) { why = std::string(who) + ": more than 2^31 - 2 trajectories"; return TLAB_EINVAL; }
+    if (ntraj > 0 && !tags) { why = std::string(who) + ": tags is null"; return TLAB_EINVAL; }
+    std::vector<std::pair<long long, int>> t((size_t)ntraj);
+    for (long long j = 0; j < ntraj; ++j) {
+        if (tags[j] < 1) { why = std::string(who) + ": a tag below 1"; return TLAB_EINVAL; }
+        t[(size_t)j] = {tags[j], (int)(j + 1)};
+    }
+    std::sort(t.begin(), t.end());
+    for (size_t j = 1; j < t.size(); ++j)
+        if (t[j].first == t[j - 1].first) { why = std::string(who) + ": a tag is listed twice"; return TLAB_EINVAL; }
+    table->swap(t);
+    return TLAB_OK;
+}
+
+// tlab_dns_trajectories_accumulate: ncol = inb_part of the driver's type, ntraj = the rows of its table (0: none was set)
+inline int particle_check_trajectories(bool has_particles, int ncol, long long ntraj, double rtime, long long counter, long long nsave,
+                                       long long np, double *const *l_q, const int *nodes, const long long *tags, int nvar,
+                                       const double *const *fields, const float *l_traj, std::string &why) {
+    const char *who = "tlab_dns_trajectories_accumulate";
+    if (!has_particles) { why = std::string(who) + ": no particles are set on this driver (tlab_dns_set_particles)"; return TLAB_EINVAL; }
+    if (ntraj < 1) { why = std::string(who) + ": no tags are tracked on this driver (tlab_dns_set_trajectories)"; return TLAB_EINVAL; }
+    if (int rc = particle_check_count(who, np, why)) return rc;
+    if (nvar < 0) { why = std::string(who) + ": nvar < 0"; return TLAB_EINVAL; }
+    if (nsave < 1 || counter < 1 || counter > nsave) { why = std::string(who) + ": counter outside 1 .. nsave"; return TLAB_EINVAL; }
+    if (std::isnan(rtime)) { why = std::string(who) + ": rtime is NaN"; return TLAB_EINVAL; }
+    if (np == 0) return TLAB_OK;
+    if (int rc = particle_check_columns(who, "l_q", l_q, ncol, why)) return rc;
+    if (nvar > 0)
+        if (int rc = particle_check_columns(who, "fields", fields, nvar, why)) return rc;
+    if (!nodes || !tags || !l_traj) { why = std::string(who) + ": nodes, tags or l_traj is null"; return TLAB_EINVAL; }
     return TLAB_OK;
 }
 

@@ -215,6 +215,9 @@ class Dns:
         self.l_q = self.l_hq = self.l_nodes = self.l_tags = None
         self.part_type, self.np = PART_TYPES["none"], 0
         self._part_ptrs = self._part_scratch = None
+        # trajectories (set_trajectories): l_traj (float32, device), the tracked tags, the sampled fields, the counter and nitera_save
+        self.l_traj = self.l_traj_tags = None
+        self.traj_fields, self.traj_counter, self.traj_nsave = [], 0, 0
 
     def set_bcs(self, velocity_jmin="noslip", velocity_jmax="noslip", scalar_jmin="dirichlet", scalar_jmax="dirichlet"):
         """Wall boundary conditions in y by the reference's dns.ini keywords ([BoundaryConditions], boundary_bcs.f90:102-190)."""
@@ -391,6 +394,11 @@ class Dns:
         check(load().tlab_dns_set_particles(self._h, code, wall, float(stokes), float(settling)), "tlab_dns_set_particles")
         self.part_type, self.np = code, int(number) if code else 0
         self._part_ptrs = self._part_scratch = None
+        if code == 0 or self.l_traj is not None:      # (the driver drops its table with the particles; a new population needs a new l_traj)
+            if code != 0:
+                check(load().tlab_dns_set_trajectories(self._h, 0, None), "tlab_dns_set_trajectories")
+            self.l_traj = self.l_traj_tags = None
+            self.traj_fields, self.traj_counter, self.traj_nsave = [], 0, 0
         if code == 0:
             self.l_q = self.l_hq = self.l_nodes = self.l_tags = None
             return
@@ -434,6 +442,85 @@ class Dns:
             self._part_scratch = torch.empty(max(need.value, 1), dtype=torch.uint8, device=self.q[0].device)
         check(L.tlab_dns_particle_sort(self._h, self.np, lq, lhq, self.l_nodes.data_ptr(), self.l_tags.data_ptr(), self._part_scratch.data_ptr(),
                                        self._part_scratch.numel(), None), "tlab_dns_particle_sort")
+
+    def _positions(self):
+        lq, _ = self._particle_arrays()
+        return lq
+
+    def FIELD_TO_PARTICLE(self, fields, out=None):
+        """FIELD_TO_PARTICLE (particle_interpolate.f90:186-332) of a list of device fields (nx ny nz each) at the particles: ADDS onto the tensors of
+        `out` (np each) as the reference does; out = None allocates zeros.  Returns out."""
+        import torch
+        _use_torch_stream()
+        lq = self._positions()
+        fields = list(fields)
+        if out is None:
+            out = [torch.zeros(max(self.np, 1), dtype=torch.float64, device=self.q[0].device)[:self.np] for _ in fields]
+        out = list(out)
+        if len(out) != len(fields):
+            raise TlabError("FIELD_TO_PARTICLE: as many targets as fields")
+        arr = lambda ts: (c_vp * max(len(ts), 1))(*[t.data_ptr() for t in ts])      # noqa: E731
+        check(load().tlab_dns_field_to_particle(self._h, len(fields), arr(fields), self.np, lq, self.l_nodes.data_ptr(), arr(out)),
+              "tlab_dns_field_to_particle")
+        return out
+
+    def PARTICLE_TO_FIELD(self, property=None, out=None, periodic=True):
+        """PARTICLE_TO_FIELD (particle_to_field.f90): the trilinear deposit of a particle property (device tensor of np; None: 1 per particle, the
+        number density) onto the grid.  periodic=True adds what falls on the seam's upper corners to index 0 (the decomposed reference; conserves the
+        property), False drops it (the serial reference).  The sums are atomic: a node with several contributions is reproduced up to rounding."""
+        import torch
+        _use_torch_stream()
+        lq = self._positions()
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.q[0].device)
+        check(load().tlab_dns_particle_to_field(self._h, self.np, lq, self.l_nodes.data_ptr(), None if property is None else property.data_ptr(),
+                                                int(bool(periodic)), out.data_ptr()), "tlab_dns_particle_to_field")
+        return out
+
+    def set_trajectories(self, number=None, tags=None, nsave=1, fields=()):
+        """ParticleTrajectories_Initialize (particle_trajectories.f90:104-149): track `tags`, or with tags = None the reference's default list of
+        `number` tags 1 + (j - 1) (np // number); l_traj is the reference's l_traj(number + 1, nsave, inb_part + len(fields)) as a zeroed float32
+        tensor of shape (inb_part + len(fields), nsave, number + 1); `fields` are the device fields sampled behind the prognostic columns
+        (TrajType = eulerian: d.q + d.s).  number = 0 (or an empty list) switches the trajectories off."""
+        import torch
+        self._particle_arrays()
+        if tags is None:
+            number = int(number or 0)
+            if number < 0 or number > self.np:
+                raise TlabError("set_trajectories: the number of trajectories must lie in 0 .. np")       # particle_trajectories.f90:76-79
+            stride = self.np // number if number else 0
+            tags = [1 + j * stride for j in range(number)]
+        tg = np.ascontiguousarray(np.asarray(tags, dtype=np.int64).ravel())
+        check(load().tlab_dns_set_trajectories(self._h, len(tg), tg.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))), "tlab_dns_set_trajectories")
+        self.l_traj = self.l_traj_tags = None
+        self.traj_fields, self.traj_counter, self.traj_nsave = [], 0, 0
+        if len(tg) == 0:
+            return
+        if int(nsave) < 1:
+            raise TlabError("set_trajectories: nsave < 1")
+        self.l_traj_tags, self.traj_fields, self.traj_nsave = tg, list(fields), int(nsave)
+        self.l_traj = torch.zeros(len(self.l_q) + len(self.traj_fields), self.traj_nsave, len(tg) + 1, dtype=torch.float32, device=self.q[0].device)
+
+    def ParticleTrajectories_Accumulate(self, rtime):
+        """particle_trajectories.f90:156-230: the next column of l_traj (the counter advances; after nsave calls, write and call
+        trajectories_written())."""
+        _use_torch_stream()
+        lq = self._positions()
+        if self.l_traj is None:
+            raise TlabError("no trajectories are set on this driver (set_trajectories)")
+        f = self.traj_fields
+        fp = (c_vp * max(len(f), 1))(*[t.data_ptr() for t in f])
+        check(load().tlab_dns_trajectories_accumulate(self._h, float(rtime), self.traj_counter + 1, self.traj_nsave, self.np, lq,
+                                                      self.l_nodes.data_ptr(), self.l_tags.data_ptr(), len(f), fp, self.l_traj.data_ptr()),
+              "tlab_dns_trajectories_accumulate")
+        self.traj_counter += 1
+
+    def trajectories_written(self):
+        """the end of ParticleTrajectories_Write (:266-267): l_traj = 0, counter = 0 (the file output itself is the caller's)."""
+        if self.l_traj is not None:
+            _use_torch_stream()
+            self.l_traj.zero_()
+        self.traj_counter = 0
 
     def set_fusion(self, on):
         """on (default): pointwise sums folded into the operator kernels; off: the reference's literal sequence."""

@@ -99,6 +99,11 @@ SIGNATURES = {
     "tlab_dns_substep_particle": (c_int, [c_vp, c_dbl, c_dbl, c_int, ctypes.c_longlong, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "tlab_dns_particle_sort": (c_int, [c_vp, ctypes.c_longlong, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, ctypes.c_longlong,
                                ctypes.POINTER(ctypes.c_longlong)]),
+    "tlab_dns_field_to_particle": (c_int, [c_vp, c_int, ctypes.POINTER(c_vp), ctypes.c_longlong, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp)]),
+    "tlab_dns_set_trajectories": (c_int, [c_vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+    "tlab_dns_trajectories_accumulate": (c_int, [c_vp, c_dbl, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(c_vp), c_vp, c_vp,
+                                         c_int, ctypes.POINTER(c_vp), c_vp]),
+    "tlab_dns_particle_to_field": (c_int, [c_vp, ctypes.c_longlong, ctypes.POINTER(c_vp), c_vp, c_vp, c_int, c_vp]),
     "tlab_deferred_sources_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]),
     "tlab_deferred_sources_stats": (c_int, [ctypes.POINTER(ctypes.c_longlong)]),
     "tlab_slab_dns_set_coriolis": (c_int, [c_vp, c_int, _dp, _dp]),

@@ -103,6 +103,92 @@ int main() {
     EXPECT(particle_key_bits(~0ULL) == 32);
     for (unsigned long long n : {1ULL, 2ULL, 1000ULL, 20ULL * 12 * 8, 70ULL * 33 * 9, 1ULL << 27, 0x7fffffffULL})
         EXPECT(n - 1 < (1ULL << particle_key_bits(n)));      // the largest cell number fits
+
+    // ---- tlab_dns_field_to_particle ----
+    {
+        const double f = 0.0;
+        std::vector<const double *> fl(9, &f), fhole(9, &f);
+        std::vector<double *> out(9, &a), ohole(9, &a);
+        fhole[8] = nullptr; ohole[0] = nullptr;
+        EXPECT(particle_check_sample(false, 1, fl.data(), 1, l3.data(), &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 0, fl.data(), 1, l3.data(), &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, -3, fl.data(), 0, l3.data(), &node, out.data(), why) == TLAB_EINVAL);      // nvar is read before np = 0 returns
+        EXPECT(particle_check_sample(true, 1, fl.data(), -1, l3.data(), &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 1, fl.data(), PARTICLE_NP_MAX + 1, l3.data(), &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 9, nullptr, 0, nullptr, nullptr, nullptr, why) == TLAB_OK);                 // np = 0 reads no pointer
+        EXPECT(particle_check_sample(true, 9, nullptr, 1, l3.data(), &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 9, fl.data(), 1, nullptr, &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 9, fl.data(), 1, l3.data(), nullptr, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 9, fl.data(), 1, l3.data(), &node, nullptr, why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 9, fhole.data(), 1, l3.data(), &node, out.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 9, fl.data(), 1, l3.data(), &node, ohole.data(), why) == TLAB_EINVAL);
+        EXPECT(particle_check_sample(true, 8, fhole.data(), 1, l3.data(), &node, out.data(), why) == TLAB_OK);          // the hole is the ninth
+        EXPECT(particle_check_sample(true, 9, fl.data(), 1, hole.data(), &node, out.data(), why) == TLAB_OK);           // positions: three columns
+        std::unique_ptr<const double *[]> f1(new const double *[1]{&f});      // exactly nvar entries on the heap
+        std::unique_ptr<double *[]> o1(new double *[1]{&a});
+        EXPECT(particle_check_sample(true, 1, f1.get(), PARTICLE_NP_MAX, l3.data(), &node, o1.get(), why) == TLAB_OK);
+    }
+    // ---- tlab_dns_particle_to_field ----
+    EXPECT(particle_check_deposit(false, 1, l3.data(), &node, &a, why) == TLAB_EINVAL);
+    EXPECT(particle_check_deposit(true, -1, l3.data(), &node, &a, why) == TLAB_EINVAL);
+    EXPECT(particle_check_deposit(true, PARTICLE_NP_MAX + 1, l3.data(), &node, &a, why) == TLAB_EINVAL);
+    EXPECT(particle_check_deposit(true, 0, nullptr, nullptr, nullptr, why) == TLAB_EINVAL);      // the field is zero-filled even then
+    EXPECT(particle_check_deposit(true, 0, nullptr, nullptr, &a, why) == TLAB_OK);
+    EXPECT(particle_check_deposit(true, 1, nullptr, &node, &a, why) == TLAB_EINVAL);
+    EXPECT(particle_check_deposit(true, 1, l3.data(), nullptr, &a, why) == TLAB_EINVAL);
+    EXPECT(particle_check_deposit(true, 1, l3.data(), &node, nullptr, why) == TLAB_EINVAL);
+    EXPECT(particle_check_deposit(true, PARTICLE_NP_MAX, hole.data(), &node, &a, why) == TLAB_OK);
+    // ---- tlab_dns_set_trajectories ----
+    {
+        std::vector<std::pair<long long, int>> table{{77, 7}};
+        const std::vector<std::pair<long long, int>> kept = table;
+        const long long good[5] = {40, 3, 1LL << 40, 1, 17}, twice[4] = {5, 9, 5, 2}, zero[3] = {4, 0, 2}, negative[2] = {-1, 3};
+        EXPECT(particle_trajectory_table(false, 5, good, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, -1, good, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, PARTICLE_NTRAJ_MAX + 1, good, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, 5, nullptr, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, 4, twice, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, 3, zero, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, 2, negative, &table, why) == TLAB_EINVAL && table == kept);
+        EXPECT(particle_trajectory_table(true, 5, good, &table, why) == TLAB_OK && table.size() == 5);
+        const std::vector<std::pair<long long, int>> want{{1, 4}, {3, 2}, {17, 5}, {40, 1}, {1LL << 40, 3}};      // sorted by tag, rows 1-based
+        EXPECT(table == want);
+        EXPECT(particle_trajectory_table(true, 2, twice, &table, why) == TLAB_OK && table.size() == 2);         // (only the first two are read)
+        EXPECT(particle_trajectory_table(true, 0, nullptr, &table, why) == TLAB_OK && table.empty());
+    }
+    // ---- tlab_dns_trajectories_accumulate ----
+    {
+        const double f = 0.0;
+        float tr = 0.0f;
+        long long tag = 1;
+        std::vector<const double *> fl(2, &f), fhole(2, &f);
+        fhole[1] = nullptr;
+        auto chk = [&](bool has, int nc, long long ntraj, double rtime, long long counter, long long nsave, long long np, double *const *lq,
+                       const int *nodes, const long long *tags, int nvar, const double *const *fields, const float *traj) {
+            return particle_check_trajectories(has, nc, ntraj, rtime, counter, nsave, np, lq, nodes, tags, nvar, fields, traj, why);
+        };
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_OK);
+        EXPECT(chk(true, 6, 4, inf, 7, 7, PARTICLE_NP_MAX, l6.data(), &node, &tag, 0, nullptr, &tr) == TLAB_OK);      // nvar = 0 reads no field list
+        EXPECT(chk(false, 0, 0, 0.5, 1, 1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 0, 0.5, 1, 1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);            // no table
+        EXPECT(chk(true, 3, 4, nan, 1, 1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 0, 1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 2, 1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 0, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, -1, -1, 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, -1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, PARTICLE_NP_MAX + 1, l3.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), &node, &tag, -1, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 0, nullptr, nullptr, nullptr, 2, nullptr, nullptr) == TLAB_OK);          // np = 0 reads no pointer
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, nullptr, &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), nullptr, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), &node, nullptr, 2, fl.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), &node, &tag, 2, nullptr, &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), &node, &tag, 2, fhole.data(), &tr) == TLAB_EINVAL);
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, l3.data(), &node, &tag, 2, fl.data(), nullptr) == TLAB_EINVAL);
+        EXPECT(chk(true, 6, 4, 0.5, 1, 1, 1, hole.data(), &node, &tag, 2, fl.data(), &tr) == TLAB_EINVAL);         // inertia reads six columns
+        EXPECT(chk(true, 3, 4, 0.5, 1, 1, 1, hole.data(), &node, &tag, 1, fhole.data(), &tr) == TLAB_OK);
+    }
     if (failures) { std::printf("particles_host_check: %d FAILED\n", failures); return 1; }
     std::printf("particles_host_check ok\n");
     return 0;
