@@ -1,0 +1,126 @@
+// The monitors of the main loop on the single-domain driver: TIME_COURANT, MINMAX, FI_INVARIANT_P and DNS_BOUNDS_CONTROL's dilatation extremes
+// (the kernels are in pointwise.hip and monitor.hip).
+#include "../../include/tlab_amd.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "dns_state.hpp"
+#include "monitor.hpp"
+
+using namespace tlab;
+
+// min / max of a device array through per-block partials reduced on the host (diagnostics: once per time step, not per substep)
+static void minmax_impl(tlab_dns_t d, const double *a, const double *v, const double *w, int mode, int nx, int ny, int nz, double *mn, double *mx) {
+    hipStream_t st = tlab_current_stream();
+    const long long n = (long long)nx * ny * nz;
+    const int nb = (int)std::min<long long>(1024, (n + 255) / 256);
+    hk(launch_minmax_partial(a, v, w, d->od[0], d->od[1], d->od[2], mode, nx, ny, nz, d->koffset, d->nz_total > 1 ? 1 : 0, d->part, nb, st), "k_minmax_partial");
+    std::vector<double> h((size_t)2 * nb);
+    hk(hipMemcpyAsync(h.data(), d->part, (size_t)2 * nb * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy");
+    hk(hipStreamSynchronize(st), "sync");
+    *mn = *std::min_element(h.begin(), h.begin() + nb);
+    *mx = *std::max_element(h.begin() + nb, h.end());
+}
+
+extern "C" {
+
+int tlab_time_courant(tlab_dns_t d, double *const *q, double cfla, double cfld, double *pmax, double *dtime) {
+    return catch_fail([&] {
+        if (!d || !q || !pmax) throw Fail(TLAB_EINVAL, "tlab_time_courant: bad arguments");
+        if (d->dx2i < 0.0) throw Fail(TLAB_EINVAL, "tlab_time_courant: the plans carry no Jacobian (tlab_fdm_plan_set_aux)");
+        double mn, mx;
+        minmax_impl(d, q[0], q[1], q[2], 1, d->nx, d->ny, d->nz, &mn, &mx);
+        pmax[0] = mx;                                   // max of |u|/dx + |v|/dy + |w|/dz over the local box (time.f90:402-451)
+        pmax[1] = d->schmidtfactor * d->dx2i;           // time.f90:466
+        if (dtime && cfla > 0.0) *dtime = courant_dtime(cfla, cfld, pmax);      // (without a CFL number the caller's dtime stands)
+    });
+}
+
+int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *tmp1) {
+    return catch_fail([&] {
+        if (!d || !u || !v || !w || !result || !tmp1) throw Fail(TLAB_EINVAL, "tlab_fi_invariant_p: bad arguments");
+        const int nx = d->nx, ny = d->ny, nz = d->nz;
+        const long long n = (long long)nx * ny * nz;
+        hipStream_t st = tlab_current_stream();
+        // result = -((du/dx + dv/dy) + dw/dz), fi_vectorcalculus.f90:130-136
+        ok(tlab_opr_partial(1, d->g[0], TLAB_OPR_P1, nx, ny, nz, 0, u, result, nullptr), "OPR_Partial_X");
+        ok(tlab_opr_partial(2, d->g[1], TLAB_OPR_P1, nx, ny, nz, 0, v, tmp1, nullptr), "OPR_Partial_Y");
+        hk(launch_add1(result, tmp1, n, st), "add");
+        ok(tlab_opr_partial(3, d->g[2], TLAB_OPR_P1, nx, ny, nz, 0, w, tmp1, nullptr), "OPR_Partial_Z");
+        hk(launch_add1(result, tmp1, n, st), "add");
+        hk(launch_negate(result, n, st), "negate");
+    });
+}
+
+int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *amn, double *amx) {
+    return catch_fail([&] {
+        if (!d || !a || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_minmax: bad arguments");
+        minmax_impl(d, a, nullptr, nullptr, 0, nx, ny, nz, amn, amx);
+    });
+}
+
+// DNS_BOUNDS_CONTROL (dns_local.f90:157-230), incompressible and anelastic: div(q) accumulated into txc[0] by the three P1 derivatives, then one
+// reduction for min, max and their first locations.  Anelastic runs weight the velocities by rbackground first (:160-162, into txc[2..4]).
+int tlab_dns_dilatation_extremes(tlab_dns_t d, double *const *q, double *const *txc, double *dil_min, double *dil_max, int *loc_min, int *loc_max) {
+    return catch_fail([&] {
+        if (!d || !q || !txc || !dil_min || !dil_max) throw Fail(TLAB_EINVAL, "tlab_dns_dilatation_extremes: bad arguments");
+        if (d->stagger) throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_dilatation_extremes: FI_INVARIANT_P_STAG (staggered pressure) is not built on the device");
+        hipStream_t st = tlab_current_stream();      // (a recorded substep runs first: q is read below)
+        follow_anelastic(d);
+        const int nx = d->nx, ny = d->ny, nz = d->nz;
+        const long long n = (long long)nx * ny * nz;
+        const double *u = q[0], *v = q[1], *w = q[2];
+        if (d->rb) {      // Thermo_Anelastic_WEIGHT_OUTPLACE(.., rbackground, q(1, i), txc(1, 2 + i))
+            for (int i = 0; i < 3; ++i) hk(launch_weight_y(txc[2 + i], q[i], d->rb, nx, ny, n, 0, st), "k_weight_y");
+            u = txc[2]; v = txc[3]; w = txc[4];
+        }
+        ok(tlab_opr_partial_add(1, d->g[0], nx, ny, nz, 0, u, nullptr, 0.0, txc[0], 0, txc[5], txc[6]), "OPR_Partial_X");
+        ok(tlab_opr_partial_add(2, d->g[1], nx, ny, nz, 0, v, nullptr, 0.0, txc[0], 1, txc[5], txc[6]), "OPR_Partial_Y");
+        ok(tlab_opr_partial_add(3, d->g[2], nx, ny, nz, 0, w, nullptr, 0.0, txc[0], 1, txc[5], txc[6]), "OPR_Partial_Z");
+        long long imn = 0, imx = 0;
+        hk(monitor_extremes(txc[0], nullptr, n, dil_min, dil_max, &imn, &imx, st), "k_extremes");
+        auto loc = [&](long long e, int *ijk) {      // 1-based, k global (tlab_dns_set_slab)
+            if (!ijk) return;
+            ijk[0] = (int)(e % nx) + 1; ijk[1] = (int)((e / nx) % ny) + 1; ijk[2] = (int)(e / ((long long)nx * ny)) + 1 + d->koffset;
+        };
+        loc(imn, loc_min);
+        loc(imx, loc_max);
+    });
+}
+
+// the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
+int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff, double *pmax) {
+    return catch_fail([&] {
+        if (d->dx2i < 0.0) throw Fail(TLAB_EINVAL, "TIME_COURANT: the plans carry no Jacobian (tlab_fdm_plan_set_aux)");
+        hipStream_t st = tlab_current_stream();
+        hk(monitor_courant_max(u, v, w, d->od[0], d->od[1], d->od[2], nx, ny, nz, ioff, koff, d->nz_total > 1 ? 1 : 0, &pmax[0], st), "k_courant");
+        pmax[1] = d->schmidtfactor * d->dx2i;
+    });
+}
+
+// MINMAX (utils/minmax.f90:6), local part, of any device array: no driver needed
+int tlab_device_minmax(const double *a, long long n, double *amn, double *amx) {
+    return catch_fail([&] {
+        if (!a || n < 1 || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_device_minmax: bad arguments");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
+        hk(monitor_extremes(a, nullptr, n, amn, amx, nullptr, nullptr, tlab_current_stream()), "k_extremes");
+    });
+}
+
+// ... of an array of either kind (the drop-in MINMAX): device memory takes the kernel, host memory the host loop of minmax.f90 -- a host array
+// never reaches a kernel, a device array is never read by the host.  Without tlab_init no array is the library's: the host loop.
+int tlab_minmax_any(const double *a, long long n, double *amn, double *amx) {
+    if (!a || n < 1 || !amn || !amx) { tlab_set_error("tlab_minmax_any: bad arguments"); return TLAB_EINVAL; }
+    const int on = tlab_device_ready() ? tlab_pointer_on_device(a) : 0;
+    if (on < 0) return on;
+    if (on) return tlab_device_minmax(a, n, amn, amx);
+    double mn = a[0], mx = a[0];
+    for (long long i = 1; i < n; ++i) { mn = std::min(mn, a[i]); mx = std::max(mx, a[i]); }
+    *amn = mn; *amx = mx;
+    return TLAB_OK;
+}
+
+}  // extern "C"

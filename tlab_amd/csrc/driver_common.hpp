@@ -1,4 +1,4 @@
-// What the three drivers (rhs.cpp: one domain, slab.cpp: z-slabs, pencil.cpp: x/z pencils) and zslab.hip share around their physics: the error
+// What the three drivers (rhs.cpp with dns_setup.cpp: one domain, slab.cpp: z-slabs, pencil.cpp: x/z pencils) and zslab.hip share around their physics: the error
 // type and the guards of their entry points, and the state and argument checks that do not depend on the decomposition.  Header-only, host code.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -101,6 +101,12 @@ struct WallBcs {
         scal_jmin.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
         scal_jmax.assign(nscal, TLAB_DNS_BCS_DIRICHLET);
     }
+    // the Neumann variant of a field as BOUNDARY_BCS_NEUMANN_Y and the kernels take it: 0 none, 1 jmin, 2 jmax, 3 both (the other side Dirichlet)
+    static int variant(int tmin, int tmax) { return (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0); }
+    int flow_variant(int i) const { return variant(flow_jmin[i], flow_jmax[i]); }
+    int scal_variant(int is) const { return variant(scal_jmin[is], scal_jmax[is]); }
+    // every wall of every velocity component is Dirichlet (no-slip)
+    bool flow_dirichlet() const { return flow_variant(0) == 0 && flow_variant(1) == 0 && flow_variant(2) == 0; }
     // tlab_*_set_bcs (who = the entry point): throws, and leaves the types as they were, unless every type is valid
     void set(const std::string &who, int nscal, const int *fmin, const int *fmax, const int *smin, const int *smax) {
         if (!fmin || !fmax || (nscal > 0 && (!smin || !smax))) throw Fail(TLAB_EINVAL, who + ": bad arguments");

@@ -86,7 +86,7 @@ int tlab_internal_zslab_burgers_z_n(tlab_zslab_plan_t P, int phase, int nx, int 
 int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, const double *p, const double *const *p_halo, const double *tail_left,
                                          const double *head_right, double *q, double *h, double dte, double kco, int scale);
 
-// ---- rhs.cpp ----
+// ---- dns_setup.cpp: the single-domain driver apart from its substep (its state: dns_state.hpp) ----
 long long tlab_internal_dns_points(tlab_dns_t d);      // deferred.cpp
 int tlab_internal_dns_nscal(tlab_dns_t d);
 int tlab_internal_dns_scal_arrays(tlab_dns_t d);      // inb_scal_array: nscal, + 1 (the liquid) with a mixture -- the arrays every s of the entry points holds
@@ -98,16 +98,7 @@ bool tlab_internal_dns_has_forces(tlab_dns_t d);
 // shared by the three drivers: n entries (<= nscal) of active / lo / hi checked, the bounds of the active ones returned (on[is] = 0 otherwise)
 bool tlab_internal_check_bounds(const char *who, int nscal, int n, const int *active, const double *lo, const double *hi, std::vector<char> &on,
                                 std::vector<double> &blo, std::vector<double> &bhi);
-// q += dte h, q = min(max(q, lo), hi), h *= kco: the scalar update of the decomposed drivers with their bounds (pencil.cpp)
-int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi);
 extern "C" {
-// the substep with the tail the caller hands over (driver_common.hpp: SubstepTail), behind tlab_time_substep_incompressible_explicit -- which passes
-// the driver's own settings -- and the replay of a record (deferred.cpp); throws tlab::Fail
-void tlab_internal_dns_substep(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
-                               const tlab::SubstepTail &tail);
-// the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
-int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff,
-                              double *pmax);
 // the wall-plane weights of a Neumann variant for the other drivers of the library (slab.cpp): 1 and (w = [2][K] device weights, K) when available
 int tlab_internal_dns_neumann_weights(tlab_dns_t d, int ibc, const double **w, int *K);
 }
@@ -121,6 +112,25 @@ struct tlab_dns_grid {
     tlab::ParticleState **particles;
 };
 void tlab_internal_dns_grid(tlab_dns_t d, tlab_dns_grid *out);
+
+// ---- pointwise.hip ----
+// q += dte h, q = min(max(q, lo), hi), h *= kco: the scalar update of the decomposed drivers with their bounds (pencil.cpp)
+int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi);
+
+// ---- rhs.cpp ----
+extern "C" {
+// the substep with the tail the caller hands over (driver_common.hpp: SubstepTail), behind tlab_time_substep_incompressible_explicit -- which passes
+// the driver's own settings -- and the replay of a record (deferred.cpp); throws tlab::Fail
+void tlab_internal_dns_substep(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
+                               const tlab::SubstepTail &tail);
+}
+
+// ---- dns_monitors.cpp ----
+extern "C" {
+// the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
+int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, const double *w, int nx, int ny, int nz, int ioff, int koff,
+                              double *pmax);
+}
 
 // ---- particles.hip ----
 void tlab_internal_particles_free(tlab::ParticleState *p);

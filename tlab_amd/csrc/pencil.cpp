@@ -317,7 +317,7 @@ bool finish_velocities(D *d, double dte, const SubstepTail *tail) {
     for (Rank &R : d->rk) ok(tlab_pw_sub3(R.hq[0], R.hq[1], R.hq[2], R.txc[1], R.txc[2], R.txc[3], n), "tlab_pw_sub3");
     for (Rank &R : d->rk)
         for (int i = 0; i < 3; ++i) {
-            const int ibc = (d->bcs.flow_jmin[i] == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (d->bcs.flow_jmax[i] == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
+            const int ibc = d->bcs.flow_variant(i);
             if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, R.hq[i], R.hb, R.ht, R.txc[0]), "tlab_boundary_bcs_neumann_y");
             ok(tlab_pw_set_wall_planes(R.hq[i], (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
         }
@@ -393,7 +393,7 @@ bool rhs(D *d, double dte, const SubstepTail *tail) {
     const bool finished = finish_velocities(d, dte, tail);
     for (Rank &R : d->rk) {
         auto walls = [&](double *h, int tmin, int tmax) {
-            const int ibc = (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
+            const int ibc = WallBcs::variant(tmin, tmax);
             if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, h, R.hb, R.ht, R.txc[0]), "tlab_boundary_bcs_neumann_y");
             ok(tlab_pw_set_wall_planes(h, (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
         };
@@ -662,7 +662,7 @@ bool rhs_overlapped(D *d, double dte, const SubstepTail *tail) {
         for (int i = 0; i < ns; ++i)
             pl.push_back({-1, [=]() {
                 for (Rank &R : d->rk) {
-                    const int ibc = (d->bcs.scal_jmin[i] == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (d->bcs.scal_jmax[i] == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
+                    const int ibc = d->bcs.scal_variant(i);
                     if (ibc) ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, R.hs[i], R.hb, R.ht, R.txc[4]), "tlab_boundary_bcs_neumann_y");
                     ok(tlab_pw_set_wall_planes(R.hs[i], (ibc & 1) ? R.hb : nullptr, (ibc & 2) ? R.ht : nullptr, nx, ny, kmax), "tlab_pw_set_wall_planes");
                 }

@@ -457,7 +457,6 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
     // like the coupling of the compact system, so a field is finished with zero wall tendencies by the kernel that holds its last term (Dirichlet
     // treatment), the weighted sums over the STORED tendencies next to the walls give the wall planes (k_wall_weighted) and k_wall_fix sets them.  All of
     // it is local in y: no exchange.  TLAB_NEUMANN_PLANES=0 / TLAB_SLAB_FUSED_X=0 keep the derivative pass (the Python driver's sequence).
-    auto ibc_of = [](int tmin, int tmax) { return (tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0); };
     const char *npe = std::getenv("TLAB_NEUMANN_PLANES");
     bool planes_route = tail && d->fused_x && !(npe && std::atoi(npe) == 0);
     auto weights_of = [&](Rank &R, int ibc, const double *&w, int &K) { return tlab_internal_dns_neumann_weights(dns_handle(d, R), ibc, &w, &K) == 1; };
@@ -466,9 +465,9 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
             const double *w;
             int K;
             for (int i = 0; i < 3; i += 2)
-                if (int ibc = ibc_of(d->bcs.flow_jmin[i], d->bcs.flow_jmax[i])) planes_route = planes_route && weights_of(R, ibc, w, K);
+                if (int ibc = d->bcs.flow_variant(i)) planes_route = planes_route && weights_of(R, ibc, w, K);
             for (int i = 0; i < ns; ++i)
-                if (int ibc = ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i])) planes_route = planes_route && weights_of(R, ibc, w, K);
+                if (int ibc = d->bcs.scal_variant(i)) planes_route = planes_route && weights_of(R, ibc, w, K);
         }
     }
     // wall planes of a field that was finished with zero wall tendencies
@@ -491,7 +490,7 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
     }
     std::vector<int> zfin((size_t)(3 + ns), 0);
     for (int i = 0; i < ns; ++i)
-        zfin[3 + i] = !zone_scal && tail && d->fused_x && !surface(i) && (ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]) == 0 || planes_route);
+        zfin[3 + i] = !zone_scal && tail && d->fused_x && !surface(i) && (d->bcs.scal_variant(i) == 0 || planes_route);
     // ---- diffusion + advection (:98-162) and the pressure forcing div(hq + q/dte) (:188-260) ----
     // (Measured in round 4 and dropped: the x and y terms of the forcing inside the Burgers launches that add the last term of u resp. v, as rhs.cpp
     // does on one device.  It needs u to end with its x term and v with its y term, i.e. the x and y launches split in two; on slabs of 64 planes the
@@ -581,7 +580,7 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
             for (Fd &f : F) f.g = nullptr;
         }
         for (const Fd &f : F) {
-            const int ibc = (f.tmin == TLAB_DNS_BCS_NEUMANN ? 1 : 0) + (f.tmax == TLAB_DNS_BCS_NEUMANN ? 2 : 0);
+            const int ibc = WallBcs::variant(f.tmin, f.tmax);
             if (ibc)       // needs the finished tendency (g is null here)
                 ok(tlab_boundary_bcs_neumann_y(d->g[1], ibc, nx, ny, kmax, f.h, R.hb, R.ht, R.txc[0]), "tlab_boundary_bcs_neumann_y");
             const double *pb = (ibc & 1) ? R.hb : nullptr, *pt = (ibc & 2) ? R.ht : nullptr;
@@ -604,7 +603,7 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
     if (grad_final) {   // u and w are finished by the gradient kernels themselves (no gradient array)
         for (Rank &R : d->rk) {
             ok(tlab_opr_gradient_final(1, d->g[0], nx, ny, kmax, R.txc[0], R.q[0], R.hq[0], tdte, kco, scale, R.txc[1]), "tlab_opr_gradient_final");
-            if (int ibc = ibc_of(d->bcs.flow_jmin[0], d->bcs.flow_jmax[0])) wall_fix(R, R.q[0], R.hq[0], ibc);
+            if (int ibc = d->bcs.flow_variant(0)) wall_fix(R, R.q[0], R.hq[0], ibc);
         }
     } else {
         for (Rank &R : d->rk) padd(d, R, 1, R.txc[0], nullptr, 0.0, R.txc[1], 0);
@@ -615,7 +614,7 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
     // v and the scalars do not wait for dp/dz: their update runs while the interface values travel (not with Neumann scalars, whose boundary
     // routine takes tmp1 = p as scratch)
     bool needs_bcs_routine = false;      // a field left for `finish` with a Neumann wall: BOUNDARY_BCS_NEUMANN_Y, which takes tmp1 = p as scratch
-    for (int i = 0; i < ns; ++i) needs_bcs_routine = needs_bcs_routine || (!zfin[3 + i] && ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]) != 0);
+    for (int i = 0; i < ns; ++i) needs_bcs_routine = needs_bcs_routine || (!zfin[3 + i] && d->bcs.scal_variant(i) != 0);
     const bool early_finish = grad_final && (scal_dirichlet || !needs_bcs_routine);
     if (early_finish)
         for (Rank &R : d->rk) finish(R);
@@ -625,7 +624,7 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
             const double *ph[2] = {R.lo[S_P], R.hi[S_P]};
             ok(tlab_internal_zslab_gradient_final_z(R.zplan, nx, ny, R.txc[0], ph, R.tail_left, R.head_right, R.q[2], R.hq[2], tdte, kco, scale),
                "tlab_zslab_gradient_final_z");
-            if (int ibc = ibc_of(d->bcs.flow_jmin[2], d->bcs.flow_jmax[2])) wall_fix(R, R.q[2], R.hq[2], ibc);
+            if (int ibc = d->bcs.flow_variant(2)) wall_fix(R, R.q[2], R.hq[2], ibc);
         }
     } else {
         for (Rank &R : d->rk) zpartial(d, R, 2, R.txc[0], S_P, nullptr, 0, 0.0, R.txc[3], 0);
@@ -635,7 +634,7 @@ void rhs_halo(D *d, double dte, const SubstepTail *tail) {
     // Neumann scalars the z pass finished: their wall planes
     for (int i = 0; i < ns; ++i)
         if (zfin[3 + i])
-            if (int ibc = ibc_of(d->bcs.scal_jmin[i], d->bcs.scal_jmax[i]))
+            if (int ibc = d->bcs.scal_variant(i))
                 for (Rank &R : d->rk) wall_fix(R, R.s[i], R.hs[i], ibc);
 }
 
