@@ -665,6 +665,36 @@ int tlab_device_minmax(const double *a, long long n, double *amn, double *amx);
  * tlab_init) -> a host loop.  A host array never reaches a kernel. */
 int tlab_minmax_any(const double *a, long long n, double *amn, double *amx);
 
+/* ---- plane statistics: module Averages and the covariance blocks of AVG_FLOW_XZ / AVG_SCAL_XZ ------------------------------------------------
+ * Profiles in y of fields a(nx, ny, nz), x fastest.  No driver handle.  The fields are classified like tlab_minmax_any: all in device memory -> two
+ * kernels (k_plane_partial, k_plane_final: deterministic, no atomics; the order of summation depends on (nx, ny, nz) and the 16-byte alignment of
+ * the fields alone, so a call repeats its bits); all in host memory (or no tlab_init) -> a host loop in the reference's order (k outer, i inner for
+ * a given j); a mix: TLAB_EINVAL.  Profiles, in and out, are HOST memory, ny doubles per column.  A recorded substep runs first; the calls return
+ * with the profile on the host (they synchronise the stream).  The scratch they need is the library's, grown on demand.
+ * TLAB_EINVAL: nx, ny or nz < 1, nf < 1, imom outside 1..4, ld < ny, a null pointer (p and rP may be NULL, but only together).
+ * tlab_avg_ik_v: AVG_IK_V (utils/averages.f90:301-327), local part, of nf arrays in ONE pass over them: column f of avg, at avg + f*ldavg, is
+ *   sum_{i,k} a[f](i, j, k) / real(nx*nz) -- a division, as in the reference.  a: HOST array of nf pointers.
+ * tlab_avg1v2d_v: AVG1V2D_V (:142-167), local part: the plane average of a**imom, imom = 1..4, the power as gfortran expands it:
+ *   a, a*a, (a*a)*a, (a*a)*(a*a). */
+int tlab_avg_ik_v(int nx, int ny, int nz, int nf, const double *const *a, double *avg, int ldavg);
+int tlab_avg1v2d_v(int nx, int ny, int nz, int imom, const double *a, double *avg);
+/* The covariances of AVG_FLOW_XZ (statistics/avg_flow_xz.f90:513-553, :597-654, incompressible / anelastic branch) in one pass over u, v, w (and p):
+ * with u' = u - fU(j), v' = v - fV(j), w' = w - fW(j), p' = p - rP(j), column c of out (at out + c*ldout) is the plane average of
+ *   0 Rxx = u'u'      1 Ryy            2 Rzz            3 Rxy = u'v'      4 Rxz = u'w'      5 Ryz = v'w'
+ *   6 rU3 = (u'u')u'  7 rU4 = u' (u'u')u'               8 rV3   9 rV4    10 rW3  11 rW4
+ *  12 Txxy = (u'u')v' 13 Tyyy = (v'v')v' 14 Tzzy = (w'w')v' 15 Txyy = (u'v')v' 16 Txzy = (u'v')w' 17 Tyzy = (v'v')w'
+ *  and with p != NULL   18 rP2 = p'p'   19 u'p'   20 v'p'   21 w'p'
+ * each term formed in the reference's operation order, unfused.  What the reference adds on the host afterwards (Ty1, Txyy += <u'p'>, Tyyy +=
+ * 2 <v'p'>, Tyzy += <w'p'>) stays with the caller.  18 columns without p, 22 with. */
+int tlab_avg_moments_flow(int nx, int ny, int nz, const double *u, const double *v, const double *w, const double *p, const double *fU,
+                          const double *fV, const double *fW, const double *rP, double *out, int ldout);
+/* The moments and fluxes of one scalar in AVG_SCAL_XZ (statistics/avg_scal_xz.f90:373-455), with s' = s - fS(j):
+ *   0 rS2 = s's'   1 rS3 = s'(s's')   2 rS4 = s' s'(s's')   3 Rsu = s'u'   4 Rsv = s'v'   5 Rsw = s'w'
+ *   6 Tssy1 = (s'v')s'   7 Tsuy1 = (s'u')v'   8 Tsvy1 = (s'v')v'   9 Tswy1 = (s'w')v'   and with p != NULL   10 Tsvy3 = p's'
+ * 10 columns without p, 11 with.  The PIs* terms need derivative fields and are not computed here. */
+int tlab_avg_moments_scal(int nx, int ny, int nz, const double *s, const double *u, const double *v, const double *w, const double *p,
+                          const double *fS, const double *fU, const double *fV, const double *fW, const double *rP, double *out, int ldout);
+
 /* RHS_GLOBAL_INCOMPRESSIBLE_1()   tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
  * it works on the module arrays q, s, hq, hs, txc and on dte).  q[3] = u,v,w; s[nscal]; hq[3], hs[nscal] are
  * accumulated into; txc[9] = tmp1..tmp9, each of isize_txc_field = (nx+2)*ny*nz doubles.  HOST arrays of DEVICE pointers.

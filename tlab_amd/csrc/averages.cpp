@@ -1,0 +1,147 @@
+// C ABI of the plane statistics (include/tlab_amd.h): tlab_avg_ik_v, tlab_avg1v2d_v, tlab_avg_moments_flow, tlab_avg_moments_scal.  Device arrays
+// take the kernels of averages.hip, host arrays the loop below in the reference's order; a host array never reaches a kernel, a device array is
+// never read by the host.  The programs (the terms of every output) are those of averages_host.hpp on both sides.
+#include "../../include/tlab_amd.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "averages_host.hpp"
+#include "driver_common.hpp"
+#include "kernels.hpp"
+
+#pragma clang fp contract(off)      // every multiply and add below stays as written
+
+using namespace tlab;
+
+namespace {
+
+// partials, table of means and profile of one launch: one buffer for the process, grown on demand (the calls run on the library's stream one
+// after the other)
+double *g_buf = nullptr;
+size_t g_buf_n = 0;
+double *scratch(size_t n) {
+    if (g_buf_n < n) {
+        if (g_buf) hk(hipFree(g_buf), "hipFree");
+        g_buf = nullptr; g_buf_n = 0;
+        hk(hipMalloc((void **)&g_buf, n * sizeof(double)), "hipMalloc(plane statistics)");
+        g_buf_n = n;
+    }
+    return g_buf;
+}
+
+// AVG_IK_V's loop nest for one plane (utils/averages.f90:311-320): k outer, i inner, one running sum per output, then the division
+template <class P>
+void host_planes(int nx, int ny, int nz, const double *const *f, const double *const *means, double *out, int ldout) {
+    const double denom = (double)((long long)nx * nz);
+    for (int j = 0; j < ny; ++j) {
+        double m[P::NMEAN > 0 ? P::NMEAN : 1], acc[P::NOUT], x[P::NFLD];
+        for (int i = 0; i < P::NMEAN; ++i) m[i] = means[i][j];
+        for (int o = 0; o < P::NOUT; ++o) acc[o] = 0.0;
+        for (int k = 0; k < nz; ++k) {
+            const size_t row = ((size_t)k * ny + j) * nx;
+            for (int i = 0; i < nx; ++i) {
+                for (int c = 0; c < P::NFLD; ++c) x[c] = f[c][row + i];
+                P::add(x, m, acc);
+            }
+        }
+        for (int o = 0; o < P::NOUT; ++o) out[(size_t)o * ldout + j] = acc[o] / denom;
+    }
+}
+
+// 1: every array is device memory, 0: every array is host memory (or no tlab_init: no array is the library's); a mix is refused
+bool on_device(const char *who, int n, const double *const *f) {
+    int ndev = 0;
+    if (tlab_device_ready())
+        for (int i = 0; i < n; ++i) {
+            const int on = tlab_pointer_on_device(f[i]);
+            if (on < 0) throw Fail(on, std::string(who) + ": " + tlab_last_error());
+            ndev += on ? 1 : 0;
+        }
+    if (ndev != 0 && ndev != n) throw Fail(TLAB_EINVAL, std::string(who) + ": host and device arrays in one call");
+    return ndev != 0;
+}
+
+// one program on its fields: f[nfld], means[nmean] (host profiles), out: nout columns ldout apart
+void run(bool device, int prog, int param, int nx, int ny, int nz, const double *const *f, const double *const *means, double *out, int ldout) {
+    const AvgInfo info = avg_info(prog, param);
+    if (!device) {
+        avg_dispatch(prog, param, [&](auto P) { host_planes<decltype(P)>(nx, ny, nz, f, means, out, ldout); });
+        return;
+    }
+    hipStream_t st = tlab_current_stream();
+    const size_t npart = (size_t)plane_moments_chunks(nz) * ny * info.nout, nmean = (size_t)info.nmean * ny, nprof = (size_t)info.nout * ny;
+    double *partial = scratch(npart + nmean + nprof), *dmeans = partial + npart, *prof = dmeans + nmean;
+    std::vector<double> hm(nmean), hp(nprof);      // (both live until the stream is synchronised below)
+    if (nmean) {
+        for (int i = 0; i < info.nmean; ++i) std::copy(means[i], means[i] + ny, hm.begin() + (size_t)i * ny);
+        hk(hipMemcpyAsync(dmeans, hm.data(), nmean * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(means)");
+    }
+    hk(launch_plane_moments(prog, param, nx, ny, nz, f, nmean ? dmeans : nullptr, partial, prof, st), "k_plane_partial");
+    hk(hipMemcpyAsync(hp.data(), prof, nprof * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(profile)");
+    hk(hipStreamSynchronize(st), "sync");
+    for (int o = 0; o < info.nout; ++o) std::copy(hp.begin() + (size_t)o * ny, hp.begin() + (size_t)(o + 1) * ny, out + (size_t)o * ldout);
+}
+
+void check_box(const char *who, int nx, int ny, int nz, int ld) {
+    if (nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": nx, ny, nz must be at least 1");
+    if (ld < ny) throw Fail(TLAB_EINVAL, std::string(who) + ": the leading dimension of the profiles is smaller than ny");
+}
+
+}  // namespace
+
+extern "C" {
+
+int tlab_avg_ik_v(int nx, int ny, int nz, int nf, const double *const *a, double *avg, int ldavg) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (nf < 1 || !a || !avg) throw Fail(TLAB_EINVAL, "tlab_avg_ik_v: nf < 1 or a null pointer");
+        check_box("tlab_avg_ik_v", nx, ny, nz, ldavg);
+        for (int f = 0; f < nf; ++f)
+            if (!a[f]) throw Fail(TLAB_EINVAL, "tlab_avg_ik_v: a null array");
+        const bool dev = on_device("tlab_avg_ik_v", nf, a);
+        for (int f0 = 0; f0 < nf; f0 += AVG_FIELDS_PER_LAUNCH) {
+            const int n = std::min(AVG_FIELDS_PER_LAUNCH, nf - f0);
+            run(dev, AVG_PROG_MEANS, n, nx, ny, nz, a + f0, nullptr, avg + (size_t)f0 * ldavg, ldavg);
+        }
+    }, TLAB_EINVAL);
+}
+
+int tlab_avg1v2d_v(int nx, int ny, int nz, int imom, const double *a, double *avg) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!a || !avg) throw Fail(TLAB_EINVAL, "tlab_avg1v2d_v: a null pointer");
+        if (imom < 1 || imom > 4) throw Fail(TLAB_EINVAL, "tlab_avg1v2d_v: imom must be 1 to 4");
+        check_box("tlab_avg1v2d_v", nx, ny, nz, ny);
+        run(on_device("tlab_avg1v2d_v", 1, &a), AVG_PROG_POWER, imom, nx, ny, nz, &a, nullptr, avg, ny);
+    }, TLAB_EINVAL);
+}
+
+int tlab_avg_moments_flow(int nx, int ny, int nz, const double *u, const double *v, const double *w, const double *p, const double *fU,
+                          const double *fV, const double *fW, const double *rP, double *out, int ldout) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!u || !v || !w || !fU || !fV || !fW || !out || (p == nullptr) != (rP == nullptr))
+            throw Fail(TLAB_EINVAL, "tlab_avg_moments_flow: a null pointer (p and rP may be NULL, together)");
+        check_box("tlab_avg_moments_flow", nx, ny, nz, ldout);
+        const double *f[4] = {u, v, w, p}, *m[4] = {fU, fV, fW, rP};
+        run(on_device("tlab_avg_moments_flow", p ? 4 : 3, f), AVG_PROG_FLOW, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
+    }, TLAB_EINVAL);
+}
+
+int tlab_avg_moments_scal(int nx, int ny, int nz, const double *s, const double *u, const double *v, const double *w, const double *p,
+                          const double *fS, const double *fU, const double *fV, const double *fW, const double *rP, double *out, int ldout) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!s || !u || !v || !w || !fS || !fU || !fV || !fW || !out || (p == nullptr) != (rP == nullptr))
+            throw Fail(TLAB_EINVAL, "tlab_avg_moments_scal: a null pointer (p and rP may be NULL, together)");
+        check_box("tlab_avg_moments_scal", nx, ny, nz, ldout);
+        const double *f[5] = {s, u, v, w, p}, *m[5] = {fS, fU, fV, fW, rP};
+        run(on_device("tlab_avg_moments_scal", p ? 5 : 4, f), AVG_PROG_SCAL, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
+    }, TLAB_EINVAL);
+}
+
+}  // extern "C"

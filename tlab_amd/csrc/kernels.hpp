@@ -221,6 +221,13 @@ void infrared_build_tables(const DerTables &g, std::vector<double> &tab, Infrare
 hipError_t launch_infrared_y(const double *l, double *hs, double *scr1, double *scr2, const double *tab, const InfraredCoef &C, double kappa,
                              double flux_top, double flux_bottom, int nx, int ny, int nz, hipStream_t st);
 
+// averages.hip: plane statistics (k_plane_partial + k_plane_final).  prog, param: a program of averages_host.hpp (AVG_PROG_*; param = the number of
+// fields, imom, or 1 with a pressure field); f: its fields; means: device, [nmean][ny] (NULL for MEANS and POWER); partial: device scratch,
+// plane_moments_chunks(nz) * ny * nout doubles; prof: device, [nout][ny], the result.  Nothing is copied or synchronised here.
+int plane_moments_chunks(int nz);
+hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, const double *const *f, const double *means, double *partial,
+                                double *prof, hipStream_t st);
+
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,

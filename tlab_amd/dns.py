@@ -603,6 +603,43 @@ class Dns:
                                                    lmax if locations else None), "tlab_dns_dilatation_extremes")
         return _extremes(mn, mx, lmin, lmax, locations)
 
+    def AVG_IK_V(self, a):
+        """AVG_IK_V (utils/averages.f90:301) of one field of the box: the profile of its plane averages, numpy (ny,)."""
+        from .operators import avg_ik_v
+        return avg_ik_v(self.nx, self.ny, self.nz, [a])[0]
+
+    def plane_means(self):
+        """rU, rV, rW and rS (a list, one profile per scalar) from one pass over q + s (AVG_FLOW_XZ :458-460, AVG_SCAL_XZ :358)."""
+        from .operators import avg_ik_v
+        m = avg_ik_v(self.nx, self.ny, self.nz, self.q + self.s)
+        return {"rU": m[0], "rV": m[1], "rW": m[2], "rS": [m[3 + i] for i in range(self.nscal)]}
+
+    def flow_moments(self, p=None):
+        """The covariances of AVG_FLOW_XZ that need no derivative (avg_flow_xz.f90:513-553, :597-654), incompressible: fU = rU.  Takes the
+        means first (and rP of a pressure field p), then one pass; a dict of profiles keyed by the reference's names (operators.FLOW_MOMENTS,
+        with p also FLOW_MOMENTS_P), plus the means."""
+        from .operators import avg_moments_flow, FLOW_MOMENTS, FLOW_MOMENTS_P
+        m = self.plane_means()
+        rP = self.AVG_IK_V(p) if p is not None else None
+        out = avg_moments_flow(self.nx, self.ny, self.nz, self.q[0], self.q[1], self.q[2], m["rU"], m["rV"], m["rW"], p, rP)
+        r = dict(zip(FLOW_MOMENTS + (FLOW_MOMENTS_P if p is not None else ()), out))
+        r.update(rU=m["rU"], rV=m["rV"], rW=m["rW"])
+        if p is not None:
+            r["rP"] = rP
+        return r
+
+    def scal_moments(self, is_, p=None):
+        """The moments and fluxes of scalar is_ (0-based) in AVG_SCAL_XZ (avg_scal_xz.f90:373-455), incompressible: fS = rS.  As flow_moments."""
+        from .operators import avg_moments_scal, SCAL_MOMENTS, SCAL_MOMENTS_P
+        m = self.plane_means()
+        rP = self.AVG_IK_V(p) if p is not None else None
+        out = avg_moments_scal(self.nx, self.ny, self.nz, self.s[is_], self.q[0], self.q[1], self.q[2], m["rS"][is_], m["rU"], m["rV"], m["rW"], p, rP)
+        r = dict(zip(SCAL_MOMENTS + (SCAL_MOMENTS_P if p is not None else ()), out))
+        r.update(rS=m["rS"][is_], rU=m["rU"], rV=m["rV"], rW=m["rW"])
+        if p is not None:
+            r["rP"] = rP
+        return r
+
     def begin_step(self):
         """hq = hs = 0 of TIME_RUNGEKUTTA (time.f90:212-216) without touching the arrays: the next substep overwrites them."""
         check(load().tlab_dns_begin_step(self._h), "tlab_dns_begin_step")

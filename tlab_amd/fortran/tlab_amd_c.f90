@@ -570,6 +570,29 @@ module TLab_AMD_C
             integer(c_long_long), value :: n
             real(c_double), intent(out) :: amn, amx
         end function
+        ! plane statistics (tlab_amd_averages.f90): fields of either kind (all device or all host), profiles in host memory
+        integer(c_int) function tlab_avg_ik_v(nx, ny, nz, nf, a, avg, ldavg) bind(C, name='tlab_avg_ik_v')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nf, ldavg
+            type(c_ptr), intent(in) :: a(*)
+            real(c_double), intent(out) :: avg(*)
+        end function
+        integer(c_int) function tlab_avg1v2d_v(nx, ny, nz, imom, a, avg) bind(C, name='tlab_avg1v2d_v')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, imom
+            type(c_ptr), value :: a
+            real(c_double), intent(out) :: avg(*)
+        end function
+        integer(c_int) function tlab_avg_moments_flow(nx, ny, nz, u, v, w, p, fU, fV, fW, rP, out, ldout) bind(C, name='tlab_avg_moments_flow')
+            import :: c_int, c_ptr
+            integer(c_int), value :: nx, ny, nz, ldout
+            type(c_ptr), value :: u, v, w, p, fU, fV, fW, rP, out
+        end function
+        integer(c_int) function tlab_avg_moments_scal(nx, ny, nz, s, u, v, w, p, fS, fU, fV, fW, rP, out, ldout) bind(C, name='tlab_avg_moments_scal')
+            import :: c_int, c_ptr
+            integer(c_int), value :: nx, ny, nz, ldout
+            type(c_ptr), value :: s, u, v, w, p, fS, fU, fV, fW, rP, out
+        end function
         integer(c_int) function tlab_boundary_bcs_neumann_y(plan, ibc, nx, ny, nz, u, bcs_hb, bcs_ht, tmp1) bind(C, name='tlab_boundary_bcs_neumann_y')
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, u, bcs_hb, bcs_ht, tmp1

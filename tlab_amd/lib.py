@@ -140,6 +140,10 @@ SIGNATURES = {
     "tlab_dns_dilatation_extremes": (c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), _dp, _dp, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "tlab_device_minmax": (c_int, [c_vp, ctypes.c_longlong, _dp, _dp]),
     "tlab_minmax_any": (c_int, [c_vp, ctypes.c_longlong, _dp, _dp]),
+    "tlab_avg_ik_v": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_vp), c_vp, c_int]),
+    "tlab_avg1v2d_v": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "tlab_avg_moments_flow": (c_int, [c_int, c_int, c_int] + [c_vp] * 9 + [c_int]),
+    "tlab_avg_moments_scal": (c_int, [c_int, c_int, c_int] + [c_vp] * 11 + [c_int]),
     "tlab_opr_burgers_add": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tlab_opr_burgers_add_n": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_int, _dp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_int]),
     "tlab_opr_partial_add": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_int, c_vp, c_vp]),

@@ -308,3 +308,85 @@ def TLab_Transpose(a, nra, nca, b):
     """b(nca, nra) = transpose of Fortran a(nra, nca); bit-exact."""
     _use_torch_stream()
     check(load().tlab_transpose(_ptr(a, nra * nca, "a"), nra, nca, _ptr(b, nra * nca, "b")), "tlab_transpose")
+
+
+# ---- plane statistics: module Averages and the covariance blocks of AVG_FLOW_XZ / AVG_SCAL_XZ (include/tlab_amd.h) ----------------------------
+FLOW_MOMENTS = ("Rxx", "Ryy", "Rzz", "Rxy", "Rxz", "Ryz", "rU3", "rU4", "rV3", "rV4", "rW3", "rW4", "Txxy", "Tyyy", "Tzzy", "Txyy", "Txzy", "Tyzy")
+FLOW_MOMENTS_P = ("rP2", "up", "vp", "wp")          # <p'p'>, <u'p'>, <v'p'> (Ty2), <w'p'>
+SCAL_MOMENTS = ("rS2", "rS3", "rS4", "Rsu", "Rsv", "Rsw", "Tssy1", "Tsuy1", "Tsvy1", "Tswy1")
+SCAL_MOMENTS_P = ("Tsvy3",)
+
+
+def _field_ptr(a, n, name, keep):
+    """the address of a field of n float64: a contiguous torch tensor (device or host) or a numpy array; None -> NULL"""
+    if a is None:
+        return c_vp(0)
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.float64 or not a.flags.c_contiguous or a.size < n:
+            raise TlabError("%s must be a contiguous float64 array of at least %d elements" % (name, n))
+        keep.append(a)
+        return c_vp(a.ctypes.data)
+    import torch
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or not a.is_contiguous() or a.numel() < n:
+        raise TlabError("%s must be a contiguous float64 tensor of at least %d elements" % (name, n))
+    keep.append(a)
+    return c_vp(a.data_ptr())
+
+
+def _profile(a, ny, name, keep):
+    if a is None:
+        return c_vp(0)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != (ny,):
+        raise TlabError("%s must hold ny = %d values" % (name, ny))
+    keep.append(a)
+    return c_vp(a.ctypes.data)
+
+
+def _stream_if_device(fields):
+    if any(f is not None and not isinstance(f, np.ndarray) and f.is_cuda for f in fields):
+        _use_torch_stream()
+
+
+def avg_ik_v(nx, ny, nz, fields):
+    """AVG_IK_V (utils/averages.f90:301) of several fields in one pass: numpy (len(fields), ny).  fields: torch tensors or numpy arrays."""
+    keep, n = [], nx * ny * nz
+    fields = list(fields)
+    ptrs = (c_vp * max(len(fields), 1))(*[_field_ptr(f, n, "field %d" % i, keep).value for i, f in enumerate(fields)])
+    out = np.zeros((max(len(fields), 1), ny))
+    _stream_if_device(fields)
+    check(load().tlab_avg_ik_v(nx, ny, nz, len(fields), ptrs, c_vp(out.ctypes.data), ny), "tlab_avg_ik_v")
+    return out[:len(fields)]
+
+
+def avg1v2d_v(nx, ny, nz, imom, a):
+    """AVG1V2D_V (utils/averages.f90:142): the plane average of a**imom, numpy (ny,)."""
+    keep = []
+    out = np.zeros(ny)
+    _stream_if_device([a])
+    check(load().tlab_avg1v2d_v(nx, ny, nz, int(imom), _field_ptr(a, nx * ny * nz, "a", keep), c_vp(out.ctypes.data)), "tlab_avg1v2d_v")
+    return out
+
+
+def avg_moments_flow(nx, ny, nz, u, v, w, fU, fV, fW, p=None, rP=None):
+    """The covariances of AVG_FLOW_XZ that need no derivative: numpy (18 or 22, ny), rows in the order of FLOW_MOMENTS (+ FLOW_MOMENTS_P)."""
+    keep, n = [], nx * ny * nz
+    out = np.zeros((22 if p is not None else 18, ny))
+    _stream_if_device([u, v, w, p])
+    check(load().tlab_avg_moments_flow(nx, ny, nz, _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep), _field_ptr(w, n, "w", keep),
+                                       _field_ptr(p, n, "p", keep), _profile(fU, ny, "fU", keep), _profile(fV, ny, "fV", keep),
+                                       _profile(fW, ny, "fW", keep), _profile(rP, ny, "rP", keep), c_vp(out.ctypes.data), ny),
+          "tlab_avg_moments_flow")
+    return out
+
+
+def avg_moments_scal(nx, ny, nz, s, u, v, w, fS, fU, fV, fW, p=None, rP=None):
+    """The moments and fluxes of one scalar in AVG_SCAL_XZ: numpy (10 or 11, ny), rows in the order of SCAL_MOMENTS (+ SCAL_MOMENTS_P)."""
+    keep, n = [], nx * ny * nz
+    out = np.zeros((11 if p is not None else 10, ny))
+    _stream_if_device([s, u, v, w, p])
+    check(load().tlab_avg_moments_scal(nx, ny, nz, _field_ptr(s, n, "s", keep), _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep),
+                                       _field_ptr(w, n, "w", keep), _field_ptr(p, n, "p", keep), _profile(fS, ny, "fS", keep),
+                                       _profile(fU, ny, "fU", keep), _profile(fV, ny, "fV", keep), _profile(fW, ny, "fW", keep),
+                                       _profile(rP, ny, "rP", keep), c_vp(out.ctypes.data), ny), "tlab_avg_moments_scal")
+    return out
