@@ -9,19 +9,23 @@ guard planes holding a sentinel, overwritten results start as NaN.
 
 Not reachable through the public ABI, and therefore not covered here:
  - the in-place scalar finish of the Burgers phase B (ffin) and halo planes in buffers of their own exist only on tlab_internal_*: they stay with
-   tests/test_gpu_slab_native.py;
- - on a uniform periodic z the separator row of a slab equals its right neighbour's (aS == aSn, binv == binvn) and koffset does not change the
-   tables: a kernel that swapped them, or a plan built for the wrong koffset, passes this file.  A blind spot, named rather than covered.
+   tests/test_gpu_slab_native.py.
+On a uniform periodic z the separator row of a slab equals its right neighbour's (aS == aSn, binv == binvn) and koffset does not change the
+tables: a kernel that swapped them, or a plan built for the wrong koffset, would pass those cases.  The `varying` cases (VARYING, tables of
+tests/periodic_tables.py whose rows all differ, device plan and oracle from the same arrays) close that: each slab's plan is built for its own
+koffset from rows no other slab has, and each separator row differs from its neighbour's; tests/test_periodic_tables_host.py holds the negative
+control (the oracle with slab 0's rows exchanged with slab 1's differs by more than 1e-3).
 The experiment switches TLAB_ZSLAB_DUAL / _EARLY / _M are read once per process and are left alone."""
 import ctypes
 
 import numpy as np
 import pytest
 from conftest import rel_err
+from guarded import Guarded, SENT, bits_equal      # noqa: F401
+import periodic_tables as PT
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
-SENT = -2.5e+300            # guard planes
 DTE, KCO = 2.0e-3, -5.0 / 9.0
 NU = (1.0 / 500.0, 1.0 / 350.0, 1.0 / 900.0, 1.0 / 120.0)
 
@@ -32,6 +36,8 @@ SLABS = {"k64_16x4_P3": (64, 0, 3), "k64_32x2_P2": (64, 32, 2), "k80_16x5_P2": (
 PLANES = {"7x5": (7, 5), "20x5": (20, 5), "64x8": (64, 8), "64x9": (64, 9)}
 SHAPES = [(s, "20x5") for s in SLABS] + [(s, p) for p in ("7x5", "64x8", "64x9") for s in ("k64_16x4_P3", "k96_32x3_P2")]
 GRAD_SHAPES = [(s, "20x5") for s in SLABS] + [(s, "7x5") for s in ("k64_16x4_P3", "k96_32x3_P2")]
+# tables whose rows all differ (tests/periodic_tables.py): 3 slabs of 64 planes, 2 of 96, 128 (16-row sub-chunks) and 256
+VARYING = [(s, p) for s in ("k64_16x4_P3", "k96_32x3_P2", "k128_16x8_P2", "k256_32x8_P2") for p in ("20x5", "7x5")]
 SCHEMES = [(4, 4), (6, 6)]         # beside the default (6, 7); (5, 7) is pentadiagonal and refused
 
 
@@ -64,20 +70,33 @@ def znodes(nz, periodic=True):
     return np.arange(nz) / nz * 2.0 if periodic else np.arange(nz) / (nz - 1) * 2.0
 
 
-def oracle_plan(nz, m1=6, m2=7):
+def oracle_plan(nz, m1=6, m2=7, kind=None):
+    """kind = None: the plan of the uniform grid; else the tables of tests/periodic_tables.py of that kind"""
     from oracle import tlab_oracle as O
+    if kind is not None:
+        return PT.oracle_plan(nz, kind, (m1, m2))
     if (nz, m1, m2) not in _OG:
         _OG[nz, m1, m2] = O.FdmPlan(znodes(nz), True, True, m1, m2)
     return _OG[nz, m1, m2]
 
 
-def device_plan(L, nz, m1=6, m2=7, periodic=True):
+def device_plan(L, nz, m1=6, m2=7, periodic=True, kind=None):
+    """kind = None: tlab_fdm_plan_create; else tlab_fdm_plan_create_from_arrays on the arrays of oracle_plan(nz, m1, m2, kind)"""
     from tlab_amd.lib import check, c_vp
-    key = (nz, m1, m2, periodic)
+    key = (nz, m1, m2, periodic, kind)
     if key not in _GZ:
         h, z = c_vp(0), znodes(nz, periodic)
-        check(L.tlab_fdm_plan_create(ctypes.byref(h), nz, z.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(periodic), 1, m1, m2, 0.1),
-              "tlab_fdm_plan_create")
+        if kind is None:
+            check(L.tlab_fdm_plan_create(ctypes.byref(h), nz, z.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(periodic), 1, m1, m2, 0.1),
+                  "tlab_fdm_plan_create")
+        else:
+            assert periodic
+            dp = ctypes.POINTER(ctypes.c_double)
+            tab = [np.asfortranarray(a, dtype=np.float64) for a in PT.host_tables(oracle_plan(nz, m1, m2, kind))]
+            tab[0], tab[2] = np.asfortranarray(tab[0][:, :3]), np.asfortranarray(tab[2][:, :3])
+            check(L.tlab_fdm_plan_create_from_arrays(ctypes.byref(h), nz, 1, 0, 3, tab[1].shape[1], tab[0].ctypes.data_as(dp), tab[1].ctypes.data_as(dp),
+                                                     3, tab[3].shape[1] - 3, tab[2].ctypes.data_as(dp), tab[3].ctypes.data_as(dp)),
+                  "tlab_fdm_plan_create_from_arrays")
         _GZ[key] = h
     return _GZ[key]
 
@@ -95,21 +114,21 @@ def field(nx, ny, nz, seed):
     return _FIELD[key]
 
 
-def ref_partial(nx, ny, nz, u, key, m=(6, 7)):
+def ref_partial(nx, ny, nz, u, key, m=(6, 7), kind=None):
     from oracle import tlab_oracle as O
-    key = ("p1", nx, ny, nz, m) + key
+    key = ("p1", nx, ny, nz, m, kind) + key
     if key not in _REF:
-        r = O.opr_partial(3, O.OPR_P1, nx, ny, nz, 0, oracle_plan(nz, *m), u)[0]
+        r = O.opr_partial(3, O.OPR_P1, nx, ny, nz, 0, oracle_plan(nz, *m, kind=kind), u)[0]
         r.setflags(write=False)
         _REF[key] = r
     return _REF[key]
 
 
-def ref_burgers(nx, ny, nz, nu, s, vel, key, m=(6, 7)):
+def ref_burgers(nx, ny, nz, nu, s, vel, key, m=(6, 7), kind=None):
     from oracle import tlab_oracle as O
-    key = ("burgers", nx, ny, nz, m, nu) + key
+    key = ("burgers", nx, ny, nz, m, kind, nu) + key
     if key not in _REF:
-        r = O.opr_burgers(3, nx, ny, nz, 0, oracle_plan(nz, *m), nu, s, vel)[0]
+        r = O.opr_burgers(3, nx, ny, nz, 0, oracle_plan(nz, *m, kind=kind), nu, s, vel)[0]
         r.setflags(write=False)
         _REF[key] = r
     return _REF[key]
@@ -118,51 +137,22 @@ def ref_burgers(nx, ny, nz, nu, s, vel, key, m=(6, 7)):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # the ring of slabs on one device
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-class Guarded:
-    """n doubles on the device between two guard zones of g doubles holding SENT."""
-
-    def __init__(self, n, g, fill):
-        import torch
-        self.n, self.g = int(n), int(g)
-        self.t = torch.full((self.n + 2 * self.g,), SENT, dtype=torch.float64, device="cuda")
-        if isinstance(fill, np.ndarray):
-            self.body.copy_(torch.from_numpy(np.array(fill, dtype=np.float64)))       # (a copy: the shared inputs are read-only)
-        else:
-            self.body.fill_(fill)
-
-    @property
-    def body(self):
-        return self.t[self.g:self.g + self.n]
-
-    def ptr(self, offset=0):
-        from tlab_amd.lib import c_vp
-        return c_vp(self.t.data_ptr() + 8 * (self.g + int(offset)))
-
-    def host(self):
-        return self.body.cpu().numpy()
-
-    def guards_intact(self):
-        h = self.t.cpu().numpy()
-        return bool(np.all(h[:self.g] == SENT) and np.all(h[self.g + self.n:] == SENT))
-
-
 class Ring:
-    def __init__(self, L, slab, plane, m=(6, 7)):
+    def __init__(self, L, slab, plane, m=(6, 7), kind=None):
+        """kind: the tables of the z direction (None: the uniform grid's; "varying": rows that all differ), for the device plan and the oracle alike"""
         from tlab_amd.lib import check, c_vp
-        self.L = L
+        self.L, self.kind = L, kind
         self.kmax, self.chunk, self.P = SLABS[slab]
         self.nx, self.ny = PLANES[plane]
         self.nz, self.nl, self.m = self.kmax * self.P, self.nx * self.ny, m
         self.plans = []
-        gz = device_plan(L, self.nz, *m)
+        gz = device_plan(L, self.nz, *m, kind=kind)
         for r in range(self.P):
             h = c_vp(0)
-            check(L.tlab_zslab_plan_create(ctypes.byref(h), gz, self.kmax, r * self.kmax, self.chunk), "tlab_zslab_plan_create")     # M x C accepted
+            # M x C accepted; with `varying` tables the separator coupling stays below the plan's 1e-19 limit at the full amplitude for every slab used
+            # here (worked out in numpy from the tables: 2.5e-27 and 8.4e-24 for the two systems at kmax = 64, the thinnest; every plan was accepted):
+            # no slab needed a lower amplitude
+            check(L.tlab_zslab_plan_create(ctypes.byref(h), gz, self.kmax, r * self.kmax, self.chunk), "tlab_zslab_plan_create")
             self.plans.append(h)
 
     def close(self):
@@ -221,8 +211,8 @@ class Operand:
 def ring(L, request):
     made = []
 
-    def make(slab, plane, m=(6, 7)):
-        made.append(Ring(L, slab, plane, m))
+    def make(slab, plane, m=(6, 7), kind=None):
+        made.append(Ring(L, slab, plane, m, kind))
         return made[-1]
     yield make
     for r in made:
@@ -270,13 +260,13 @@ def check_overwrite_and_accumulate(got, got_acc, ref, prior, what):
 def partial_cases(R, m=(6, 7)):
     nx, ny, nz = R.nx, R.ny, R.nz
     u, ub, prior = R.field(1), R.field(2), R.field(9)
-    tag = "partial_z %dx%d kmax=%d chunk=%d P=%d scheme=%s" % (nx, ny, R.kmax, R.chunk, R.P, m)
+    tag = "partial_z %dx%d kmax=%d chunk=%d P=%d scheme=%s%s" % (nx, ny, R.kmax, R.chunk, R.P, m, " %s tables" % R.kind if R.kind else "")
     got, acc = run_partial(R, u, None, 0.0, prior, tag)
-    check_overwrite_and_accumulate(got, acc, ref_partial(nx, ny, nz, u, (1,), m), prior, tag)
+    check_overwrite_and_accumulate(got, acc, ref_partial(nx, ny, nz, u, (1,), m, R.kind), prior, tag)
     scale = 1.0 / DTE
     comb = u + scale * ub
     got, acc = run_partial(R, u, ub, scale, prior, tag + " ub")
-    check_overwrite_and_accumulate(got, acc, ref_partial(nx, ny, nz, comb, (1, 2, scale), m), prior, tag + " ub")
+    check_overwrite_and_accumulate(got, acc, ref_partial(nx, ny, nz, comb, (1, 2, scale), m, R.kind), prior, tag + " ub")
 
 
 @pytest.mark.parametrize("slab,plane", SHAPES, ids=_ids(SHAPES))
@@ -311,15 +301,27 @@ def run_burgers(R, nu, s, vel, prior, what):
 def burgers_cases(R, m=(6, 7)):
     nx, ny, nz = R.nx, R.ny, R.nz
     s, vel, prior = R.field(3), R.field(4), R.field(9)
-    tag = "burgers_z %dx%d kmax=%d chunk=%d P=%d scheme=%s" % (nx, ny, R.kmax, R.chunk, R.P, m)
+    tag = "burgers_z %dx%d kmax=%d chunk=%d P=%d scheme=%s%s" % (nx, ny, R.kmax, R.chunk, R.P, m, " %s tables" % R.kind if R.kind else "")
     got, acc, _, _ = run_burgers(R, NU[0], s, vel, prior, tag)
-    check_overwrite_and_accumulate(got, acc, ref_burgers(nx, ny, nz, NU[0], s, vel, (3, 4), m), prior, tag)
+    check_overwrite_and_accumulate(got, acc, ref_burgers(nx, ny, nz, NU[0], s, vel, (3, 4), m, R.kind), prior, tag)
 
 
 @pytest.mark.parametrize("slab,plane", SHAPES, ids=_ids(SHAPES))
 def test_burgers_z(ring, slab, plane):
     """tlab_zslab_burgers_z with distinct s and vel; overwrite against the oracle, accumulation bit for bit."""
     burgers_cases(ring(slab, plane))
+
+
+@pytest.mark.parametrize("slab,plane", VARYING, ids=_ids(VARYING))
+def test_partial_z_varying_tables(ring, slab, plane):
+    """test_partial_z on tables whose rows all differ: every slab's plan from rows of its own, every separator row unlike its neighbour's."""
+    partial_cases(ring(slab, plane, kind="varying"))
+
+
+@pytest.mark.parametrize("slab,plane", VARYING, ids=_ids(VARYING))
+def test_burgers_z_varying_tables(ring, slab, plane):
+    """test_burgers_z on tables whose rows all differ (both systems, each with its own rows)."""
+    burgers_cases(ring(slab, plane, kind="varying"))
 
 
 @pytest.mark.parametrize("slab,plane", SHAPES, ids=_ids(SHAPES))
