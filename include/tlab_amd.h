@@ -694,6 +694,68 @@ int tlab_avg_moments_flow(int nx, int ny, int nz, const double *u, const double 
  * 10 columns without p, 11 with.  The PIs* terms need derivative fields and are not computed here. */
 int tlab_avg_moments_scal(int nx, int ny, int nz, const double *s, const double *u, const double *v, const double *w, const double *p,
                           const double *fS, const double *fU, const double *fV, const double *fW, const double *rP, double *out, int ldout);
+/* The groups of AVG_FLOW_XZ on the nine velocity derivatives (Section 3, statistics/avg_flow_xz.f90:988-1248, and the pressure strain :681-699), in
+ * three passes over them instead of about 60 temporaries and reductions.  grad: HOST array of 9 pointers dudx dudy dudz dvdx dvdy dvdz dwdx dwdy
+ * dwdz; with d = dudx + dvdy + dwdz, c23 = 2.0/3.0, column c of out (at out + c*ldout) is the plane average of
+ *  first pass (no means)
+ *   0 vortx = dwdy - dvdz   1 vorty = dudz - dwdx   2 vortz = dvdx - dudy
+ *   3 Tau_yy = dvdy*2.0 - dudx - dwdz   4 Tau_xy = dudy + dvdx   5 Tau_yz = dvdz + dwdy                                     (RAW)
+ *  second pass (means rU_y rV_y rW_y and columns 0-2)
+ *   6-32 U_x2 U_x3 U_x4  V_y.  W_z.  U_y.  U_z.  V_x.  V_z.  W_x.  W_y.: a*a, (a*a)*a, ((a*a)*a)*a of a = the derivative, the y-derivatives
+ *        minus rU_y / rV_y / rW_y                                                                                           (:1021-1106)
+ *   33 U_ii2 = (d - rV_y)*(d - rV_y)          34-36 vortx2 vorty2 vortz2 = (vort - column 0..2)**2                        (:1110, :993-1010)
+ *   37 Phi (RAW) = dudx**2 + dvdy**2 + dwdz**2 + 0.5*((dudy+dvdx)**2 + (dudz+dwdx)**2 + (dvdz+dwdy)**2) - d**2/3.0          (:1136)
+ *   38-43 Exx Eyy Ezz Exy Exz Eyz (RAW), the expressions of :1145-1176, each with p = d*c23
+ *  third pass (means: columns 3-5, fU fV fW (, rP)); t22 = (raw_yy - Tau_yy)*c23, t12 = raw_xy - Tau_xy, t23 = raw_yz - Tau_yz
+ *   44 Txxy_v = t12 u'  45 Tyyy_v = t22 v'  46 Tzzy_v = t23 w'  47 Txyy_v = t22 u' + t12 v'  48 Txzy_v = t23 u' + t12 w'
+ *   49 Tyzy_v = t23 v' + t22 w'                                                                                          (:1212-1245)
+ *   and with p != NULL   50-52 PIxx PIyy PIzz (RAW) = p' dudx, p' dvdy, p' dwdz   53 PIxy = p'(dudy+dvdx)  54 PIxz = p'(dudz+dwdx)
+ *   55 PIyz = p'(dvdz+dwdy)                                                                                        (:681-683, :697-699)
+ * 50 columns without p, 56 with.  Constant transport: the vis factors of EQNS_TRANS_POWERLAW / SUTHERLAND are not applied.  RAW = before what
+ * the reference applies to the profile on the host, which stays with the caller:
+ *   Phi = Phi*visc*2 (:1140)   Tau_yy = Tau_yy*visc*c23, Tau_xy = Tau_xy*visc, Tau_yz = Tau_yz*visc (:1187, :1195, :1203)
+ *   Txxy -= Txxy_v*visc*2, Tyyy -= Tyyy_v*visc*2, Tzzy -= Tzzy_v*visc*2, Ty3 -= (each of the three)*visc (:1215-1230)
+ *   Txyy -= Txyy_v*visc, Txzy -= Txzy_v*visc, Tyzy -= Tyzy_v*visc (:1236-1248)
+ *   Exx = (Exx*visc - Tau_xy*rU_y)*2, Eyy = (Eyy*visc - Tau_yy*rV_y)*2, Ezz = (Ezz*visc - Tau_yz*rW_y)*2, Exy = Exy*visc - Tau_xy*rV_y -
+ *   Tau_yy*rU_y, Exz = Exz*visc - Tau_xy*rW_y - Tau_yz*rU_y, Eyz = Eyz*visc - Tau_yy*rW_y - Tau_yz*rV_y (:1263-1268, the finished Tau)
+ *   PIxx = PIxx*2, PIyy = PIyy*2, PIzz = PIzz*2 (:687-689)
+ * tlab_avg_ugradp: the plane average of u*dpdx + v*dpdy + w*dpdz (:673), one column of ny.
+ * tlab_avg_gradients_scal: the same for one scalar (statistics/avg_scal_xz.f90); grads: HOST array of 3 pointers dsdx dsdy dsdz
+ *   0 Fy (RAW) = dsdy (:738)   1 Ess (RAW) = dsdx*dsdx + dsdy*dsdy + dsdz*dsdz (:607)
+ *   2-10 S_x2 S_y2 S_z2 S_x3 S_y3 S_z3 S_x4 S_y4 S_z4, the chains of :714-730, y minus rS_y
+ *   11 Tssy2 (RAW) = (dsdy - Fy) s'   12-14 Tsuy2_d Tsvy2_d Tswy2_d = (dsdy - Fy) u', v', w' (:742-745, Fy = column 0)
+ *   and with p != NULL (then fS_y is needed too)   15 PIsu = p' dsdx   16 PIsv = p'(dsdy - fS_y)   17 PIsw = p' dsdz (:451-453)
+ *   15 columns without p, 18 with.  The caller's lines: Ess = Ess*diff*2 (:610), Tssy2 = -Tssy2*diff*2 (:748), Tsuy2 -= Tsuy2_d*diff, Tsvy2 -=
+ *   Tsvy2_d*diff, Tswy2 -= Tswy2_d*diff (:750-754), Fy = Fy*diff (:756). */
+int tlab_avg_gradients_flow(int nx, int ny, int nz, const double *const *grad, const double *u, const double *v, const double *w, const double *p,
+                            const double *fU, const double *fV, const double *fW, const double *rP, const double *rU_y, const double *rV_y,
+                            const double *rW_y, double *out, int ldout);
+int tlab_avg_ugradp(int nx, int ny, int nz, const double *u, const double *v, const double *w, const double *dpdx, const double *dpdy,
+                    const double *dpdz, double *out);
+int tlab_avg_gradients_scal(int nx, int ny, int nz, const double *const *grads, const double *s, const double *u, const double *v, const double *w,
+                            const double *p, const double *fS, const double *fU, const double *fV, const double *fW, const double *rP,
+                            const double *rS_y, const double *fS_y, double *out, int ldout);
+/* One pass of the above on its own, for a decomposed host that reduces the profiles of a pass over its ranks before the next pass takes them as
+ * means (AVG_IK_V's MPI_ALLREDUCE): pass 1-3 = the passes of tlab_avg_gradients_flow, 4-5 = those of tlab_avg_gradients_scal; with_p for passes
+ * 3 and 5.  fields, means: HOST arrays of pointers in the order the pass reads them; out: the columns of that pass alone, from column 0.
+ *   pass  fields                                   means                                      columns
+ *   1     the 9 gradients                          -                                          6  (0-5 above)
+ *   2     the 9 gradients                          rU_y rV_y rW_y vortx vorty vortz           38 (6-43)
+ *   3     the 9 gradients, u v w (, p)             Tau_yy Tau_xy Tau_yz (raw) fU fV fW (, rP)  6 or 12 (44-55)
+ *   4     dsdx dsdy dsdz                           rS_y                                       11 (0-10)
+ *   5     dsdy s u v w (, p dsdx dsdz)             Fy (raw) fS fU fV fW (, rP fS_y)            4 or 7 (11-17) */
+int tlab_avg_gradients_pass(int pass, int with_p, int nx, int ny, int nz, const double *const *fields, const double *const *means, double *out,
+                            int ldout);
+/* The same on a driver, with the derivatives of Section 3 (:976-986) in front: q[3], txc[9] HOST arrays of DEVICE pointers.  With p the three
+ * derivatives of p go to txc[6..8] first (:670-672) and ugradp is written as column 56 (out holds 57 columns then, 50 without p); then the nine
+ * OPR_Partial_{X,Y,Z}(OPR_P1) of u, v, w with the driver's plans, bcs = 0, into txc[0..8] = dudx .. dwdz, which hold them on return; then
+ * tlab_avg_gradients_flow on them.  tlab_dns_avg_gradients_scal: dsdx dsdy dsdz of s into txc[0..2], then tlab_avg_gradients_scal. */
+int tlab_dns_avg_gradients_flow(tlab_dns_t d, double *const *q, const double *p, double *const *txc, const double *fU, const double *fV,
+                                const double *fW, const double *rP, const double *rU_y, const double *rV_y, const double *rW_y, double *out,
+                                int ldout);
+int tlab_dns_avg_gradients_scal(tlab_dns_t d, const double *s, double *const *q, const double *p, double *const *txc, const double *fS,
+                                const double *fU, const double *fV, const double *fW, const double *rP, const double *rS_y, const double *fS_y,
+                                double *out, int ldout);
 
 /* RHS_GLOBAL_INCOMPRESSIBLE_1()   tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
  * it works on the module arrays q, s, hq, hs, txc and on dte).  q[3] = u,v,w; s[nscal]; hq[3], hs[nscal] are

@@ -1,4 +1,6 @@
-// C ABI of the plane statistics (include/tlab_amd.h): tlab_avg_ik_v, tlab_avg1v2d_v, tlab_avg_moments_flow, tlab_avg_moments_scal.  Device arrays
+// C ABI of the plane statistics (include/tlab_amd.h): tlab_avg_ik_v, tlab_avg1v2d_v, tlab_avg_moments_flow, tlab_avg_moments_scal and the gradient
+// statistics tlab_avg_gradients_flow, tlab_avg_ugradp, tlab_avg_gradients_scal, tlab_avg_gradients_pass (several programs one after the other:
+// the profiles of one pass are the means of the next).  Device arrays
 // take the kernels of averages.hip, host arrays the loop below in the reference's order; a host array never reaches a kernel, a device array is
 // never read by the host.  The programs (the terms of every output) are those of averages_host.hpp on both sides.
 #include "../../include/tlab_amd.h"
@@ -141,6 +143,80 @@ int tlab_avg_moments_scal(int nx, int ny, int nz, const double *s, const double 
         check_box("tlab_avg_moments_scal", nx, ny, nz, ldout);
         const double *f[5] = {s, u, v, w, p}, *m[5] = {fS, fU, fV, fW, rP};
         run(on_device("tlab_avg_moments_scal", p ? 5 : 4, f), AVG_PROG_SCAL, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
+    }, TLAB_EINVAL);
+}
+
+// One pass of the gradient statistics: the program of pass 1-3 (flow) or 4-5 (scalar) on its own fields and means, in the program's order
+// (averages_host.hpp).  A decomposed host reduces the profiles of one pass over its ranks before it hands them to the next as means.
+int tlab_avg_gradients_pass(int pass, int with_p, int nx, int ny, int nz, const double *const *fields, const double *const *means, double *out,
+                            int ldout) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        const char *who = "tlab_avg_gradients_pass";
+        static const int progs[5] = {AVG_PROG_GRAD_FLOW1, AVG_PROG_GRAD_FLOW2, AVG_PROG_GRAD_FLOW3, AVG_PROG_GRAD_SCAL1, AVG_PROG_GRAD_SCAL2};
+        if (pass < 1 || pass > 5) throw Fail(TLAB_EINVAL, std::string(who) + ": pass must be 1 to 5");
+        const AvgInfo info = avg_info(progs[pass - 1], with_p ? 1 : 0);
+        if (!fields || !out || (info.nmean > 0 && !means)) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
+        check_box(who, nx, ny, nz, ldout);
+        for (int i = 0; i < info.nfld; ++i)
+            if (!fields[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
+        for (int i = 0; i < info.nmean; ++i)
+            if (!means[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null profile");
+        run(on_device(who, info.nfld, fields), progs[pass - 1], with_p ? 1 : 0, nx, ny, nz, fields, means, out, ldout);
+    }, TLAB_EINVAL);
+}
+
+int tlab_avg_gradients_flow(int nx, int ny, int nz, const double *const *grad, const double *u, const double *v, const double *w, const double *p,
+                            const double *fU, const double *fV, const double *fW, const double *rP, const double *rU_y, const double *rV_y,
+                            const double *rW_y, double *out, int ldout) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        const char *who = "tlab_avg_gradients_flow";
+        if (!grad || !u || !v || !w || !fU || !fV || !fW || !rU_y || !rV_y || !rW_y || !out || (p == nullptr) != (rP == nullptr))
+            throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer (p and rP may be NULL, together)");
+        check_box(who, nx, ny, nz, ldout);
+        const double *f[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, u, v, w, p};
+        for (int i = 0; i < 9; ++i) {
+            if (!grad[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null gradient array");
+            f[i] = grad[i];
+        }
+        const bool dev = on_device(who, p ? 13 : 12, f);
+        auto col = [&](int c) { return out + (size_t)c * ldout; };
+        run(dev, AVG_PROG_GRAD_FLOW1, 0, nx, ny, nz, f, nullptr, col(0), ldout);
+        const double *m2[6] = {rU_y, rV_y, rW_y, col(0), col(1), col(2)};
+        run(dev, AVG_PROG_GRAD_FLOW2, 0, nx, ny, nz, f, m2, col(6), ldout);
+        const double *m3[7] = {col(3), col(4), col(5), fU, fV, fW, rP};
+        run(dev, AVG_PROG_GRAD_FLOW3, p ? 1 : 0, nx, ny, nz, f, m3, col(44), ldout);
+    }, TLAB_EINVAL);
+}
+
+int tlab_avg_ugradp(int nx, int ny, int nz, const double *u, const double *v, const double *w, const double *dpdx, const double *dpdy,
+                    const double *dpdz, double *out) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!u || !v || !w || !dpdx || !dpdy || !dpdz || !out) throw Fail(TLAB_EINVAL, "tlab_avg_ugradp: a null pointer");
+        check_box("tlab_avg_ugradp", nx, ny, nz, ny);
+        const double *f[6] = {u, v, w, dpdx, dpdy, dpdz};
+        run(on_device("tlab_avg_ugradp", 6, f), AVG_PROG_UGRADP, 0, nx, ny, nz, f, nullptr, out, ny);
+    }, TLAB_EINVAL);
+}
+
+int tlab_avg_gradients_scal(int nx, int ny, int nz, const double *const *grads, const double *s, const double *u, const double *v, const double *w,
+                            const double *p, const double *fS, const double *fU, const double *fV, const double *fW, const double *rP,
+                            const double *rS_y, const double *fS_y, double *out, int ldout) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        const char *who = "tlab_avg_gradients_scal";
+        if (!grads || !grads[0] || !grads[1] || !grads[2] || !s || !u || !v || !w || !fS || !fU || !fV || !fW || !rS_y || !out ||
+            (p == nullptr) != (rP == nullptr) || (p && !fS_y))
+            throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer (p and rP may be NULL, together; fS_y is needed with p)");
+        check_box(who, nx, ny, nz, ldout);
+        const double *all[8] = {grads[0], grads[1], grads[2], s, u, v, w, p}, *f[8] = {grads[1], s, u, v, w, p, grads[0], grads[2]};
+        const bool dev = on_device(who, p ? 8 : 7, all);
+        auto col = [&](int c) { return out + (size_t)c * ldout; };
+        run(dev, AVG_PROG_GRAD_SCAL1, 0, nx, ny, nz, grads, &rS_y, col(0), ldout);
+        const double *m2[7] = {col(0), fS, fU, fV, fW, rP, fS_y};
+        run(dev, AVG_PROG_GRAD_SCAL2, p ? 1 : 0, nx, ny, nz, f, m2, col(11), ldout);
     }, TLAB_EINVAL);
 }
 

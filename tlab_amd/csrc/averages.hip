@@ -1,13 +1,16 @@
 // Horizontal-plane statistics on the device: the plane averages of module Averages (utils/averages.f90: AVG_IK_V :301-327, AVG1V2D_V :142-167) and
 // the moment groups of AVG_FLOW_XZ (statistics/avg_flow_xz.f90:513-553, :597-654) and AVG_SCAL_XZ (statistics/avg_scal_xz.f90:373-455) that need no
-// derivative, as TWO passes over the fields (the means, then every covariance) instead of one temporary field and one reduction per output.
+// derivative, as TWO passes over the fields (the means, then every covariance) instead of one temporary field and one reduction per output; and
+// the groups of the same routines on the velocity and scalar gradients (:976-1248, :673-699; avg_scal_xz.f90:451-453, :607, :714-745) as three
+// more passes over the nine gradient fields.
 //
 //   k_plane_partial<P, V>  grid (ny, nchunks), 256 threads: the workgroup (j, c) sums plane j over the rows k of chunk c (AVG_ROWS_PER_GROUP rows).
 //                          Wave w takes the rows c R + w, + 4, ..; its lanes run along x, V = 2: 16-byte loads (nx even, every field 16-byte
-//                          aligned), V = 1: 8-byte loads.  U rows of every field are requested before the first is used (U NFLD <= 16 loads in
-//                          flight per lane); the sums have no dependent chain on the loads.  The means of plane j are the same for the whole
-//                          workgroup and come from a device table [NMEAN][ny] through scalar loads.  All NOUT sums of the program (at most 22)
-//                          stay in registers; then the wave by __shfl_xor, the four waves through LDS, and thread 0 stores partial[c][j][o].
+//                          aligned), V = 1: 8-byte loads.  U = P::ROWS rows of every field are requested before the first is used (U NFLD
+//                          loads in flight per lane, 12 to 18); the sums have no dependent chain on the loads.  The means of plane j are the
+//                          same for the whole workgroup and come from the program's device table [NMEAN][ny] through scalar loads.  All NOUT
+//                          sums of the program (at most 38) stay in registers; then the wave by __shfl_xor, the four waves through LDS,
+//                          and thread 0 stores partial[c][j][o].
 //   k_plane_final          sums the chunks of each (j, o) in chunk order and DIVIDES by real(nx nz) (avg/real(nx*nz, wp), averages.f90:320).
 //
 // No atomics and no workgroup that waits for or counts another: the order of summation is a function of (nx, ny, nz) and the alignment alone, so
@@ -68,7 +71,7 @@ __device__ __forceinline__ void avg_rows(const AvgArgs &a, size_t row0, size_t r
 
 template <class P, int V>
 __global__ void __launch_bounds__(AVG_THREADS) k_plane_partial(const AvgArgs a) {
-    constexpr int U = P::NFLD <= 4 ? 4 : 16 / P::NFLD;
+    constexpr int U = P::ROWS;
     __shared__ double red[AVG_WAVES][P::NOUT];
     const int j = blockIdx.x, c = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int k1 = min(a.nz, (c + 1) * AVG_ROWS_PER_GROUP);
@@ -137,9 +140,7 @@ hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, con
     const double bytes = 8.0 * nx * ny * (double)nz * info.nfld;
     const bool known = avg_dispatch(prog, param, [&](auto P) {
         using Prog = decltype(P);
-        const char *tag = prog == AVG_PROG_MEANS ? "k_plane_partial<MEANS>" : prog == AVG_PROG_POWER ? "k_plane_partial<POWER>"
-                        : prog == AVG_PROG_FLOW ? "k_plane_partial<FLOW>" : "k_plane_partial<SCAL>";
-        ProfScope ps(tag, st, bytes);
+        ProfScope ps(Prog::TAG, st, bytes);
         if (vec) hipLaunchKernelGGL((k_plane_partial<Prog, 2>), grid, dim3(AVG_THREADS), 0, st, a);
         else hipLaunchKernelGGL((k_plane_partial<Prog, 1>), grid, dim3(AVG_THREADS), 0, st, a);
     });

@@ -55,6 +55,47 @@ int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const do
     });
 }
 
+// Section 3 of AVG_FLOW_XZ (statistics/avg_flow_xz.f90:976-986) in front of the gradient statistics, and with p the pressure block (:670-674) in
+// front of that: the derivatives by the driver's plans, bcs = 0, into the reference's arrays (dudx .. dwdz = txc[0..8]; dp/dx, dp/dy, dp/dz in
+// dwdx, dwdy, dwdz first)
+int tlab_dns_avg_gradients_flow(tlab_dns_t d, double *const *q, const double *p, double *const *txc, const double *fU, const double *fV,
+                                const double *fW, const double *rP, const double *rU_y, const double *rV_y, const double *rW_y, double *out,
+                                int ldout) {
+    return catch_fail([&] {
+        const char *who = "tlab_dns_avg_gradients_flow";
+        if (!d || !q || !txc || !fU || !fV || !fW || !rU_y || !rV_y || !rW_y || !out || (p == nullptr) != (rP == nullptr))
+            throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer (p and rP may be NULL, together)");
+        for (int i = 0; i < 3; ++i)
+            if (!q[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null velocity array");
+        for (int i = 0; i < 9; ++i)
+            if (!txc[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null txc array");
+        const int nx = d->nx, ny = d->ny, nz = d->nz;
+        if (ldout < ny) throw Fail(TLAB_EINVAL, std::string(who) + ": the leading dimension of the profiles is smaller than ny");
+        if (p) {
+            for (int dir = 1; dir <= 3; ++dir) ok(tlab_opr_partial(dir, d->g[dir - 1], TLAB_OPR_P1, nx, ny, nz, 0, p, txc[5 + dir], nullptr), "OPR_Partial(p)");
+            ok(tlab_avg_ugradp(nx, ny, nz, q[0], q[1], q[2], txc[6], txc[7], txc[8], out + (size_t)56 * ldout), "tlab_avg_ugradp");
+        }
+        for (int c = 0; c < 3; ++c)
+            for (int dir = 1; dir <= 3; ++dir)
+                ok(tlab_opr_partial(dir, d->g[dir - 1], TLAB_OPR_P1, nx, ny, nz, 0, q[c], txc[3 * c + dir - 1], nullptr), "OPR_Partial");
+        ok(tlab_avg_gradients_flow(nx, ny, nz, txc, q[0], q[1], q[2], p, fU, fV, fW, rP, rU_y, rV_y, rW_y, out, ldout), "tlab_avg_gradients_flow");
+    });
+}
+
+// ... and of one scalar (statistics/avg_scal_xz.f90:446-448, :602-604): dsdx, dsdy, dsdz = txc[0..2]
+int tlab_dns_avg_gradients_scal(tlab_dns_t d, const double *s, double *const *q, const double *p, double *const *txc, const double *fS,
+                                const double *fU, const double *fV, const double *fW, const double *rP, const double *rS_y, const double *fS_y,
+                                double *out, int ldout) {
+    return catch_fail([&] {
+        const char *who = "tlab_dns_avg_gradients_scal";
+        if (!d || !s || !q || !txc || !q[0] || !q[1] || !q[2] || !txc[0] || !txc[1] || !txc[2] || !out)
+            throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
+        const int nx = d->nx, ny = d->ny, nz = d->nz;
+        for (int dir = 1; dir <= 3; ++dir) ok(tlab_opr_partial(dir, d->g[dir - 1], TLAB_OPR_P1, nx, ny, nz, 0, s, txc[dir - 1], nullptr), "OPR_Partial");
+        ok(tlab_avg_gradients_scal(nx, ny, nz, txc, s, q[0], q[1], q[2], p, fS, fU, fV, fW, rP, rS_y, fS_y, out, ldout), "tlab_avg_gradients_scal");
+    });
+}
+
 int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *amn, double *amx) {
     return catch_fail([&] {
         if (!d || !a || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_minmax: bad arguments");

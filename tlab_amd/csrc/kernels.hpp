@@ -222,7 +222,7 @@ hipError_t launch_infrared_y(const double *l, double *hs, double *scr1, double *
                              double flux_top, double flux_bottom, int nx, int ny, int nz, hipStream_t st);
 
 // averages.hip: plane statistics (k_plane_partial + k_plane_final).  prog, param: a program of averages_host.hpp (AVG_PROG_*; param = the number of
-// fields, imom, or 1 with a pressure field); f: its fields; means: device, [nmean][ny] (NULL for MEANS and POWER); partial: device scratch,
+// fields, imom, or 1 with a pressure field); f: its fields; means: device, [nmean][ny] (NULL for a program without means); partial: device scratch,
 // plane_moments_chunks(nz) * ny * nout doubles; prof: device, [nout][ny], the result.  Nothing is copied or synchronised here.
 int plane_moments_chunks(int nz);
 hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, const double *const *f, const double *means, double *partial,

@@ -640,6 +640,86 @@ class Dns:
             r["rP"] = rP
         return r
 
+    def profile_derivative(self, profiles):
+        """OPR_Partial_Y(OPR_P1, 1, jmax, 1, bcs, g(2), ..) of profiles (numpy (n, ny)) with the driver's y plan: numpy (n, ny).  The line
+        kernels have no test on a box of one line, so profile i is replicated along x into plane i of a box (nx, ny, n) -- lines of the length
+        every substep runs -- and line 0 of each plane is returned."""
+        import torch
+        from .operators import OPR_Partial_Y, OPR_P1
+        prof = np.atleast_2d(np.asarray(profiles, dtype=np.float64))
+        n = prof.shape[0]
+        box = np.ascontiguousarray(np.broadcast_to(prof[:, :, None], (n, self.ny, self.nx)))
+        a = torch.from_numpy(box.reshape(-1)).to(self.q[0].device)
+        res = torch.empty_like(a)
+        OPR_Partial_Y(OPR_P1, self.nx, self.ny, n, 0, self.g[1], a, res)
+        return np.ascontiguousarray(res.cpu().numpy().reshape(n, self.ny, self.nx)[:, :, 0])
+
+    def flow_gradient_stats(self, p=None):
+        """Section 3 of AVG_FLOW_XZ (avg_flow_xz.f90:976-1248, with p also :670-699), incompressible, constant transport: the nine velocity
+        derivatives into self.txc (which hold dudx .. dwdz on return) and the plane statistics on them.  A dict keyed by
+        operators.FLOW_GRADIENTS (with p also FLOW_GRADIENTS_P and "ugradp"): the finished profiles of the reference -- Phi, Tau_yy, Tau_xy,
+        Tau_yz, Exx .. Eyz, PIxx, PIyy, PIzz after its host lines (:1140, :1187-1203, :1263-1268, :687-689) with the driver's visc -- and the
+        raw columns of those under "<name>_raw"; plus the means rU rV rW (rP) and rU_y rV_y rW_y."""
+        from .operators import FLOW_GRADIENTS, FLOW_GRADIENTS_P
+        _use_torch_stream()
+        m = self.plane_means()
+        rP = self.AVG_IK_V(p) if p is not None else None
+        rU_y, rV_y, rW_y = self.profile_derivative([m["rU"], m["rV"], m["rW"]])
+        q, _, _, _, txc = self._arrays()
+        ny = self.ny
+        out = np.zeros((57 if p is not None else 50, ny))
+        prof = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        check(load().tlab_dns_avg_gradients_flow(self._h, q, p.data_ptr() if p is not None else None, txc, prof(m["rU"]), prof(m["rV"]),
+                                                 prof(m["rW"]), prof(rP) if p is not None else None, prof(rU_y), prof(rV_y), prof(rW_y),
+                                                 prof(out), ny), "tlab_dns_avg_gradients_flow")
+        names = FLOW_GRADIENTS + (FLOW_GRADIENTS_P if p is not None else ())
+        r = dict(zip(names, out))
+        visc, c23 = self.visc, 2.0 / 3.0
+        for k in ("Phi", "Tau_yy", "Tau_xy", "Tau_yz", "Exx", "Eyy", "Ezz", "Exy", "Exz", "Eyz") + (("PIxx", "PIyy", "PIzz") if p is not None else ()):
+            r[k + "_raw"] = r[k]
+        r["Phi"] = r["Phi_raw"] * visc * 2.0                                         # :1140
+        r["Tau_yy"] = r["Tau_yy_raw"] * visc * c23                                   # :1187
+        r["Tau_xy"] = r["Tau_xy_raw"] * visc                                         # :1195
+        r["Tau_yz"] = r["Tau_yz_raw"] * visc                                         # :1203
+        r["Exx"] = (r["Exx_raw"] * visc - r["Tau_xy"] * rU_y) * 2.0                  # :1263-1268
+        r["Eyy"] = (r["Eyy_raw"] * visc - r["Tau_yy"] * rV_y) * 2.0
+        r["Ezz"] = (r["Ezz_raw"] * visc - r["Tau_yz"] * rW_y) * 2.0
+        r["Exy"] = r["Exy_raw"] * visc - r["Tau_xy"] * rV_y - r["Tau_yy"] * rU_y
+        r["Exz"] = r["Exz_raw"] * visc - r["Tau_xy"] * rW_y - r["Tau_yz"] * rU_y
+        r["Eyz"] = r["Eyz_raw"] * visc - r["Tau_yy"] * rW_y - r["Tau_yz"] * rV_y
+        if p is not None:
+            for k in ("PIxx", "PIyy", "PIzz"):
+                r[k] = r[k + "_raw"] * 2.0                                           # :687-689
+            r["ugradp"] = out[56]
+            r["rP"] = rP
+        r.update(rU=m["rU"], rV=m["rV"], rW=m["rW"], rU_y=rU_y, rV_y=rV_y, rW_y=rW_y)
+        return r
+
+    def scal_gradient_stats(self, is_, p=None):
+        """The gradient groups of scalar is_ (0-based) in AVG_SCAL_XZ (avg_scal_xz.f90:451-453, :607-610, :714-756), incompressible (fS = rS,
+        fS_y = rS_y): dsdx dsdy dsdz into self.txc[0..2] and the plane statistics on them.  A dict keyed by operators.SCAL_GRADIENTS (with p
+        also SCAL_GRADIENTS_P): Ess finished (Ess*diff*2, diff = visc / schmidt, :610) with the raw column under "Ess_raw"; plus the means."""
+        from .operators import SCAL_GRADIENTS, SCAL_GRADIENTS_P
+        _use_torch_stream()
+        m = self.plane_means()
+        rP = self.AVG_IK_V(p) if p is not None else None
+        rS = m["rS"][is_]
+        rS_y = self.profile_derivative([rS])[0]
+        q, _, _, _, txc = self._arrays()
+        ny = self.ny
+        out = np.zeros((18 if p is not None else 15, ny))
+        prof = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+        check(load().tlab_dns_avg_gradients_scal(self._h, self.s[is_].data_ptr(), q, p.data_ptr() if p is not None else None, txc, prof(rS),
+                                                 prof(m["rU"]), prof(m["rV"]), prof(m["rW"]), prof(rP) if p is not None else None, prof(rS_y),
+                                                 prof(rS_y) if p is not None else None, prof(out), ny), "tlab_dns_avg_gradients_scal")
+        r = dict(zip(SCAL_GRADIENTS + (SCAL_GRADIENTS_P if p is not None else ()), out))
+        r["Ess_raw"] = r["Ess"]
+        r["Ess"] = r["Ess_raw"] * (self.visc / float(self.schmidt[is_])) * 2.0      # :610
+        r.update(rS=rS, rU=m["rU"], rV=m["rV"], rW=m["rW"], rS_y=rS_y)
+        if p is not None:
+            r["rP"] = rP
+        return r
+
     def begin_step(self):
         """hq = hs = 0 of TIME_RUNGEKUTTA (time.f90:212-216) without touching the arrays: the next substep overwrites them."""
         check(load().tlab_dns_begin_step(self._h), "tlab_dns_begin_step")

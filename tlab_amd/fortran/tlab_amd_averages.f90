@@ -8,6 +8,14 @@
 !                                           product and average it: one pass over u, v, w (and p) instead of one temporary and one AVG_IK_V per
 !                                           output.  out(jmax, 18 or 22): columns of the caller's mean2d in the order of include/tlab_amd.h.
 !   TLab_AMD_Avg_Moments_Scal               the same for avg_scal_xz.f90:373-455: out(jmax, 10 or 11).
+!   TLab_AMD_Avg_Gradients_Flow            the groups of Section 3 of AVG_FLOW_XZ on the nine gradient arrays (avg_flow_xz.f90:988-1248, with p also
+!                                           the pressure strain :681-699) in three passes: out(jmax, 50 or 56) in the order of include/tlab_amd.h,
+!                                           RAW: the caller's host lines (Phi*visc*2, Tau*visc, E = (E*visc - Tau*rU_y)*2, PIxx*2, Txxy -= ..) stay.
+!                                           The arguments are AVG_FLOW_XZ's own arrays dudx .. dwdz, u, v, w, p_loc and its mean2d macros.
+!   TLab_AMD_Avg_UGradP                     avg_flow_xz.f90:673-674 on u, v, w and the three derivatives of p (there in dwdx, dwdy, dwdz)
+!   TLab_AMD_Avg_Gradients_Scal             avg_scal_xz.f90:451-453, :607, :714-745 on dsdx, dsdy, dsdz: out(jmax, 15 or 18)
+!                                           With USE_MPI every pass is followed by the reference's MPI_ALLREDUCE (averages.f90:320-324), so that the
+!                                           means a later pass subtracts are the global ones, as the reference's AVG_IK_V returns them.
 ! The arrays are classified by the library (tlab_pointer_on_device): host arrays take a host loop in the reference's order, so the routines serve
 ! either kind; a mix is refused.  The profiles are host memory.  The moment routines give the LOCAL averages: a decomposed host reduces them as it
 ! does the profiles of AVG_IK_V.  What the reference adds on the host afterwards (Ty1, Txyy, Tyyy, Tyzy) stays with the caller.
@@ -21,6 +29,7 @@ module TLab_AMD_Averages
     implicit none
     private
     public :: TLab_AMD_AVG_IK_V, TLab_AMD_AVG1V2D_V, TLab_AMD_Avg_Moments_Flow, TLab_AMD_Avg_Moments_Scal
+    public :: TLab_AMD_Avg_Gradients_Flow, TLab_AMD_Avg_UGradP, TLab_AMD_Avg_Gradients_Scal
 
 contains
     subroutine TLab_AMD_AVG_IK_V(nx, ny, nz, a, avg, wrk)
@@ -82,5 +91,95 @@ contains
         call TLab_AMD_Check(tlab_avg_moments_scal(nx, ny, nz, c_loc(s), c_loc(u), c_loc(v), c_loc(w), pp, c_loc(fS), c_loc(fU), c_loc(fV), &
                                                   c_loc(fW), pm, c_loc(out), ny), 'tlab_avg_moments_scal')
     end subroutine TLab_AMD_Avg_Moments_Scal
+
+    ! out(:, 1:50) in the order of include/tlab_amd.h (vortx .. Tyzy_v); with p and rP also (:, 51:56) = PIxx PIyy PIzz PIxy PIxz PIyz.  wrk(ny, *): as
+    ! many columns as out (used with USE_MPI only)
+    subroutine TLab_AMD_Avg_Gradients_Flow(nx, ny, nz, dudx, dudy, dudz, dvdx, dvdy, dvdz, dwdx, dwdy, dwdz, u, v, w, &
+                                           fU, fV, fW, rU_y, rV_y, rW_y, out, wrk, p, rP)
+        integer, intent(in) :: nx, ny, nz
+        real(c_double), intent(in), target, dimension(nx, ny, nz) :: dudx, dudy, dudz, dvdx, dvdy, dvdz, dwdx, dwdy, dwdz, u, v, w
+        real(c_double), intent(in), target :: fU(ny), fV(ny), fW(ny), rU_y(ny), rV_y(ny), rW_y(ny)
+        real(c_double), intent(out), target :: out(ny, *)
+        real(c_double), intent(inout) :: wrk(ny, *)
+        real(c_double), intent(in), target, optional :: p(nx, ny, nz), rP(ny)
+        type(c_ptr) :: pp, pm, g(13), m(7)
+        integer :: ip
+
+        pp = c_null_ptr; pm = c_null_ptr; ip = 0
+        if (present(p)) pp = c_loc(p)
+        if (present(rP)) pm = c_loc(rP)
+        if (present(p)) ip = 1
+        g(1:9) = [c_loc(dudx), c_loc(dudy), c_loc(dudz), c_loc(dvdx), c_loc(dvdy), c_loc(dvdz), c_loc(dwdx), c_loc(dwdy), c_loc(dwdz)]
+#ifdef USE_MPI
+        g(10:13) = [c_loc(u), c_loc(v), c_loc(w), pp]
+        m(1) = c_null_ptr
+        call TLab_AMD_Check(tlab_avg_gradients_pass(1, 0, nx, ny, nz, g, m, c_loc(out(1, 1)), ny), 'tlab_avg_gradients_pass')
+        call Reduce(ny, 6, out(1, 1), wrk)
+        m(1:6) = [c_loc(rU_y), c_loc(rV_y), c_loc(rW_y), c_loc(out(1, 1)), c_loc(out(1, 2)), c_loc(out(1, 3))]
+        call TLab_AMD_Check(tlab_avg_gradients_pass(2, 0, nx, ny, nz, g, m, c_loc(out(1, 7)), ny), 'tlab_avg_gradients_pass')
+        m(1:7) = [c_loc(out(1, 4)), c_loc(out(1, 5)), c_loc(out(1, 6)), c_loc(fU), c_loc(fV), c_loc(fW), pm]
+        call TLab_AMD_Check(tlab_avg_gradients_pass(3, ip, nx, ny, nz, g, m, c_loc(out(1, 45)), ny), 'tlab_avg_gradients_pass')
+        call Reduce(ny, 44 + 6*ip, out(1, 7), wrk)
+#else
+        call TLab_AMD_Check(tlab_avg_gradients_flow(nx, ny, nz, g(1:9), c_loc(u), c_loc(v), c_loc(w), pp, c_loc(fU), c_loc(fV), c_loc(fW), pm, &
+                                                    c_loc(rU_y), c_loc(rV_y), c_loc(rW_y), c_loc(out), ny), 'tlab_avg_gradients_flow')
+#endif
+    end subroutine TLab_AMD_Avg_Gradients_Flow
+
+    ! avg = the plane average of u*dpdx + v*dpdy + w*dpdz; the argument list of AVG_IK_V behind the fields
+    subroutine TLab_AMD_Avg_UGradP(nx, ny, nz, u, v, w, dpdx, dpdy, dpdz, avg, wrk)
+        integer, intent(in) :: nx, ny, nz
+        real(c_double), intent(in), target, dimension(nx, ny, nz) :: u, v, w, dpdx, dpdy, dpdz
+        real(c_double), intent(out), target :: avg(ny)
+        real(c_double), intent(inout) :: wrk(ny)
+
+        call TLab_AMD_Check(tlab_avg_ugradp(nx, ny, nz, c_loc(u), c_loc(v), c_loc(w), c_loc(dpdx), c_loc(dpdy), c_loc(dpdz), c_loc(avg)), &
+                            'tlab_avg_ugradp')
+#ifdef USE_MPI
+        call Reduce(ny, 1, avg, wrk)
+#endif
+    end subroutine TLab_AMD_Avg_UGradP
+
+    ! out(:, 1:15) = Fy Ess S_x2 S_y2 S_z2 S_x3 S_y3 S_z3 S_x4 S_y4 S_z4 Tssy2 Tsuy2_d Tsvy2_d Tswy2_d; with p, rP and fS_y also (:, 16:18) = PIsu PIsv PIsw
+    subroutine TLab_AMD_Avg_Gradients_Scal(nx, ny, nz, dsdx, dsdy, dsdz, s, u, v, w, fS, fU, fV, fW, rS_y, out, wrk, p, rP, fS_y)
+        integer, intent(in) :: nx, ny, nz
+        real(c_double), intent(in), target, dimension(nx, ny, nz) :: dsdx, dsdy, dsdz, s, u, v, w
+        real(c_double), intent(in), target :: fS(ny), fU(ny), fV(ny), fW(ny), rS_y(ny)
+        real(c_double), intent(out), target :: out(ny, *)
+        real(c_double), intent(inout) :: wrk(ny, *)
+        real(c_double), intent(in), target, optional :: p(nx, ny, nz), rP(ny), fS_y(ny)
+        type(c_ptr) :: pp, pm, py, g(8), m(7)
+        integer :: ip
+
+        pp = c_null_ptr; pm = c_null_ptr; py = c_null_ptr; ip = 0
+        if (present(p)) pp = c_loc(p)
+        if (present(rP)) pm = c_loc(rP)
+        if (present(fS_y)) py = c_loc(fS_y)
+        if (present(p)) ip = 1
+        g(1:3) = [c_loc(dsdx), c_loc(dsdy), c_loc(dsdz)]
+#ifdef USE_MPI
+        m(1) = c_loc(rS_y)
+        call TLab_AMD_Check(tlab_avg_gradients_pass(4, 0, nx, ny, nz, g, m, c_loc(out(1, 1)), ny), 'tlab_avg_gradients_pass')
+        call Reduce(ny, 11, out(1, 1), wrk)
+        g(1:8) = [c_loc(dsdy), c_loc(s), c_loc(u), c_loc(v), c_loc(w), pp, c_loc(dsdx), c_loc(dsdz)]
+        m(1:7) = [c_loc(out(1, 1)), c_loc(fS), c_loc(fU), c_loc(fV), c_loc(fW), pm, py]
+        call TLab_AMD_Check(tlab_avg_gradients_pass(5, ip, nx, ny, nz, g, m, c_loc(out(1, 12)), ny), 'tlab_avg_gradients_pass')
+        call Reduce(ny, 4 + 3*ip, out(1, 12), wrk)
+#else
+        call TLab_AMD_Check(tlab_avg_gradients_scal(nx, ny, nz, g(1:3), c_loc(s), c_loc(u), c_loc(v), c_loc(w), pp, c_loc(fS), c_loc(fU), &
+                                                    c_loc(fV), c_loc(fW), pm, c_loc(rS_y), py, c_loc(out), ny), 'tlab_avg_gradients_scal')
+#endif
+    end subroutine TLab_AMD_Avg_Gradients_Scal
+
+#ifdef USE_MPI
+    ! the reduction of AVG_IK_V (averages.f90:320-324) on nc columns of local averages
+    subroutine Reduce(ny, nc, avg, wrk)
+        integer, intent(in) :: ny, nc
+        real(c_double), intent(inout) :: avg(ny*nc), wrk(ny*nc)
+
+        call MPI_ALLREDUCE(avg, wrk, ny*nc, MPI_REAL8, MPI_SUM, MPI_COMM_WORLD, ims_err)
+        avg = wrk/real(ims_npro_i*ims_npro_k, c_double)
+    end subroutine Reduce
+#endif
 
 end module TLab_AMD_Averages

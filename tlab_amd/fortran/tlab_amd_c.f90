@@ -593,6 +593,32 @@ module TLab_AMD_C
             integer(c_int), value :: nx, ny, nz, ldout
             type(c_ptr), value :: s, u, v, w, p, fS, fU, fV, fW, rP, out
         end function
+        ! ... on derivative fields: grad(9) = dudx dudy dudz dvdx dvdy dvdz dwdx dwdy dwdz, grads(3) = dsdx dsdy dsdz
+        integer(c_int) function tlab_avg_gradients_flow(nx, ny, nz, grad, u, v, w, p, fU, fV, fW, rP, rU_y, rV_y, rW_y, out, ldout) &
+            bind(C, name='tlab_avg_gradients_flow')
+            import :: c_int, c_ptr
+            integer(c_int), value :: nx, ny, nz, ldout
+            type(c_ptr), intent(in) :: grad(9)
+            type(c_ptr), value :: u, v, w, p, fU, fV, fW, rP, rU_y, rV_y, rW_y, out
+        end function
+        integer(c_int) function tlab_avg_ugradp(nx, ny, nz, u, v, w, dpdx, dpdy, dpdz, out) bind(C, name='tlab_avg_ugradp')
+            import :: c_int, c_ptr
+            integer(c_int), value :: nx, ny, nz
+            type(c_ptr), value :: u, v, w, dpdx, dpdy, dpdz, out
+        end function
+        integer(c_int) function tlab_avg_gradients_scal(nx, ny, nz, grads, s, u, v, w, p, fS, fU, fV, fW, rP, rS_y, fS_y, out, ldout) &
+            bind(C, name='tlab_avg_gradients_scal')
+            import :: c_int, c_ptr
+            integer(c_int), value :: nx, ny, nz, ldout
+            type(c_ptr), intent(in) :: grads(3)
+            type(c_ptr), value :: s, u, v, w, p, fS, fU, fV, fW, rP, rS_y, fS_y, out
+        end function
+        integer(c_int) function tlab_avg_gradients_pass(pass, with_p, nx, ny, nz, fields, means, out, ldout) bind(C, name='tlab_avg_gradients_pass')
+            import :: c_int, c_ptr
+            integer(c_int), value :: pass, with_p, nx, ny, nz, ldout
+            type(c_ptr), intent(in) :: fields(*), means(*)
+            type(c_ptr), value :: out
+        end function
         integer(c_int) function tlab_boundary_bcs_neumann_y(plan, ibc, nx, ny, nz, u, bcs_hb, bcs_ht, tmp1) bind(C, name='tlab_boundary_bcs_neumann_y')
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, u, bcs_hb, bcs_ht, tmp1

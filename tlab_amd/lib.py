@@ -144,6 +144,12 @@ SIGNATURES = {
     "tlab_avg1v2d_v": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "tlab_avg_moments_flow": (c_int, [c_int, c_int, c_int] + [c_vp] * 9 + [c_int]),
     "tlab_avg_moments_scal": (c_int, [c_int, c_int, c_int] + [c_vp] * 11 + [c_int]),
+    "tlab_avg_gradients_flow": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_vp)] + [c_vp] * 12 + [c_int]),
+    "tlab_avg_ugradp": (c_int, [c_int, c_int, c_int] + [c_vp] * 7),
+    "tlab_avg_gradients_scal": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_vp)] + [c_vp] * 13 + [c_int]),
+    "tlab_avg_gradients_pass": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_int]),
+    "tlab_dns_avg_gradients_flow": (c_int, [c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp)] + [c_vp] * 8 + [c_int]),
+    "tlab_dns_avg_gradients_scal": (c_int, [c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp)] + [c_vp] * 8 + [c_int]),
     "tlab_opr_burgers_add": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tlab_opr_burgers_add_n": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_int, _dp, ctypes.POINTER(c_vp), c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_int]),
     "tlab_opr_partial_add": (c_int, [c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_int, c_vp, c_vp]),

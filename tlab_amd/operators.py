@@ -390,3 +390,63 @@ def avg_moments_scal(nx, ny, nz, s, u, v, w, fS, fU, fV, fW, p=None, rP=None):
                                        _profile(fU, ny, "fU", keep), _profile(fV, ny, "fV", keep), _profile(fW, ny, "fW", keep),
                                        _profile(rP, ny, "rP", keep), c_vp(out.ctypes.data), ny), "tlab_avg_moments_scal")
     return out
+
+
+# ---- ... and the groups on the velocity and scalar gradients (Section 3 of AVG_FLOW_XZ; include/tlab_amd.h lists the terms) --------------------
+def _chains(names):
+    return tuple("%s%d" % (n, k) for n in names for k in (2, 3, 4))
+
+
+FLOW_GRADIENTS = (("vortx", "vorty", "vortz", "Tau_yy", "Tau_xy", "Tau_yz") + _chains(("U_x", "V_y", "W_z", "U_y", "U_z", "V_x", "V_z", "W_x", "W_y"))
+                  + ("U_ii2", "vortx2", "vorty2", "vortz2", "Phi", "Exx", "Eyy", "Ezz", "Exy", "Exz", "Eyz")
+                  + ("Txxy_v", "Tyyy_v", "Tzzy_v", "Txyy_v", "Txzy_v", "Tyzy_v"))
+FLOW_GRADIENTS_P = ("PIxx", "PIyy", "PIzz", "PIxy", "PIxz", "PIyz")
+SCAL_GRADIENTS = ("Fy", "Ess", "S_x2", "S_y2", "S_z2", "S_x3", "S_y3", "S_z3", "S_x4", "S_y4", "S_z4", "Tssy2", "Tsuy2_d", "Tsvy2_d", "Tswy2_d")
+SCAL_GRADIENTS_P = ("PIsu", "PIsv", "PIsw")
+
+
+def avg_gradients_flow(nx, ny, nz, grad, u, v, w, fU, fV, fW, rU_y, rV_y, rW_y, p=None, rP=None):
+    """The groups of AVG_FLOW_XZ on the nine velocity derivatives grad = (dudx, dudy, dudz, dvdx, .., dwdz): numpy (50 or 56, ny), rows in the
+    order of FLOW_GRADIENTS (+ FLOW_GRADIENTS_P), raw (before the visc, c23 and 2.0 of the reference's host lines)."""
+    keep, n = [], nx * ny * nz
+    grad = list(grad)
+    if len(grad) != 9:
+        raise TlabError("grad must hold the nine velocity derivatives")
+    ptrs = (c_vp * 9)(*[_field_ptr(g, n, "grad %d" % i, keep).value for i, g in enumerate(grad)])
+    out = np.zeros((56 if p is not None else 50, ny))
+    _stream_if_device(grad + [u, v, w, p])
+    check(load().tlab_avg_gradients_flow(nx, ny, nz, ptrs, _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep), _field_ptr(w, n, "w", keep),
+                                         _field_ptr(p, n, "p", keep), _profile(fU, ny, "fU", keep), _profile(fV, ny, "fV", keep),
+                                         _profile(fW, ny, "fW", keep), _profile(rP, ny, "rP", keep), _profile(rU_y, ny, "rU_y", keep),
+                                         _profile(rV_y, ny, "rV_y", keep), _profile(rW_y, ny, "rW_y", keep), c_vp(out.ctypes.data), ny),
+          "tlab_avg_gradients_flow")
+    return out
+
+
+def avg_ugradp(nx, ny, nz, u, v, w, dpdx, dpdy, dpdz):
+    """The plane average of u*dpdx + v*dpdy + w*dpdz (avg_flow_xz.f90:673), numpy (ny,)."""
+    keep, n = [], nx * ny * nz
+    out = np.zeros(ny)
+    fields = [u, v, w, dpdx, dpdy, dpdz]
+    _stream_if_device(fields)
+    check(load().tlab_avg_ugradp(nx, ny, nz, *[_field_ptr(f, n, "field %d" % i, keep) for i, f in enumerate(fields)], c_vp(out.ctypes.data)),
+          "tlab_avg_ugradp")
+    return out
+
+
+def avg_gradients_scal(nx, ny, nz, grads, s, u, v, w, fS, fU, fV, fW, rS_y, p=None, rP=None, fS_y=None):
+    """The groups of AVG_SCAL_XZ on grads = (dsdx, dsdy, dsdz): numpy (15 or 18, ny), rows in the order of SCAL_GRADIENTS (+ SCAL_GRADIENTS_P),
+    raw.  With p also rP and fS_y."""
+    keep, n = [], nx * ny * nz
+    grads = list(grads)
+    if len(grads) != 3:
+        raise TlabError("grads must hold dsdx, dsdy, dsdz")
+    ptrs = (c_vp * 3)(*[_field_ptr(g, n, "grads %d" % i, keep).value for i, g in enumerate(grads)])
+    out = np.zeros((18 if p is not None else 15, ny))
+    _stream_if_device(grads + [s, u, v, w, p])
+    check(load().tlab_avg_gradients_scal(nx, ny, nz, ptrs, _field_ptr(s, n, "s", keep), _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep),
+                                         _field_ptr(w, n, "w", keep), _field_ptr(p, n, "p", keep), _profile(fS, ny, "fS", keep),
+                                         _profile(fU, ny, "fU", keep), _profile(fV, ny, "fV", keep), _profile(fW, ny, "fW", keep),
+                                         _profile(rP, ny, "rP", keep), _profile(rS_y, ny, "rS_y", keep), _profile(fS_y, ny, "fS_y", keep),
+                                         c_vp(out.ctypes.data), ny), "tlab_avg_gradients_scal")
+    return out
