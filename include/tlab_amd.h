@@ -757,7 +757,47 @@ int tlab_dns_avg_gradients_scal(tlab_dns_t d, const double *s, double *const *q,
                                 const double *fU, const double *fV, const double *fW, const double *rP, const double *rS_y, const double *fS_y,
                                 double *out, int ldout);
 
-/* RHS_GLOBAL_INCOMPRESSIBLE_1()   tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
+/* ---- plane PDFs: module PDFS (utils/pdfs.f90) and PDF1V_N / PDF2V (statistics/pdf.f90), the block stats_pdfs of DNS_STATISTICS ------------------
+ * Histograms (counts, not normalised) of fields u(nx, ny, nz), x fastest, in every plane j and -- when ny > 1 -- in the whole volume, written as
+ * plane ny + 1.  No driver handle; the conventions of the plane statistics above: all arrays in device memory -> the kernels of csrc/pdfs.hip, all
+ * in host memory (or no tlab_init) -> the reference's loops on the host; a mix: TLAB_EINVAL.  A recorded substep runs first; results are in HOST
+ * memory on return; scratch is the library's.  No global atomics, no float atomics: counts are integers (32 bits per workgroup in LDS, 64 bits
+ * across workgroups), exact in any order, so a call repeats its bits and they are the reference's while a count stays below 2^53.
+ * The bin of a point is up = int(q) + 1, q = (u - umin)/ustep (one subtraction, one division, fp64, unfused), ustep = (umax - umin)/real(nbins)
+ * and 1 where that is 0; pdf(nbins+1) = umin + 0.5 ustep, pdf(nbins+2) = umax - 0.5 ustep with the step before that replacement.  int()
+ * truncates toward zero: with an external interval a value slightly below umin (q in (-1, 0)) is counted in bin 1 and a value equal to umax is
+ * dropped, as in the reference.  Where Fortran's int() is undefined the result is defined: an external interval counts a point iff
+ * -1 < q < nbins; a local interval counts every finite q > -1, in bin min(trunc(q) + 1, nbins); NaN and infinite q are dropped.  Fields that hold
+ * NaN are OUTSIDE the contract (their min / max are not the reference's).
+ * A gate (igate != 0): only points with gate == igate take part (PDF1V2D1G); min and max start from big_wp = 1e20 and -big_wp, and a plane without
+ * a gated point goes through the same expressions with those.  gate: int8, the layout of a field; may be NULL when igate == 0.
+ * TLAB_EINVAL: nx, ny, nz or nv < 1, nbins < 1 or above the compiled limit 4096, a null field, igate != 0 with a null gate, ibc outside 0..5.
+ *
+ * tlab_pdf1v_n: the calculation of PDF1V_N (statistics/pdf.f90:14-91; no file is written).  u: HOST array of nv pointers; ibc[nv]: 0 external
+ *   interval [umin[v], umax[v]], 1 local interval, 2..5 local interval, then PDF_ANALIZE(ibc - 2, .., plim = 1e-4) of every plane and the histogram
+ *   on the analysed interval as an external one.  pdf: (nbins+2, ny+1, nv) doubles, Fortran order; the last plane is zero when ny == 1.  umin,
+ *   umax may be NULL when no ibc is 0.  All fields share the passes (min/max; histogram; histogram on the analysed intervals): at most three
+ *   device-to-host synchronisations whatever nv and ny.
+ * tlab_pdf_minmax_planes, tlab_pdf_histogram_planes: the two passes on their own, for a decomposed host that reduces min / max, then the counts,
+ *   over its ranks in between (the MPI_ALLREDUCEs of PDF1V2D).  umin, umax: (ny+1, nv) doubles, the volume's as plane ny+1 (computed also when
+ *   ny == 1); ilim[v] == 0: the intervals of field v are external (a point outside is dropped), otherwise local (the last point in the last bin).
+ *   pdf as above, bounds included.
+ * tlab_pdf_analize: PDF_ANALIZE (utils/pdfs.f90:329-379), host arithmetic on one pdf(nbins+2).
+ * tlab_pdf2v: PDF2V (statistics/pdf.f90:123-159) over PDF2V2D, single rank: min / max of u, the min / max of v in every u-bin, the
+ *   nbins[0] x nbins[1] histogram with both indices clipped to the last bin.  pdf: (nbins[0]*nbins[1] + 2 + 2*nbins[0], ny+1), bin (up, vp) at
+ *   (vp-1)*nbins[0] + up.  nbins[0]*nbins[1] at most 4096, nbins[0] at most 1024.
+ * tlab_gate_threshold: gate[i] = a[i] > thr ? 1 : 0 for n points (the gate of dns_statistics.f90:106-110); a and gate of one kind.  On the device
+ *   the call returns with the kernel enqueued on the library's stream. */
+int tlab_pdf1v_n(int nx, int ny, int nz, int nv, int nbins, const int *ibc, const double *umin, const double *umax, const double *const *u,
+                 int igate, const signed char *gate, double *pdf);
+int tlab_pdf_minmax_planes(int nx, int ny, int nz, int nv, const double *const *u, int igate, const signed char *gate, double *umin, double *umax);
+int tlab_pdf_histogram_planes(int nx, int ny, int nz, int nv, int nbins, const int *ilim, const double *umin, const double *umax,
+                              const double *const *u, int igate, const signed char *gate, double *pdf);
+int tlab_pdf_analize(int ibc, int nbins, const double *pdf, double *umin, double *umax, double plim, int *nplim);
+int tlab_pdf2v(int nx, int ny, int nz, const int *nbins, const double *u, const double *v, double *pdf);
+int tlab_gate_threshold(const double *a, long long n, double thr, signed char *gate);
+
+/* RHS_GLOBAL_INCOMPRESSIBLE_1()  tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
  * it works on the module arrays q, s, hq, hs, txc and on dte).  q[3] = u,v,w; s[nscal]; hq[3], hs[nscal] are
  * accumulated into; txc[9] = tmp1..tmp9, each of isize_txc_field = (nx+2)*ny*nz doubles.  HOST arrays of DEVICE pointers.
  * Convective form, RhsMode = combined.  The flow blocks of the relaxation buffer zones at Jmin / Jmax are applied in the reference's place and the

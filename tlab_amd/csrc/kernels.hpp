@@ -228,6 +228,33 @@ int plane_moments_chunks(int nz);
 hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, const double *const *f, const double *means, double *partial,
                                 double *prof, hipStream_t st);
 
+// pdfs.hip: plane PDFs (k_pdf_minmax, k_pdf_hist and their final kernels; pdfs_host.hpp holds the bin of a point).  F: at most PDF_FIELDS_PER_LAUNCH
+// fields of one box and the gate (igate != 0: only points with gate == igate take part).  Nothing is copied or synchronised here.
+//   launch_pdf_minmax  partial: scratch, nv * pdf_chunks(nz) * ny * 2 doubles; mm: [nv][ny + 1][2] = (min, max) of every plane and of the volume
+//   launch_pdf_hist    iv: [nv][ny + 1][2] = (umin, ustep) of every plane and of the volume; bit v of ext_mask: field v has an external interval
+//                      (a point outside is dropped; otherwise the last point goes to the last bin), of vol_mask: the volume has an interval of its
+//                      own and is binned too (otherwise its counts are the sum of the planes'); cnt: scratch, nv * pdf_chunks(nz) * ny * 2 * nbins
+//                      32-bit words; volpart: scratch, nv * ny * nbins 64-bit words; pdf: [nv][ny + 1][nbins] counts as doubles (plane ny: the volume,
+//                      not written when ny == 1)
+//   launch_pdf2v_range per u-bin min / max of v (PDF2V2D, utils/pdfs.f90:259-268), u-bins from iv [ny + 1][2]; partial: scratch,
+//                      pdf_chunks(nz) * ny * 2 * nb1 * 2 doubles; volpart: scratch, ny * nb1 * 2 doubles; rng: [ny + 1][nb1][2] = (vmin, vmax)
+//   launch_pdf2v_hist  the joint histogram: viv [ny + 1][nb1][2] = (vmin, vstep) of every u-bin; cnt, volpart as above with nbins = nb1 * nb2;
+//                      pdf: [ny + 1][nb1 * nb2], bin (up, vp) at vp * nb1 + up
+struct PdfFields {
+    int nv;
+    const double *f[8];
+    const signed char *gate;
+    int igate, nx, ny, nz;
+};
+int pdf_chunks(int nz);
+hipError_t launch_pdf_minmax(const PdfFields &F, double *partial, double *mm, hipStream_t st);
+hipError_t launch_pdf_hist(const PdfFields &F, int nbins, unsigned ext_mask, unsigned vol_mask, const double *iv, unsigned *cnt,
+                           unsigned long long *volpart, double *pdf, hipStream_t st);
+hipError_t launch_pdf2v_range(const PdfFields &F, int nb1, const double *iv, double *partial, double *volpart, double *rng, hipStream_t st);
+hipError_t launch_pdf2v_hist(const PdfFields &F, int nb1, int nb2, const double *iv, const double *viv, unsigned *cnt, unsigned long long *volpart,
+                             double *pdf, hipStream_t st);
+hipError_t launch_gate_threshold(const double *a, long long n, double thr, signed char *gate, hipStream_t st);
+
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,

@@ -640,6 +640,17 @@ class Dns:
             r["rP"] = rP
         return r
 
+    def plane_pdfs(self, p=None, nbins=32, ibc=2, gate=None, igate=0, umin=0.0, umax=0.0):
+        """The block stats_pdfs of DNS_STATISTICS (dns_statistics.f90:122-148): the histograms of PDF1V_N for u, v, w, (p,) and every scalar in
+        one call of tlab_pdf1v_n -- three passes over the fields for all planes and the volume.  A dict keyed by the reference's tags u v w (p)
+        s1 s2 ..: numpy (ny + 1, nbins + 2) each, nbins counts and the centres of the first and the last bin per plane, the volume last.  gate
+        (an int8 tensor of the box) with igate != 0: only points with gate == igate take part; umin, umax: the external interval(s) of ibc = 0.  No file is written."""
+        from .operators import pdf1v_n
+        fields = self.q + ([p] if p is not None else []) + self.s
+        tags = ["u", "v", "w"] + (["p"] if p is not None else []) + ["s%d" % (i + 1) for i in range(self.nscal)]
+        out = pdf1v_n(self.nx, self.ny, self.nz, fields, nbins, ibc, umin, umax, gate, igate)
+        return dict(zip(tags, out))
+
     def profile_derivative(self, profiles):
         """OPR_Partial_Y(OPR_P1, 1, jmax, 1, bcs, g(2), ..) of profiles (numpy (n, ny)) with the driver's y plan: numpy (n, ny).  The line
         kernels have no test on a box of one line, so profile i is replicated along x into plane i of a box (nx, ny, n) -- lines of the length

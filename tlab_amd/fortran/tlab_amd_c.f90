@@ -619,6 +619,54 @@ module TLab_AMD_C
             type(c_ptr), intent(in) :: fields(*), means(*)
             type(c_ptr), value :: out
         end function
+        ! plane PDFs (tlab_amd_pdfs.f90): fields and gate of either kind (all device or all host), intervals and histograms in host memory
+        integer(c_int) function tlab_pdf1v_n(nx, ny, nz, nv, nbins, ibc, umin, umax, u, igate, gate, pdf) bind(C, name='tlab_pdf1v_n')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nv, nbins, igate
+            integer(c_int), intent(in) :: ibc(*)
+            real(c_double), intent(in) :: umin(*), umax(*)
+            type(c_ptr), intent(in) :: u(*)
+            type(c_ptr), value :: gate
+            real(c_double), intent(out) :: pdf(*)
+        end function
+        integer(c_int) function tlab_pdf_minmax_planes(nx, ny, nz, nv, u, igate, gate, umin, umax) bind(C, name='tlab_pdf_minmax_planes')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nv, igate
+            type(c_ptr), intent(in) :: u(*)
+            type(c_ptr), value :: gate
+            real(c_double), intent(out) :: umin(*), umax(*)
+        end function
+        integer(c_int) function tlab_pdf_histogram_planes(nx, ny, nz, nv, nbins, ilim, umin, umax, u, igate, gate, pdf) &
+            bind(C, name='tlab_pdf_histogram_planes')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nv, nbins, igate
+            integer(c_int), intent(in) :: ilim(*)
+            real(c_double), intent(in) :: umin(*), umax(*)
+            type(c_ptr), intent(in) :: u(*)
+            type(c_ptr), value :: gate
+            real(c_double), intent(out) :: pdf(*)
+        end function
+        integer(c_int) function tlab_pdf_analize(ibc, nbins, pdf, umin, umax, plim, nplim) bind(C, name='tlab_pdf_analize')
+            import :: c_int, c_double
+            integer(c_int), value :: ibc, nbins
+            real(c_double), intent(in) :: pdf(*)
+            real(c_double), intent(inout) :: umin, umax
+            real(c_double), value :: plim
+            integer(c_int), intent(out) :: nplim
+        end function
+        integer(c_int) function tlab_pdf2v(nx, ny, nz, nbins, u, v, pdf) bind(C, name='tlab_pdf2v')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz
+            integer(c_int), intent(in) :: nbins(2)
+            type(c_ptr), value :: u, v
+            real(c_double), intent(out) :: pdf(*)
+        end function
+        integer(c_int) function tlab_gate_threshold(a, n, thr, gate) bind(C, name='tlab_gate_threshold')
+            import :: c_int, c_ptr, c_double, c_long_long
+            type(c_ptr), value :: a, gate
+            integer(c_long_long), value :: n
+            real(c_double), value :: thr
+        end function
         integer(c_int) function tlab_boundary_bcs_neumann_y(plan, ibc, nx, ny, nz, u, bcs_hb, bcs_ht, tmp1) bind(C, name='tlab_boundary_bcs_neumann_y')
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, u, bcs_hb, bcs_ht, tmp1

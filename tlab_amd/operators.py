@@ -450,3 +450,109 @@ def avg_gradients_scal(nx, ny, nz, grads, s, u, v, w, fS, fU, fV, fW, rS_y, p=No
                                          _profile(rP, ny, "rP", keep), _profile(rS_y, ny, "rS_y", keep), _profile(fS_y, ny, "fS_y", keep),
                                          c_vp(out.ctypes.data), ny), "tlab_avg_gradients_scal")
     return out
+
+
+# ---- plane PDFs: module PDFS and PDF1V_N / PDF2V (include/tlab_amd.h) --------------------------------------------------------------------------
+def _gate_ptr(gate, n, keep):
+    """the address of an int8 gate of n points: a contiguous torch tensor (device or host) or a numpy array; None -> NULL"""
+    if gate is None:
+        return c_vp(0)
+    if isinstance(gate, np.ndarray):
+        if gate.dtype != np.int8 or not gate.flags.c_contiguous or gate.size < n:
+            raise TlabError("gate must be a contiguous int8 array of at least %d elements" % n)
+        keep.append(gate)
+        return c_vp(gate.ctypes.data)
+    import torch
+    if not isinstance(gate, torch.Tensor) or gate.dtype != torch.int8 or not gate.is_contiguous() or gate.numel() < n:
+        raise TlabError("gate must be a contiguous int8 tensor of at least %d elements" % n)
+    keep.append(gate)
+    return c_vp(gate.data_ptr())
+
+
+def _field_ptrs(fields, n, keep):
+    return (c_vp * max(len(fields), 1))(*[_field_ptr(f, n, "field %d" % i, keep).value for i, f in enumerate(fields)])
+
+
+def pdf1v_n(nx, ny, nz, fields, nbins, ibc, umin=None, umax=None, gate=None, igate=0):
+    """The calculation of PDF1V_N (statistics/pdf.f90:14) for several fields in shared passes: numpy (nv, ny + 1, nbins + 2) -- nbins counts and
+    the centres of the first and the last bin per plane, the volume as the last plane (zero when ny == 1).  ibc: one value or one per field
+    (0: the external interval umin, umax of the field; 1: local; 2..5: local, PDF_ANALIZE(ibc - 2), then the analysed interval)."""
+    fields = list(fields)
+    nv, n, keep = len(fields), nx * ny * nz, []
+    ibc_ = np.ascontiguousarray(np.broadcast_to(np.asarray(ibc, dtype=np.int32), (max(nv, 1),)))
+    lo = None if umin is None else np.ascontiguousarray(np.broadcast_to(np.asarray(umin, dtype=np.float64), (max(nv, 1),)))
+    hi = None if umax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(umax, dtype=np.float64), (max(nv, 1),)))
+    out = np.zeros((max(nv, 1), ny + 1, max(int(nbins), 0) + 2))
+    _stream_if_device(fields)
+    check(load().tlab_pdf1v_n(nx, ny, nz, nv, int(nbins), c_vp(ibc_.ctypes.data), c_vp(lo.ctypes.data if lo is not None else 0),
+                              c_vp(hi.ctypes.data if hi is not None else 0), _field_ptrs(fields, n, keep), int(igate), _gate_ptr(gate, n, keep),
+                              c_vp(out.ctypes.data)), "tlab_pdf1v_n")
+    return out[:nv]
+
+
+def pdf_minmax_planes(nx, ny, nz, fields, gate=None, igate=0):
+    """The min/max pass of pdf1v_n on its own: (umin, umax), numpy (nv, ny + 1) each, the volume's as the last plane."""
+    fields = list(fields)
+    nv, n, keep = len(fields), nx * ny * nz, []
+    lo, hi = np.zeros((max(nv, 1), ny + 1)), np.zeros((max(nv, 1), ny + 1))
+    _stream_if_device(fields)
+    check(load().tlab_pdf_minmax_planes(nx, ny, nz, nv, _field_ptrs(fields, n, keep), int(igate), _gate_ptr(gate, n, keep), c_vp(lo.ctypes.data),
+                                        c_vp(hi.ctypes.data)), "tlab_pdf_minmax_planes")
+    return lo[:nv], hi[:nv]
+
+
+def pdf_histogram_planes(nx, ny, nz, fields, nbins, ilim, umin, umax, gate=None, igate=0):
+    """The histogram pass of pdf1v_n on its own, with the intervals of every plane handed in: umin, umax numpy (nv, ny + 1); ilim: one value or
+    one per field, 0 = external intervals.  numpy (nv, ny + 1, nbins + 2)."""
+    fields = list(fields)
+    nv, n, keep = len(fields), nx * ny * nz, []
+    ilim_ = np.ascontiguousarray(np.broadcast_to(np.asarray(ilim, dtype=np.int32), (max(nv, 1),)))
+    lo, hi = (np.ascontiguousarray(a, dtype=np.float64) for a in (umin, umax))
+    if lo.shape != (nv, ny + 1) or hi.shape != (nv, ny + 1):
+        raise TlabError("umin and umax must have the shape (nv, ny + 1)")
+    out = np.zeros((max(nv, 1), ny + 1, max(int(nbins), 0) + 2))
+    _stream_if_device(fields)
+    check(load().tlab_pdf_histogram_planes(nx, ny, nz, nv, int(nbins), c_vp(ilim_.ctypes.data), c_vp(lo.ctypes.data), c_vp(hi.ctypes.data),
+                                           _field_ptrs(fields, n, keep), int(igate), _gate_ptr(gate, n, keep), c_vp(out.ctypes.data)),
+          "tlab_pdf_histogram_planes")
+    return out[:nv]
+
+
+def pdf_analize(ibc, nbins, pdf, plim=1.0e-4):
+    """PDF_ANALIZE (utils/pdfs.f90:329): (umin_ext, umax_ext, nplim) of one pdf(nbins + 2)."""
+    pdf = np.ascontiguousarray(pdf, dtype=np.float64)
+    if pdf.shape != (nbins + 2,):
+        raise TlabError("pdf must hold nbins + 2 values")
+    lo, hi, npl = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+    check(load().tlab_pdf_analize(int(ibc), int(nbins), c_vp(pdf.ctypes.data), ctypes.byref(lo), ctypes.byref(hi), float(plim), ctypes.byref(npl)),
+          "tlab_pdf_analize")
+    return lo.value, hi.value, npl.value
+
+
+def pdf2v(nx, ny, nz, nbins, u, v):
+    """The calculation of PDF2V (statistics/pdf.f90:123): numpy (ny + 1, nb1*nb2 + 2 + 2*nb1), bin (up, vp) at (vp-1)*nb1 + up, then the centres
+    of the first and last u-bin and, per u-bin, of the first and last v-bin; the volume as the last plane (zero when ny == 1)."""
+    keep, n = [], nx * ny * nz
+    nb = np.ascontiguousarray(nbins, dtype=np.int32)
+    if nb.shape != (2,):
+        raise TlabError("nbins must hold two values")
+    out = np.zeros((ny + 1, max(int(nb[0]) * int(nb[1]), 0) + 2 + 2 * max(int(nb[0]), 0)))
+    _stream_if_device([u, v])
+    check(load().tlab_pdf2v(nx, ny, nz, c_vp(nb.ctypes.data), _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep), c_vp(out.ctypes.data)),
+          "tlab_pdf2v")
+    return out
+
+
+def gate_threshold(a, thr, gate=None):
+    """gate = a > thr ? 1 : 0 as int8 (the gate of dns_statistics.f90:106-110), of the kind of a: a torch tensor or a numpy array."""
+    keep = []
+    if isinstance(a, np.ndarray):
+        n = a.size
+        gate = np.empty(n, dtype=np.int8) if gate is None else gate
+    else:
+        import torch
+        n = a.numel()
+        gate = torch.empty(n, dtype=torch.int8, device=a.device) if gate is None else gate
+    _stream_if_device([a])
+    check(load().tlab_gate_threshold(_field_ptr(a, n, "a", keep), n, float(thr), _gate_ptr(gate, n, keep)), "tlab_gate_threshold")
+    return gate
