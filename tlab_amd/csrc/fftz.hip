@@ -204,6 +204,154 @@ __global__ void __launch_bounds__(1024) k_fftz(FftzArgs a) {
     }
 }
 
+// ---- the same transform with the exchanges in two rounds, real parts then imaginary parts (n <= 512) ----
+// What the exchange buffer must hold, not the registers, limits how many lines a CU has in flight, and rows of 256 B load and store faster than rows
+// of 128 B.  Here a workgroup owns FZS_T = 16 neighbouring lines and the buffer holds n * 16 doubles instead of n * 16 complex numbers (64 KB at
+// n = 512, two workgroups per CU): all threads write the real parts, barrier, all read them, barrier, then the same for the imaginary parts.  A
+// workgroup has n threads; a thread holds FZS_NV = 16 values: two radix-8 items of a pass, or four radix-4 / eight radix-2 items of the last one;
+// item q of a thread is j = jt + q * tl with tl = n / 16 threads per line.  The index maps (j + r m) * T + t and (j0 + r Ns) * T + t and every
+// operation on the data are those of k_fftz, so the output is the same to the bit.
+// The length N and with it the chain of passes are template arguments, so that the passes follow each other as straight-line code: values that
+// live across a run-time loop of passes cost the register allocator a second copy of all of them.
+// The twiddles of the passes after the first come from a copy of the table in LDS behind the exchange buffer (N * 16 B more), requested together
+// with the operands of the first pass and published by the first barrier of the first exchange: no trip to the global table between exchanges.
+constexpr int FZS_T = 16, FZS_NV = 16;
+
+// k_fftz leaves it to the compiler which of the two products of a.x b.y + a.y b.x is rounded on its own and which one goes into the fused
+// multiply-add, and the compiler settles that by the code around the expression.  To give the same bits this form writes out what k_fftz<., 8>
+// compiles to: the twiddle product (w = table entry, conjugated for SGN > 0; TAIL: the radix-4 / radix-2 pass) ...
+template <int SGN, bool TAIL>
+__device__ __forceinline__ cd fftz_twiddle(cd a, double2 w) {
+#pragma clang fp contract(off)
+    const double pyy = a.y * w.y, pxy = a.x * w.y, pyx = a.y * w.x;
+    if (SGN > 0) return {__builtin_fma(a.x, w.x, pyy), __builtin_fma(a.y, w.x, -pxy)};
+    if (TAIL) return {__builtin_fma(a.x, w.x, -pyy), __builtin_fma(a.x, w.y, pyx)};
+    return {__builtin_fma(a.x, w.x, -pyy), __builtin_fma(a.y, w.x, pxy)};
+}
+// ... and the products with W8 and W8^3 inside the 8-point transform (dft8 above)
+template <int SGN>
+__device__ __forceinline__ void fftz_dft8(cd *v) {
+#pragma clang fp contract(off)
+    cd e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6], o0 = v[1], o1 = v[3], o2 = v[5], o3 = v[7];
+    dft4<SGN>(e0, e1, e2, e3);
+    dft4<SGN>(o0, o1, o2, o3);
+    const double h = 0.70710678118654752440;
+    const double p1 = o1.x * h;
+    if (SGN > 0) {
+        const double p3 = o3.y * -h;
+        o1 = {__builtin_fma(-h, o1.y, p1), __builtin_fma(h, o1.y, p1)};
+        o3 = {__builtin_fma(-h, o3.x, p3), __builtin_fma(h, o3.x, p3)};
+    } else {
+        const double p3 = o3.x * -h;
+        o1 = {__builtin_fma(h, o1.y, p1), __builtin_fma(h, o1.y, -p1)};
+        o3 = {__builtin_fma(h, o3.y, p3), __builtin_fma(-h, o3.y, p3)};
+    }
+    o2 = mul_pm_i<SGN>(o2);
+    v[0] = e0 + o0; v[4] = e0 - o0;
+    v[1] = e1 + o1; v[5] = e1 - o1;
+    v[2] = e2 + o2; v[6] = e2 - o2;
+    v[3] = e3 + o3; v[7] = e3 - o3;
+}
+
+// twiddle products and the R-point transforms of a thread's items, in registers (Ns = product of the radices done before; tw: the global table in
+// the first pass, where entry 0 serves every item, the copy in LDS after it)
+template <int R, int SGN, int N, int Ns>
+__device__ __forceinline__ void fftz_items(const double2 *tw, cd (&v)[FZS_NV], int jt) {
+    constexpr int tl = N / FZS_NV;
+#pragma unroll
+    for (int q = 0; q < FZS_NV / R; ++q) {
+        const int j = jt + q * tl;
+        // twiddles exp(SGN 2 pi i (j % Ns) r / (Ns R))
+        const int k0 = (j & (Ns - 1)) * (N / (Ns * R));
+#pragma unroll
+        for (int r = 1; r < R; ++r) v[q * R + r] = fftz_twiddle<SGN, R != 8>(v[q * R + r], tw[(k0 * r) & (N - 1)]);
+        if constexpr (R == 8) fftz_dft8<SGN>(&v[q * R]);
+        else if constexpr (R == 4) dft4<SGN>(v[q * R], v[q * R + 1], v[q * R + 2], v[q * R + 3]);
+        else dft2<SGN>(v[q * R], v[q * R + 1]);
+    }
+}
+
+// the outputs of a radix-8 pass become the inputs of the radix-RN pass after it
+template <int RN, int N, int Ns>
+__device__ __forceinline__ void fftz_exchange(cd (&v)[FZS_NV], int t, int jt, double *lds) {
+    constexpr int T = FZS_T, NV = FZS_NV, tl = N / NV, mn = N / RN;
+    int wr[NV / 8];
+#pragma unroll
+    for (int q = 0; q < NV / 8; ++q) {
+        const int j = jt + q * tl;
+        wr[q] = ((j / Ns) * (Ns * 8) + (j & (Ns - 1))) * T + t;
+    }
+    const int rd = jt * T + t;
+    double re[NV];
+#pragma unroll
+    for (int q = 0; q < NV / 8; ++q)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) lds[wr[q] + r * Ns * T] = v[q * 8 + r].x;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV / RN; ++q)
+#pragma unroll
+        for (int r = 0; r < RN; ++r) re[q * RN + r] = lds[rd + (q * tl + r * mn) * T];
+    __syncthreads();          // every real part has been read
+#pragma unroll
+    for (int q = 0; q < NV / 8; ++q)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) lds[wr[q] + r * Ns * T] = v[q * 8 + r].y;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NV / RN; ++q)
+#pragma unroll
+        for (int r = 0; r < RN; ++r) v[q * RN + r] = {re[q * RN + r], lds[rd + (q * tl + r * mn) * T]};
+}
+
+// the pass at Ns and everything after it
+template <int SGN, int N, int Ns>
+__device__ __forceinline__ void fftz_chain(const FftzArgs &a, cd (&v)[FZS_NV], int t, int jt, long long col, bool colok, double *lds, const double2 *twl) {
+    constexpr int R = N / Ns >= 8 ? 8 : N / Ns, tl = N / FZS_NV;
+    fftz_items<R, SGN, N, Ns>(Ns == 1 ? a.tw : twl, v, jt);
+    if constexpr (Ns * R == N) {
+        if (colok) {
+#pragma unroll
+            for (int q = 0; q < FZS_NV / R; ++q) {
+                const int j = jt + q * tl;
+                const int j0 = (j / Ns) * (Ns * R) + (j & (Ns - 1));
+#pragma unroll
+                for (int r = 0; r < R; ++r) a.out[col + (long long)(j0 + r * Ns) * a.nlines] = make_double2(v[q * R + r].x, v[q * R + r].y);
+            }
+        }
+    } else {
+        static_assert(R == 8, "only the last pass has another radix");
+        constexpr int RN = N / (Ns * 8) >= 8 ? 8 : N / (Ns * 8);
+        if constexpr (Ns > 1) __syncthreads();          // every imaginary part of the exchange before has been read
+        fftz_exchange<RN, N, Ns>(v, t, jt, lds);
+        fftz_chain<SGN, N, Ns * 8>(a, v, t, jt, col, colok, lds, twl);
+    }
+}
+
+// blockDim = N.  The second launch bound is HIP's, waves per SIMD: two workgroups of up to eight waves per CU, at most 128 VGPRs.  Every thread
+// reaches every barrier: there is no branch around one.
+template <int SGN, int N>
+__global__ void __launch_bounds__(N, 4) k_fftz_split(FftzArgs a) {
+    extern __shared__ double fzs_lds[];
+    constexpr int T = FZS_T, tl = N / FZS_NV;
+    double2 *twl = reinterpret_cast<double2 *>(fzs_lds + N * T);
+    const int t = threadIdx.x % T;
+    const int jt = threadIdx.x / T;              // 0 .. tl - 1
+    const long long col = (long long)blockIdx.x * T + t;
+    const bool colok = col < a.nlines;
+    cd v[FZS_NV];
+#pragma unroll
+    for (int q = 0; q < FZS_NV / 8; ++q)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            double2 w = make_double2(0.0, 0.0);
+            if (colok) w = a.in[col + (long long)(jt + q * tl + r * (N / 8)) * a.nlines];
+            v[q * 8 + r] = {w.x, w.y};
+        }
+    twl[threadIdx.x] = a.tw[threadIdx.x];
+    fftz_chain<SGN, N, 1>(a, v, t, jt, col, colok, fzs_lds, twl);
+}
+
 // ================================================================================================
 // k_fftx_r2c : real-to-complex FFT of contiguous lines (OPR_Fourier_X_Forward: dfftw_plan_many_dft_r2c, opr_fourier.f90:163-166), in ONE pass
 // over the data.  rocFFT does this transform as a half-length complex FFT + a separate even/odd post-processing kernel (0.34 + 0.38 ms at
@@ -487,6 +635,33 @@ static void fftz_launch(int dir, const FftzArgs &a, hipStream_t st) {
     else hipLaunchKernelGGL((k_fftz<+1, T>), dim3(grid), dim3(block), lds, st, a);
 }
 
+template <int N>
+static void fftz_launch_split_n(int dir, const FftzArgs &a, hipStream_t st) {
+    const unsigned grid = (unsigned)((a.nlines + FZS_T - 1) / FZS_T);
+    const size_t lds = (size_t)N * FZS_T * sizeof(double) + (size_t)N * sizeof(double2);      // <= 72 KB
+    static bool attr_done = false;
+    if (lds > 64 * 1024 && !attr_done) {      // N = 512
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fftz_split<-1, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fftz_split<+1, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipGetLastError();
+        attr_done = true;
+    }
+    if (dir > 0) hipLaunchKernelGGL((k_fftz_split<-1, N>), dim3(grid), dim3(N), lds, st, a);      // forward: exp(-i ...)
+    else hipLaunchKernelGGL((k_fftz_split<+1, N>), dim3(grid), dim3(N), lds, st, a);
+}
+
+static void fftz_launch_split(int dir, const FftzArgs &a, hipStream_t st) {
+    switch (a.n) {      // FftzPlan::supported: 8^a * {1, 2, 4}
+    case 16: fftz_launch_split_n<16>(dir, a, st); break;
+    case 32: fftz_launch_split_n<32>(dir, a, st); break;
+    case 64: fftz_launch_split_n<64>(dir, a, st); break;
+    case 128: fftz_launch_split_n<128>(dir, a, st); break;
+    case 256: fftz_launch_split_n<256>(dir, a, st); break;
+    case 512: fftz_launch_split_n<512>(dir, a, st); break;
+    default: throw std::runtime_error("k_fftz: no split form for this length");
+    }
+}
+
 void FftzPlan::exec(int dir, const double *in, double *out, hipStream_t st) const {
     FftzArgs a{};
     a.in = reinterpret_cast<const double2 *>(in);
@@ -495,6 +670,14 @@ void FftzPlan::exec(int dir, const double *in, double *out, hipStream_t st) cons
     a.nlines = nlines; a.n = n; a.npass = (int)radix.size();
     for (size_t p = 0; p < radix.size(); ++p) a.radix[p] = radix[p];
     ProfScope ps("k_fftz", st, (double)nlines * n * 32.0);
+    // TLAB_FFTZ_SPLIT=0: the whole-complex exchange of k_fftz for every length (read on every call: one process can run both forms).  n = 1024
+    // and 2048 stay on it: the split form has not been measured there.
+    const char *es = getenv("TLAB_FFTZ_SPLIT");
+    if (n <= 512 && !(es && atoi(es) == 0)) {
+        fftz_launch_split(dir, a, st);
+        if (hipGetLastError() != hipSuccess) throw std::runtime_error("k_fftz launch failed");
+        return;
+    }
     static const int t16 = [] { const char *e = getenv("TLAB_FFTZ_T"); return e ? atoi(e) : 8; }();      // experiment: 16 lines (256-B rows), 1024 threads, one workgroup per CU
     if (n <= 512 && t16 == 16) fftz_launch<16>(dir, a, st);
     else if (n <= 1024) fftz_launch<8>(dir, a, st);       // 8 neighbouring lines per workgroup (128-B rows), n * 8 * 16 B of LDS
