@@ -400,6 +400,40 @@ int tlab_dns_set_buoyancy(tlab_dns_t d, int type, const double *vector, int nsca
 /* TLab_Sources_Flow on its own: hq += the terms above and nothing else.  HOST arrays of DEVICE pointers q[3], s[nscal], hq[3]; a component no force
  * touches is neither read nor written, a velocity or scalar no active term needs is not read.  At most 2^31 - 1 points. */
 int tlab_dns_sources_flow(tlab_dns_t d, double *const *q, double *const *s, double *const *hq);
+/* FI_PRESSURE_BOUSSINESQ(q, s, p, tmp1, tmp2, tmp, decomposition)   physics/fi_pressure_boussinesq.f90:8-280 -- the pressure of a velocity field,
+ * what DNS_STATISTICS_TEMPORAL (dns_statistics.f90:93), planes.f90, visuals.f90, averages.f90, pdfs.f90 and spectra.f90 call first.  q[3], s[nscal
+ * (+ 1 with a mixture)], tmp[ntmp]: HOST arrays of DEVICE pointers; p, tmp1, tmp2 and every tmp[i] hold isize_txc_field = (nx+2)*ny*nz doubles, as
+ * for tlab_opr_poisson.  ntmp >= 3; >= 7 for DCMP_ADVECTION and DCMP_DIFFUSION.  The codes are the reference's (include/dns_const.h:30-36);
+ * DCMP_RESOLVED (1) is not a case of the routine: it and any other value are TLAB_EINVAL, as are a null pointer and too few work arrays.
+ * In the reference's order: the three sums tmp[0..2] are zeroed; TLab_Sources_Flow is added (DCMP_TOTAL only: every other decomposition zeroes the
+ * sums again, :74-86); the nine OPR_Burgers terms are added (x, y, z of each component, bcs = 0); div of the sums by OPR_P1; the wall planes of
+ * the second sum are the Neumann data; OPR_Poisson(BCS_NN); OPR_FILTER(p) where a [PressureFilter] is set.  No buffer zone acts (the routine has
+ * none), remove_divergence plays no role (no q / dte enters), no scalar equation is launched.
+ * The call is a ROUTE through the stages of the substep (csrc/rhs.cpp), with tmp[0..2] in the place of the tendencies and p in that of the forcing:
+ * the five- and three-launch Burgers forms, the per-equation sums on the fast kernels and the fused divergence launches serve wherever they serve
+ * the substep.  Against the reference, which adds the sources first and then X, Y, Z, those routes add the body forces in the mid-sequence slot and
+ * the directions in launch order: rounding only.
+ *   DCMP_DIFFUSION  the same launches with an all-zero advecting velocity (tmp[6], the reference's tmp9 = 0).  The reference AS COMPILED does not
+ *                   compute this: its OPR_Burgers ignores the velocity argument under OPR_B_SELF and takes the transposed velocity of the call
+ *                   before under OPR_B_U_IN, so its x and y terms still advect; the device computes what the call states.
+ *   DCMP_ADVECTION  DCMP_ADVDIFF minus DCMP_DIFFUSION (:145-148): two passes of the Burgers launches, the sums of the second in tmp[3..5].
+ *   DCMP_CORIOLIS, DCMP_BUOYANCY  one launch of k_body_force on zeroed sums with the other term switched off.  The reference's DCMP_BUOYANCY
+ *                   subtracts bbackground for the y component only (:171-177) where TLab_Sources_Flow subtracts it for all three
+ *                   (tlab_sources.f90:68); the device holds one profile: a horizontal gravity component together with a non-zero bbackground is
+ *                   TLAB_EUNSUPPORTED under this decomposition.
+ * Anelastic runs (the sums weighted by rbackground before their derivative; the wall planes scaled once, by rbackground at the wall) and the
+ * staggered pressure grid (the sums and the planes interpolated onto the pressure nodes, p back by OPR_P0_INT_PV along z, then x, :272-275) take
+ * the literal stages.  Work arrays a route needs beyond the caller's are the library's, allocated on first use and kept with the driver.
+ * q, s, hq, hs and the driver's state are unchanged: the one-shot flag of tlab_dns_begin_step is neither read nor consumed.  A recorded substep
+ * runs first; like tlab_dns_sources_flow the call returns with its launches enqueued on the library's stream. */
+#define TLAB_DCMP_TOTAL 0
+#define TLAB_DCMP_ADVECTION 2
+#define TLAB_DCMP_ADVDIFF 3
+#define TLAB_DCMP_DIFFUSION 4
+#define TLAB_DCMP_CORIOLIS 5
+#define TLAB_DCMP_BUOYANCY 6
+int tlab_dns_pressure(tlab_dns_t d, int decomposition, double *const *q, double *const *s, double *p, double *tmp1, double *tmp2, double *const *tmp,
+                      int ntmp);
 /* Cloud-top physics of the single-domain driver: [Thermodynamics] Type = Linear, Mixture = AirWaterLinear, and [Infrared] Type = Bulk1dLocal
  * (which the reference maps to grayliquid) -- examples/Case16-21, 54, 55.
  *   Mixture: TLAB_MIXT_NONE or TLAB_MIXT_AIRWATERLINEAR (the reference's MIXT_TYPE_AIRWATER_LINEAR) with thermo_param(1:nparam), HOST values,
@@ -653,6 +687,18 @@ int tlab_dns_set_slab(tlab_dns_t d, int koffset);
 int tlab_time_courant(tlab_dns_t d, double *const *q, double cfla, double cfld, double *pmax, double *dtime);
 int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *tmp1);
 int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *amn, double *amx);
+/* FI_VORTICITY(nx,ny,nz,u,v,w,result,tmp1,tmp2)   mappings/fi_vorticity.f90:28-59 : result = (v,x - u,y)^2 + (u,z - w,x)^2 + (w,y - v,z)^2, the
+ *   squared magnitude of the vorticity.  Six OPR_Partial(OPR_P1, bcs = 0) with the driver's plans in the reference's order -- v,x  u,y  u,z  w,x
+ *   w,y  v,z -- into txc6[0..5] (a HOST array of six DEVICE pointers, nx*ny*nz doubles each, which hold them on return), then ONE pass
+ *   (k_vorticity_magnitude) that reads the six and writes ((a-b)*(a-b) + (c-d)*(c-d)) + (e-f)*(e-f), unfused: the reference's operation order, where
+ *   the reference makes three two-operand passes over result through two work arrays.  result aliases none of the six.  No IBM.  Returns with the
+ *   launches enqueued on the library's stream.
+ * tlab_vorticity_from_gradients: that pass on its own, no driver handle, for arrays of either kind (all device -> the kernel, all host or no
+ *   tlab_init -> a host loop with the same operations; a mix: TLAB_EINVAL).  16-byte accesses where all seven arrays are 16-byte aligned, 8-byte
+ *   accesses otherwise.  1 <= n <= 2^31 - 1. */
+int tlab_fi_vorticity(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *const *txc6);
+int tlab_vorticity_from_gradients(long long n, const double *vx, const double *uy, const double *uz, const double *wx, const double *wy,
+                                  const double *vz, double *result);
 /* DNS_BOUNDS_CONTROL with the location of its failure branch (tools/dns/dns_local.f90:157-230, incompressible / anelastic):
  *   dil_min, dil_max = min / max of div(q) (= -FI_INVARIANT_P, logs_data(10:11)); loc_min, loc_max (int[3] each; NULL = not wanted) = the 1-based
  *   (i, j, k) of the first occurrence in column-major order (Fortran minloc / maxloc), k offset by tlab_dns_set_slab.  q[3], txc[9]: HOST arrays
@@ -787,7 +833,14 @@ int tlab_dns_avg_gradients_scal(tlab_dns_t d, const double *s, double *const *q,
  *   nbins[0] x nbins[1] histogram with both indices clipped to the last bin.  pdf: (nbins[0]*nbins[1] + 2 + 2*nbins[0], ny+1), bin (up, vp) at
  *   (vp-1)*nbins[0] + up.  nbins[0]*nbins[1] at most 4096, nbins[0] at most 1024.
  * tlab_gate_threshold: gate[i] = a[i] > thr ? 1 : 0 for n points (the gate of dns_statistics.f90:106-110); a and gate of one kind.  On the device
- *   the call returns with the kernel enqueued on the library's stream. */
+ *   the call returns with the kernel enqueued on the library's stream.
+ * tlab_inter_n_xz: the calculation of INTER_N_XZ (statistics/avg_xz.f90:109-153; no file is written) over INTER1V2D (utils/averages.f90:214-239),
+ *   local part: inter(j, ip) = count(gate(:, j, :) == ip) / real(nx*nz) for every plane j and level ip = 1 .. np, inter(ny, np) in Fortran
+ *   order, HOST memory.  Values of the gate outside 1 .. np, 0 included, are not counted.  On the device all planes and levels come from ONE pass
+ *   over the gate (k_gate_count: 32-bit counters in LDS, a second kernel sums the chunks into 64-bit counts and divides once per output); a count
+ *   is exact and so is the reference's sum of 1.0, so the result is the reference's bit for bit.  The call synchronises the stream.
+ *   TLAB_EINVAL: nx, ny or nz < 1, np outside 1 .. 127, a null pointer. */
+int tlab_inter_n_xz(int nx, int ny, int nz, int np, const signed char *gate, double *inter);
 int tlab_pdf1v_n(int nx, int ny, int nz, int nv, int nbins, const int *ibc, const double *umin, const double *umax, const double *const *u,
                  int igate, const signed char *gate, double *pdf);
 int tlab_pdf_minmax_planes(int nx, int ny, int nz, int nv, const double *const *u, int igate, const signed char *gate, double *umin, double *umax);

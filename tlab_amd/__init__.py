@@ -15,4 +15,5 @@ from .operators import (  # noqa: F401
     TLab_Transpose, PoissonPlan, OPR_Poisson, OPR_Helmholtz, poisson_set_exact, BOUNDARY_BCS_NEUMANN_Y,
     avg_ik_v, avg1v2d_v, avg_moments_flow, avg_moments_scal, avg_gradients_flow, avg_ugradp, avg_gradients_scal,
     pdf1v_n, pdf_minmax_planes, pdf_histogram_planes, pdf_analize, pdf2v, gate_threshold,
+    fi_vorticity, vorticity_from_gradients, inter_n_xz,
 )

@@ -55,6 +55,45 @@ int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const do
     });
 }
 
+// FI_VORTICITY (mappings/fi_vorticity.f90:28-59): the six derivatives in the reference's order, kept in txc6, then one pass over them
+int tlab_fi_vorticity(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *const *txc6) {
+    return catch_fail([&] {
+        if (!d || !u || !v || !w || !result || !txc6) throw Fail(TLAB_EINVAL, "tlab_fi_vorticity: bad arguments");
+        for (int i = 0; i < 6; ++i)
+            if (!txc6[i]) throw Fail(TLAB_EINVAL, "tlab_fi_vorticity: a null txc array");
+        const int nx = d->nx, ny = d->ny, nz = d->nz;
+        const double *fld[6] = {v, u, u, w, w, v};      // v,x  u,y  u,z  w,x  w,y  v,z
+        const int dir[6] = {1, 2, 3, 1, 2, 3};
+        for (int i = 0; i < 6; ++i) ok(tlab_opr_partial(dir[i], d->g[dir[i] - 1], TLAB_OPR_P1, nx, ny, nz, 0, fld[i], txc6[i], nullptr), "OPR_Partial");
+        hk(launch_vorticity_magnitude(txc6[0], txc6[1], txc6[2], txc6[3], txc6[4], txc6[5], result, (long long)nx * ny * nz, tlab_current_stream()),
+           "k_vorticity_magnitude");
+    });
+}
+
+// ... and the pass on its own, for arrays of either kind (classified like tlab_minmax_any; a mix is refused)
+int tlab_vorticity_from_gradients(long long n, const double *vx, const double *uy, const double *uz, const double *wx, const double *wy,
+                                  const double *vz, double *result) {
+#pragma clang fp contract(off)      // the host loop keeps every operation as written, like the kernel
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        const char *who = "tlab_vorticity_from_gradients";
+        const double *a[7] = {vx, uy, uz, wx, wy, vz, result};
+        if (n < 1 || n > 0x7fffffffLL) throw Fail(TLAB_EINVAL, std::string(who) + ": n must be 1 to 2^31 - 1");
+        int ndev = 0;
+        for (const double *p : a) {
+            if (!p) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
+            const int on = tlab_device_ready() ? tlab_pointer_on_device(p) : 0;
+            if (on < 0) throw Fail(on, std::string(who) + ": " + tlab_last_error());
+            ndev += on ? 1 : 0;
+        }
+        if (ndev != 0 && ndev != 7) throw Fail(TLAB_EINVAL, std::string(who) + ": host and device arrays in one call");
+        if (ndev) hk(launch_vorticity_magnitude(vx, uy, uz, wx, wy, vz, result, n, tlab_current_stream()), "k_vorticity_magnitude");
+        else
+            for (long long i = 0; i < n; ++i)
+                result[i] = ((vx[i] - uy[i]) * (vx[i] - uy[i]) + (uz[i] - wx[i]) * (uz[i] - wx[i])) + (wy[i] - vz[i]) * (wy[i] - vz[i]);
+    }, TLAB_EINVAL);
+}
+
 // Section 3 of AVG_FLOW_XZ (statistics/avg_flow_xz.f90:976-986) in front of the gradient statistics, and with p the pressure block (:670-674) in
 // front of that: the derivatives by the driver's plans, bcs = 0, into the reference's arrays (dudx .. dwdz = txc[0..8]; dp/dx, dp/dy, dp/dz in
 // dwdx, dwdy, dwdz first)

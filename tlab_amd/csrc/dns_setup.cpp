@@ -436,6 +436,7 @@ int tlab_dns_set_buoyancy(tlab_dns_t d, int type, const double *vector, int nsca
             hk(hipStreamSynchronize(tlab_current_stream()), "sync");      // (a kernel that reads the old profile may still be in flight)
             hk(hipMemcpy(d->bprof, prof.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy");
         }
+        d->bback = F.bod >= 2 && bbackground && std::any_of(bbackground, bbackground + d->ny, [](double v) { return v != 0.0; });
         d->force.bod = F.bod; d->force.ns = F.ns;
         for (int i = 0; i < 3; ++i) d->force.g[i] = F.g[i];
         for (int i = 0; i < tlab::BODY_FORCE_MAX_SCAL; ++i) { d->force.c[i] = F.c[i]; d->force.sidx[i] = F.sidx[i]; }

@@ -51,6 +51,9 @@ struct tlab_dns {
     // the buoyancy function subtracts (or starts from), made from bbackground when it is set
     tlab::BodyForce force;
     double *bprof = nullptr;
+    bool bback = false;                            // a non-zero bbackground went into bprof (DCMP_BUOYANCY of the pressure subtracts it for y alone)
+    // tlab_dns_pressure (FI_PRESSURE_BOUSSINESQ): the work arrays of a route beyond what the caller hands, isize_txc_field doubles each, made on first use
+    double *pwork[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     // [Thermodynamics] Mixture (tlab_dns_set_mixture): with one set, s carries inb_scal_array = nscal + 1 arrays, the last the diagnostic liquid
     int mixture = TLAB_MIXT_NONE;
     std::vector<double> thermo_param;
@@ -80,6 +83,7 @@ struct tlab_dns {
         for (NeuW &n : neuw) if (n.w) (void)hipFree(n.w);
         if (wall_planes) (void)hipFree(wall_planes);
         if (bprof) (void)hipFree(bprof);
+        for (double *p : pwork) if (p) (void)hipFree(p);
         if (ir.tab) (void)hipFree(ir.tab);
         tlab_internal_particles_free(particles);
         for (auto &g : buff)
@@ -104,6 +108,10 @@ TLAB_HIDDEN void follow_anelastic(tlab_dns *d);
 // the launches of one substep; tail: what follows the RHS (SubstepTail), NULL: the RHS on its own -- no update, no scalar zones, no forces
 TLAB_HIDDEN void rhs_substep(tlab_dns *d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
                              const SubstepTail *tail);
+// FI_PRESSURE_BOUSSINESQ: the Burgers, forcing and solve stages of that substep on the sums tmp[0..2] (tmp[0..6] for DCMP_ADVECTION and _DIFFUSION)
+// with p as the forcing array; dcmp: a checked TLAB_DCMP_*.  No driver state changes but the scratch d->pwork and the solver's two wall planes.
+TLAB_HIDDEN void pressure_boussinesq(tlab_dns *d, int dcmp, double *const *q, double *const *s, double *p, double *tmp1, double *tmp2,
+                                     double *const *tmp);
 
 // ---- dns_setup.cpp: the launches the substep shares with the entry points tlab_dns_buffer_relax_* / _sources_* / _diagnostic ----
 // RELAX_BLOCK of the blocks of one group (0: BOUNDARY_BUFFER_RELAX_FLOW on q, hq; 1: BOUNDARY_BUFFER_RELAX_SCAL on s, hs), Jmin before Jmax, four fields a launch

@@ -175,6 +175,9 @@ hipError_t launch_pencil_repack(double *a, double *buf, int nxh, int ny, int kma
 hipError_t launch_add1(double *h, const double *a, long long n, hipStream_t st);
 hipError_t launch_axpy1(double *o, const double *a, const double *b, double s, long long n, hipStream_t st);
 hipError_t launch_sum3(double *a, const double *b, const double *c, long long n, hipStream_t st);
+// r = ((vx - uy)**2 + (uz - wx)**2) + (wy - vz)**2, unfused (FI_VORTICITY); r aliases no input; at most 2^31 - 1 points
+hipError_t launch_vorticity_magnitude(const double *vx, const double *uy, const double *uz, const double *wx, const double *wy, const double *vz,
+                                      double *r, long long n, hipStream_t st);
 hipError_t launch_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n, hipStream_t st);
 
 hipError_t launch_get_wall_planes(const double *f, double *hb, double *ht, int nx, int ny, int nz, hipStream_t st);
@@ -254,6 +257,9 @@ hipError_t launch_pdf2v_range(const PdfFields &F, int nb1, const double *iv, dou
 hipError_t launch_pdf2v_hist(const PdfFields &F, int nb1, int nb2, const double *iv, const double *viv, unsigned *cnt, unsigned long long *volpart,
                              double *pdf, hipStream_t st);
 hipError_t launch_gate_threshold(const double *a, long long n, double thr, signed char *gate, hipStream_t st);
+//   launch_gate_count  INTER1V2D of every plane and level 1 .. np (at most GATE_MAX_LEVELS): cnt: scratch, pdf_chunks(nz) * ny * np 32-bit words;
+//                      inter: [np][ny] = count / real(nx * nz)
+hipError_t launch_gate_count(const signed char *gate, int nx, int ny, int nz, int np, unsigned *cnt, double *inter, hipStream_t st);
 
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);

@@ -1,6 +1,6 @@
 // C ABI of the plane PDFs (include/tlab_amd.h): tlab_pdf1v_n (PDF1V_N, statistics/pdf.f90:14-91, without its file), its two passes on their own
 // tlab_pdf_minmax_planes / tlab_pdf_histogram_planes, tlab_pdf_analize (PDF_ANALIZE, host arithmetic), tlab_pdf2v (PDF2V, :123-159) and
-// tlab_gate_threshold.  Device arrays take the kernels of pdfs.hip, host arrays the reference's loops below; a host array never reaches a kernel, a
+// tlab_gate_threshold, and the intermittency factors of a gate, tlab_inter_n_xz (INTER_N_XZ, statistics/avg_xz.f90:109-153).  Device arrays take the kernels of pdfs.hip, host arrays the reference's loops below; a host array never reaches a kernel, a
 // device array is never read by the host.  The bin of a point, the step of an interval and PDF_ANALIZE are those of pdfs_host.hpp on both sides;
 // every interval bound is computed HERE, on the host, for both kinds of array.
 #include "../../include/tlab_amd.h"
@@ -359,6 +359,35 @@ int tlab_gate_threshold(const double *a, long long n, double thr, signed char *g
         if (on_device("tlab_gate_threshold", {a, gate})) hk(launch_gate_threshold(a, n, thr, gate, tlab_current_stream()), "k_gate_threshold");
         else
             for (long long i = 0; i < n; ++i) gate[i] = a[i] > thr ? 1 : 0;
+    }, TLAB_EINVAL);
+}
+
+// INTER_N_XZ (statistics/avg_xz.f90:109-153, without its file) over INTER1V2D (utils/averages.f90:214-239): a count is exact and so is the
+// reference's sum of 1.0_wp, so both kinds give the reference's bits
+int tlab_inter_n_xz(int nx, int ny, int nz, int np, const signed char *gate, double *inter) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        const char *who = "tlab_inter_n_xz";
+        if (nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": nx, ny, nz must be at least 1");
+        if (np < 1 || np > GATE_MAX_LEVELS) throw Fail(TLAB_EINVAL, std::string(who) + ": np must be 1 to " + std::to_string(GATE_MAX_LEVELS));
+        if (!gate || !inter) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
+        const Box B{who, on_device(who, {gate}), nx, ny, nz, 0, gate};
+        const double denom = (double)((long long)nx * nz);
+        if (!B.dev) {
+            for (int j = 0; j < ny; ++j)
+                for (int ip = 1; ip <= np; ++ip) {
+                    double avg = 0.0;
+                    for_plane(B, j, [&](size_t i) { if (gate[i] == ip) avg = avg + 1.0; });
+                    inter[(size_t)(ip - 1) * ny + j] = avg / denom;
+                }
+            return;
+        }
+        hipStream_t st = tlab_current_stream();
+        const size_t nout = (size_t)ny * np, o_cnt = up16(nout * sizeof(double));
+        char *buf = scratch(o_cnt + up16((size_t)pdf_chunks(nz) * nout * sizeof(unsigned)));
+        hk(launch_gate_count(gate, nx, ny, nz, np, (unsigned *)(buf + o_cnt), (double *)buf, st), "k_gate_count");
+        hk(hipMemcpyAsync(inter, buf, nout * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(intermittency)");
+        hk(hipStreamSynchronize(st), "sync");
     }, TLAB_EINVAL);
 }
 

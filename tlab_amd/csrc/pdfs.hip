@@ -20,6 +20,7 @@
 //                           histogram IS the sum of the planes')
 //   k_pdf_hist_volume       sums those over the planes.
 //   k_gate_threshold        gate = a > thr ? 1 : 0 (the gate of dns_statistics.f90:106-110).
+//   k_gate_count            INTER1V2D for every plane and level in one pass over the gate (further down), k_gate_count_final its chunks.
 //
 // No global atomics, no float atomics, no workgroup that waits for or counts another: integer counts are exact in any order, so a call repeats
 // its bits, and they are the reference's as long as a count stays below 2^53 (a chunk of one plane below 2^32).
@@ -338,6 +339,54 @@ __global__ void __launch_bounds__(PDF_THREADS) k_gate_threshold(const double *__
     for (long long i = (long long)blockIdx.x * PDF_THREADS + threadIdx.x; i < n; i += stride) gate[i] = a[i] > thr ? 1 : 0;
 }
 
+// ---- INTER1V2D (utils/averages.f90:214-239) for every plane and level at once: the counts of gate == 1 .. np -------------------------------------
+// k_gate_count: the grid and the rows of k_pdf_hist, grid (ny, nchunks).  A row is nx gate bytes; where its first byte is 16-byte aligned (the same
+// for every lane of the wave) a lane takes 16 of them per load and the rest of the row goes byte by byte, otherwise the whole row does.  Level g in
+// 1 .. np adds to tab[(g - 1) GATE_REP + lane % GATE_REP], a 32-bit counter in LDS; every other value, 0 included, is not counted.  The counts of
+// the workgroup go to cnt[c][j][np] with plain vector stores.
+constexpr int GATE_REP = 32;
+
+__global__ void __launch_bounds__(PDF_THREADS) k_gate_count(const signed char *__restrict__ gate, int nx, int ny, int nz, int np,
+                                                            unsigned *__restrict__ cnt) {
+    __shared__ unsigned tab[GATE_MAX_LEVELS * GATE_REP];      // [np][GATE_REP]
+    const int j = blockIdx.x, c = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, rl = lane & (GATE_REP - 1);
+    for (int t = threadIdx.x; t < np * GATE_REP; t += PDF_THREADS) tab[t] = 0u;
+    __syncthreads();
+    auto count = [&](int g) {
+        if (g >= 1 && g <= np) atomicAdd(&tab[(g - 1) * GATE_REP + rl], 1u);
+    };
+    const int k1 = min(nz, (c + 1) * PDF_ROWS_PER_GROUP);
+    for (int k = c * PDF_ROWS_PER_GROUP + wave; k < k1; k += PDF_WAVES) {
+        const signed char *row = gate + ((size_t)k * ny + j) * nx;
+        const int nvec = ((uintptr_t)row & 15) == 0 ? nx / 16 : 0;
+        for (int i = lane; i < nvec; i += 64) {
+            const uint4 v = reinterpret_cast<const uint4 *>(row)[i];
+            const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) count((int)(signed char)(w[e >> 2] >> (8 * (e & 3))));
+        }
+        for (int i = nvec * 16 + lane; i < nx; i += 64) count((int)row[i]);
+    }
+    __syncthreads();
+    unsigned *out = cnt + ((size_t)c * ny + j) * np;
+    for (int t = threadIdx.x; t < np; t += PDF_THREADS) {
+        unsigned s = 0u;
+        for (int r = 0; r < GATE_REP; ++r) s += tab[t * GATE_REP + ((r + threadIdx.x) & (GATE_REP - 1))];      // (rotated, as in k_pdf_hist)
+        out[t] = s;
+    }
+}
+
+// inter[ip][j] = (the chunks of plane j, level ip + 1, as a 64-bit integer) / denom: grid (ny); one division per output, in fp64
+__global__ void __launch_bounds__(PDF_THREADS) k_gate_count_final(const unsigned *__restrict__ cnt, int nchunks, int ny, int np, double denom,
+                                                                  double *__restrict__ inter) {
+    const int j = blockIdx.x;
+    for (int ip = threadIdx.x; ip < np; ip += PDF_THREADS) {
+        unsigned long long s = 0ull;
+        for (int c = 0; c < nchunks; ++c) s += cnt[((size_t)c * ny + j) * np + ip];
+        inter[(size_t)ip * ny + j] = (double)s / denom;
+    }
+}
+
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // the argument block of one launch; false: bad arguments
@@ -450,6 +499,17 @@ hipError_t launch_pdf2v_hist(const PdfFields &F, int nb1, int nb2, const double 
     }
     hipLaunchKernelGGL(k_pdf_hist_planes, dim3((unsigned)F.ny, 1u), block, 0, st, cnt, nchunks, F.ny, a.ntab, nb, a.ntab == 2 ? 1u : 0u, pdf, volpart);
     if (F.ny > 1) hipLaunchKernelGGL(k_pdf_hist_volume, dim3((unsigned)((nb + 63) / 64), 1u), block, 0, st, volpart, F.ny, nb, pdf);
+    return hipGetLastError();
+}
+
+hipError_t launch_gate_count(const signed char *gate, int nx, int ny, int nz, int np, unsigned *cnt, double *inter, hipStream_t st) {
+    if (!gate || !cnt || !inter || nx < 1 || ny < 1 || nz < 1 || np < 1 || np > GATE_MAX_LEVELS || pdf_chunks(nz) > 65535) return hipErrorInvalidValue;
+    const int nchunks = pdf_chunks(nz);
+    {
+        ProfScope ps("k_gate_count", st, (double)nx * ny * (double)nz);
+        hipLaunchKernelGGL(k_gate_count, dim3((unsigned)ny, (unsigned)nchunks), dim3(PDF_THREADS), 0, st, gate, nx, ny, nz, np, cnt);
+    }
+    hipLaunchKernelGGL(k_gate_count_final, dim3((unsigned)ny), dim3(PDF_THREADS), 0, st, cnt, nchunks, ny, np, (double)((long long)nx * nz), inter);
     return hipGetLastError();
 }
 

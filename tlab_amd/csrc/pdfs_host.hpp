@@ -20,7 +20,8 @@ constexpr int PDF_ROWS_PER_GROUP = 32;      // rows of k one workgroup of k_pdf_
 constexpr int PDF_MAX_BINS = 4096;          // nbins of tlab_pdf1v_n, nbins(1)*nbins(2) of tlab_pdf2v: above it TLAB_EINVAL
 constexpr int PDF_LDS_WORDS = 8192;         // 32-bit counters of one workgroup: 2 tables (plane, volume) x nbins x replicas
 constexpr int PDF_FIELDS_PER_LAUNCH = 8;    // more fields go in groups
-constexpr double PDF_BIG = 1.0e20;          // big_wp (base/tlab_constants.f90): where the gated min / max start
+constexpr int GATE_MAX_LEVELS = 127;        // np of tlab_inter_n_xz: the positive values of an int8 gate
+constexpr double PDF_BIG = 1.0e20;         // big_wp (base/tlab_constants.f90): where the gated min / max start
 
 // the 0-based bin of u, or -1 for a point that is not counted
 __host__ __device__ __forceinline__ int pdf_bin(double u, double umin, double ustep, int nbins, bool ext) {

@@ -73,6 +73,36 @@ __global__ void __launch_bounds__(256) k_sum3(double *__restrict__ a, const doub
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) a[n - 1] = a[n - 1] + b[n - 1] + c[n - 1];
 }
 
+// r = ((vx - uy)**2 + (uz - wx)**2) + (wy - vz)**2      (FI_VORTICITY, mappings/fi_vorticity.f90:41-51: the reference's three two-operand passes
+// over result in one, every operation as written).  V = 2: 16-byte accesses (all seven arrays 16-byte aligned), the odd last point by one thread;
+// V = 1: 8-byte accesses.
+__device__ __forceinline__ double vorticity_magnitude(double vx, double uy, double uz, double wx, double wy, double vz) {
+#pragma clang fp contract(off)
+    return ((vx - uy) * (vx - uy) + (uz - wx) * (uz - wx)) + (wy - vz) * (wy - vz);
+}
+template <int V>
+__global__ void __launch_bounds__(256) k_vorticity_magnitude(const double *__restrict__ vx, const double *__restrict__ uy,
+                                                             const double *__restrict__ uz, const double *__restrict__ wx,
+                                                             const double *__restrict__ wy, const double *__restrict__ vz, double *__restrict__ r,
+                                                             long long n) {
+    const long long stride = (long long)gridDim.x * blockDim.x, i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (V == 2) {
+        const long long n2 = n >> 1;
+        for (long long i = i0; i < n2; i += stride) {
+            const double2 a = reinterpret_cast<const double2 *>(vx)[i], b = reinterpret_cast<const double2 *>(uy)[i],
+                          c = reinterpret_cast<const double2 *>(uz)[i], d = reinterpret_cast<const double2 *>(wx)[i],
+                          e = reinterpret_cast<const double2 *>(wy)[i], f = reinterpret_cast<const double2 *>(vz)[i];
+            double2 o;
+            o.x = vorticity_magnitude(a.x, b.x, c.x, d.x, e.x, f.x);
+            o.y = vorticity_magnitude(a.y, b.y, c.y, d.y, e.y, f.y);
+            reinterpret_cast<double2 *>(r)[i] = o;
+        }
+        if ((n & 1) && i0 == 0) r[n - 1] = vorticity_magnitude(vx[n - 1], uy[n - 1], uz[n - 1], wx[n - 1], wy[n - 1], vz[n - 1]);
+    } else {
+        for (long long i = i0; i < n; i += stride) r[i] = vorticity_magnitude(vx[i], uy[i], uz[i], wx[i], wy[i], vz[i]);
+    }
+}
+
 // h1 -= a ; h2 -= b ; h3 -= c     (hq = hq - grad p, :348-352)
 __global__ void __launch_bounds__(256) k_sub3(double *__restrict__ h1, double *__restrict__ h2, double *__restrict__ h3,
                                               const double *__restrict__ a, const double *__restrict__ b, const double *__restrict__ c, long long n) {
@@ -438,6 +468,17 @@ hipError_t launch_axpy3w(double *o1, double *o2, double *o3, const double *h1, c
 hipError_t launch_sum3(double *a, const double *b, const double *c, long long n, hipStream_t st) {
     ProfScope ps("k_sum3", st, (double)n * 32);
     hipLaunchKernelGGL(k_sum3, dim3(pw_grid(n / 2)), dim3(256), 0, st, a, b, c, n);
+    return CHECK_LAUNCH();
+}
+hipError_t launch_vorticity_magnitude(const double *vx, const double *uy, const double *uz, const double *wx, const double *wy, const double *vz,
+                                      double *r, long long n, hipStream_t st) {
+    if (!vx || !uy || !uz || !wx || !wy || !vz || !r || n < 1 || n > 0x7fffffffLL) return hipErrorInvalidValue;
+    uintptr_t bits = 0;
+    for (const void *p : {(const void *)vx, (const void *)uy, (const void *)uz, (const void *)wx, (const void *)wy, (const void *)vz, (const void *)r})
+        bits |= (uintptr_t)p;
+    ProfScope ps("k_vorticity_magnitude", st, (double)n * 56);
+    if ((bits & 15) == 0) hipLaunchKernelGGL(k_vorticity_magnitude<2>, dim3(pw_grid((n + 1) / 2)), dim3(256), 0, st, vx, uy, uz, wx, wy, vz, r, n);
+    else hipLaunchKernelGGL(k_vorticity_magnitude<1>, dim3(pw_grid(n)), dim3(256), 0, st, vx, uy, uz, wx, wy, vz, r, n);
     return CHECK_LAUNCH();
 }
 hipError_t launch_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n, hipStream_t st) {

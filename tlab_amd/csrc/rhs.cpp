@@ -2,8 +2,9 @@
 // Runge-Kutta substep around it (TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT, tools/dns/time.f90:559-664, and the scaling
 // of the tendencies, :261-298), orchestrating the device operators so that no field leaves HBM during a substep.
 // Same operator sequence, same scratch roles (tmp1..tmp9 = txc(:,1:9)) as the reference.
-// This file is the substep and nothing else: the route (which launches a configuration makes, decided once), the stages that make them, and the
-// three entry points.  The driver's state is in dns_state.hpp; its creation and settings in dns_setup.cpp.
+// This file is the substep and nothing else: the route (which launches a configuration makes, decided once), the stages that make them, the
+// three entry points, and the one other route through the same stages, which stops at the pressure (FI_PRESSURE_BOUSSINESQ: pressure_boussinesq,
+// tlab_dns_pressure).  The driver's state is in dns_state.hpp; its creation and settings in dns_setup.cpp.
 #include "../../include/tlab_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -113,6 +114,7 @@ struct Route {
     int ibc_q[3];                 // the Neumann variant of u, v, w (WallBcs::variant: 0 none, 1 jmin, 2 jmax, 3 both) ...
     std::vector<int> ibc_s;       // ... and of the scalars
     bool any_q;                   // a velocity component with a Neumann wall: its planes need the finished tendency first
+    bool p_only;                  // the route stops at the pressure (PressureOnly below): no scalar equation, no dp/dy, nothing after the solve
     bool walls_dirichlet;         // no velocity wall is Neumann (a Neumann wall of any component sends all three through the unfused subtraction)
     bool any_surface;             // a scalar with the dynamic surface model: its wall planes are not zero, and it keeps planes of its own
     // ---- the equations: every fused form assumes the plain operators; anelastic runs, the staggered pressure grid
@@ -183,15 +185,20 @@ struct Route {
     bool gw_defer[3];
 };
 
+// What a call that stops at the pressure (FI_PRESSURE_BOUSSINESQ, pressure_boussinesq below) asks of a route: the three momentum equations alone, no
+// buffer zones (the reference's routine has none), and the body forces whether or not a tail is there.  NULL: the substep, or the RHS on its own.
+struct PressureOnly { bool forces; };
+
 // The one side effect: neumann_weights builds and caches the weights of a variant on first use (allocations, launches, a synchronisation; it may
 // throw).  tlab_dns_set_bcs has built those of the variants in use, so inside a substep the call is a lookup.
-Route decide_route(tlab_dns *d, const SubstepTail *tail) {
+Route decide_route(tlab_dns *d, const SubstepTail *tail, const PressureOnly *po = nullptr) {
     static const bool finish_off = [] { const char *e = getenv("TLAB_SCALAR_FINISH"); return e && atoi(e) == 0; }();
     const char *npe = getenv("TLAB_NEUMANN_PLANES");
     const bool neu_planes = !(npe && atoi(npe) == 0);
-    const int nx = d->nx, ny = d->ny, nz = d->nz, ns = d->nscal;
+    const int nx = d->nx, ny = d->ny, nz = d->nz, ns = po ? 0 : d->nscal;
     tlab_fdm_plan_t gx = d->g[0], gy = d->g[1], gz = d->g[2];
     Route r;
+    r.p_only = po != nullptr;
     bool scal_neu = false;
     r.any_q = r.any_surface = false;
     for (int iq = 0; iq < 3; ++iq) r.any_q = (r.ibc_q[iq] = d->bcs.flow_variant(iq)) != 0 || r.any_q;
@@ -206,9 +213,9 @@ Route decide_route(tlab_dns *d, const SubstepTail *tail) {
     r.stag = d->stagger;
     r.literal = r.anel || r.stag || dealias;
     r.pfilter = d->pressure_filter_set();
-    r.forces = tail && tail->forces && d->force.any();
+    r.forces = po ? po->forces : tail && tail->forces && d->force.any();
     r.scal_src = tail && tail->scal_sources && d->infrared_on();
-    r.zone_flow = d->buffer_any(0);
+    r.zone_flow = !po && d->buffer_any(0);
     r.zone_scal = tail && tail->scal_zones && ns > 0 && d->buffer_any(1);
 
     auto burgers_ok = [&](int dir, tlab_fdm_plan_t g) {
@@ -260,14 +267,16 @@ struct Ctx {
     double dte, kco, idte;
     int scale;
     double *const *q, *const *s, *const *hq, *const *hs;
+    double *const *vel;           // the advecting velocity of each direction: q, but for the diffusion part of a pressure decomposition (zeros)
     double *tmp1, *tmp2, *tmp3, *tmp4, *tmp5, *tmp7, *tmp8, *tmp9;      // txc(:,1:9) in the reference's roles
     tlab_fdm_plan_t gx, gy, gz;
     std::vector<tlab::ClipBounds> tail_clip;      // the bounds of the tail as the kernels take them
-    Ctx(tlab_dns *d_, double dte_, double *const *q_, double *const *s_, double *const *hq_, double *const *hs_, double *const *txc, const SubstepTail *tail_)
+    Ctx(tlab_dns *d_, double dte_, double *const *q_, double *const *s_, double *const *hq_, double *const *hs_, double *const *txc, const SubstepTail *tail_,
+        bool p_only = false, double *const *vel_ = nullptr)
         : d(d_), tail(tail_), nx(d_->nx), ny(d_->ny), nz(d_->nz), n((long long)d_->nx * d_->ny * d_->nz), st(tlab_current_stream()), dte(dte_),
           kco(tail_ ? tail_->kco : 1.0),
-          idte(d_->remove_divergence ? 1.0 / dte_ : 0.0),      // hq + 0 q is hq bit for bit: the same kernels serve the else-branch (:234-250)
-          scale(tail_ ? tail_->scale : 0), q(q_), s(s_), hq(hq_), hs(hs_), tmp1(txc[0]), tmp2(txc[1]), tmp3(txc[2]), tmp4(txc[3]), tmp5(txc[4]),
+          idte(d_->remove_divergence && !p_only ? 1.0 / dte_ : 0.0),      // hq + 0 q is hq bit for bit: the same kernels serve the else-branch (:234-250)
+          scale(tail_ ? tail_->scale : 0), q(q_), s(s_), hq(hq_), hs(hs_), vel(vel_ ? vel_ : q_), tmp1(txc[0]), tmp2(txc[1]), tmp3(txc[2]), tmp4(txc[3]), tmp5(txc[4]),
           tmp7(txc[6]), tmp8(txc[7]), tmp9(txc[8]), gx(d_->g[0]), gy(d_->g[1]), gz(d_->g[2]) {
         if (tail && tail->bounds)
             for (size_t is = 0; is < tail->bounds->on.size(); ++is) tail_clip.push_back({tail->bounds->lo[is], tail->bounds->hi[is]});
@@ -299,12 +308,12 @@ void keep_surface_planes(const Ctx &c) {
 // hq = hq + tmp_a + tmp_b + tmp_c afterwards; here each kernel adds its result to hq directly (same summation order)
 // when the fused kernels apply, and falls back to tmp + k_add3 per equation otherwise. ----
 struct Eq { double *dst; const double *fld; double nu; int order[3]; };   // order = directions in the reference's summation order
-std::vector<Eq> equations(const Ctx &c) {
+std::vector<Eq> equations(const Ctx &c, bool scalars = true) {
     const double nu = c.d->visc;
     std::vector<Eq> eqs = {{c.hq[0], c.q[0], nu, {1, 2, 3}},      // hq1 + tmp1(X) + tmp7(Y) + tmp8(Z)   (:110)
                            {c.hq[1], c.q[1], nu, {2, 1, 3}},      // hq2 + tmp2(Y) + tmp7(X) + tmp8(Z)   (:122)
                            {c.hq[2], c.q[2], nu, {3, 1, 2}}};     // hq3 + tmp3(Z) + tmp7(X) + tmp8(Y)   (:134)
-    for (int is = 0; is < c.d->nscal; ++is) eqs.push_back({c.hs[is], c.s[is], c.d->visc / c.d->schmidt[is], {1, 2, 3}});   // :158, opr_burgers.f90:97
+    for (int is = 0; is < c.d->nscal && scalars; ++is) eqs.push_back({c.hs[is], c.s[is], c.d->visc / c.d->schmidt[is], {1, 2, 3}});   // :158, opr_burgers.f90:97
     return eqs;
 }
 
@@ -342,7 +351,7 @@ void burgers_batch(const Ctx &c, const Route &r, const std::vector<Eq> &eqs, int
     }
     const bool any_fin = fin[0] || fin[1] || fin[2] || fin[3];
     const bool any_clip = clip[0] || clip[1] || clip[2] || clip[3];
-    if (!tlab_internal_burgers_acc_n(dir, c.d->g[dir - 1], c.nx, c.ny, c.nz, 0, nf, nup, sp, c.q[dir - 1], rp, overwrite, any_fin ? fin : nullptr, c.dte,
+    if (!tlab_internal_burgers_acc_n(dir, c.d->g[dir - 1], c.nx, c.ny, c.nz, 0, nf, nup, sp, c.vel[dir - 1], rp, overwrite, any_fin ? fin : nullptr, c.dte,
                                      c.kco, c.scale ? 1 : 0, divp, c.idte, fresh_mask, r.anel ? c.d->rib : nullptr, any_clip ? clip : nullptr, clo, chi))
         throw Fail(TLAB_EINVAL, "internal: inconsistent fused Burgers path");
 }
@@ -397,7 +406,7 @@ void burgers_per_equation(const Ctx &c, const Route &r, const std::vector<Eq> &e
         int npend = 0;
         for (int k = 0; k < 3; ++k) {
             const int dir = e.order[k];
-            const double *vel = c.q[dir - 1];
+            const double *vel = c.vel[dir - 1];
             if (r.acc_direct && tlab_internal_burgers_acc(dir, d->g[dir - 1], c.nx, c.ny, c.nz, 0, e.nu, e.fld, vel, e.dst)) continue;
             ok(tlab_opr_burgers(dir, d->g[dir - 1], e.fld == vel ? TLAB_OPR_B_SELF : TLAB_OPR_B_U_IN, c.nx, c.ny, c.nz, 0, e.nu, e.fld, vel, tmps[k], c.tmp9, 0),
                "OPR_Burgers");
@@ -410,6 +419,12 @@ void burgers_per_equation(const Ctx &c, const Route &r, const std::vector<Eq> &e
         }
     }
     mid_sequence_terms(c, r);      // (the tendencies were zeroed or accumulated above; the forcing follows)
+}
+
+void burgers_sums(const Ctx &c, const Route &r, const std::vector<Eq> &eqs, bool fresh) {
+    if (r.div_all) burgers_five_launches(c, r, eqs, fresh);
+    else if (r.batched) burgers_three_launches(c, r, eqs, fresh);
+    else burgers_per_equation(c, r, eqs, fresh);
 }
 
 // the tail of the scalars under a buffer zone, once the wall planes of hs hold their BC values: BOUNDARY_BUFFER_RELAX_SCAL, s += dte hs, bounds, hs *= kco
@@ -502,10 +517,10 @@ void pressure_solve(const Ctx &c, const Route &r) {
         hk(launch_scale(d->bcs_ht, d->rb_wall[1], (long long)nx * nz, c.st), "scale");
     }
     if (r.v_final) tlab_internal_poisson_arm_v_final(d->poisson, c.q[1], c.hq[1], c.dte, c.kco, c.scale);
-    ok(tlab_opr_poisson(d->poisson, nx, ny, nz, TLAB_BCS_NN, c.tmp1, c.tmp2, c.tmp4, d->bcs_hb, d->bcs_ht, c.tmp3), "OPR_Poisson");
+    ok(tlab_opr_poisson(d->poisson, nx, ny, nz, TLAB_BCS_NN, c.tmp1, c.tmp2, c.tmp4, d->bcs_hb, d->bcs_ht, r.p_only ? nullptr : c.tmp3), "OPR_Poisson");
     if (r.pfilter) {      // filter pressure p and its vertical gradient dpdy (:286-290)
         ok(tlab_opr_filter(nx, ny, nz, d->pfilter[0], d->pfilter[1], d->pfilter[2], d->pfilter_rep, c.tmp1, c.tmp4), "OPR_FILTER(p)");
-        ok(tlab_opr_filter(nx, ny, nz, d->pfilter[0], d->pfilter[1], d->pfilter[2], d->pfilter_rep, c.tmp3, c.tmp4), "OPR_FILTER(dpdy)");
+        if (!r.p_only) ok(tlab_opr_filter(nx, ny, nz, d->pfilter[0], d->pfilter[1], d->pfilter[2], d->pfilter_rep, c.tmp3, c.tmp4), "OPR_FILTER(dpdy)");
     }
 }
 
@@ -672,9 +687,7 @@ void tlab::rhs_substep(tlab_dns *d, double dte, double *const *q, double *const 
     const Route r = decide_route(d, tail);
     const std::vector<Eq> eqs = equations(c);
 
-    if (r.div_all) burgers_five_launches(c, r, eqs, fresh);
-    else if (r.batched) burgers_three_launches(c, r, eqs, fresh);
-    else burgers_per_equation(c, r, eqs, fresh);
+    burgers_sums(c, r, eqs, fresh);
     if (r.zone_epi) zone_wall_planes(c);
     pressure_forcing(c, r);
     pressure_solve(c, r);
@@ -693,7 +706,89 @@ void tlab::rhs_substep(tlab_dns *d, double dte, double *const *q, double *const 
     else boundary_conditions_rhs_only(c, r);
 }
 
+// ---- FI_PRESSURE_BOUSSINESQ (physics/fi_pressure_boussinesq.f90:8-280): the stages above up to the solve, on three sums that are the caller's
+// work arrays instead of the tendencies.  tmp[0..2] take the place of hq (they count as fresh: the first launch of each overwrites), p that of the
+// forcing array tmp1, the caller's tmp1 | tmp2 that of the solver's work arrays tmp2 | tmp4; idte = 0 (no q / dte in the forcing), no scalar
+// equation, no buffer zone, no tail.  What a route needs beyond that -- the sums of the literal forcing, the interpolation array of the staggered
+// grid, the temporaries of the per-equation Burgers sums -- is the driver's own scratch, allocated on first use and kept.  Nothing of the driver's
+// state is read that a substep consumes (d->fresh) and nothing is written but that scratch and the two wall planes every solve overwrites.
+namespace {
+enum { PW_TMP3, PW_TMP5, PW_TMP7, PW_TMP8, PW_TMP9 };      // the slots of tlab_dns::pwork, by the role of rhs_global_incompressible_1.f90
+double *pressure_work(tlab_dns *d, int slot) {
+    if (!d->pwork[slot]) hk(hipMalloc((void **)&d->pwork[slot], (size_t)(d->nx + 2) * d->ny * d->nz * sizeof(double)), "hipMalloc(pressure scratch)");
+    return d->pwork[slot];
+}
+}  // namespace
+
+void tlab::pressure_boussinesq(tlab_dns *d, int dcmp, double *const *q, double *const *s, double *p, double *tmp1, double *tmp2, double *const *tmp) {
+    follow_anelastic(d);
+    const bool total = dcmp == TLAB_DCMP_TOTAL, burgers = total || dcmp == TLAB_DCMP_ADVDIFF || dcmp == TLAB_DCMP_ADVECTION || dcmp == TLAB_DCMP_DIFFUSION;
+    if (dcmp == TLAB_DCMP_BUOYANCY && d->bback && (d->force.g[0] != 0.0 || d->force.g[2] != 0.0))
+        throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_pressure: DCMP_BUOYANCY with a horizontal gravity component and a non-zero bbackground (the reference "
+                                      "subtracts bbackground for the y component only there, fi_pressure_boussinesq.f90:171-177; the device holds one profile)");
+    const PressureOnly po{total && d->force.any()};
+    Route r = decide_route(d, nullptr, &po);
+    // Only the plain Burgers sums of ONE pass can carry the forcing terms on their launches (the epilogue differentiates the tendency of the field
+    // that is the advecting velocity of the launch): the difference of two passes (advection), the sums under a zero velocity (diffusion) and the
+    // body forces on their own are differentiated afterwards, by the fused forcing launches where they apply
+    if (dcmp != TLAB_DCMP_TOTAL && dcmp != TLAB_DCMP_ADVDIFF) r.div_all = r.div_in_burgers = false;
+    const bool literal_forcing = !(r.div_all || r.div_in_burgers);      // (the fused forcing launches may decline: the literal sums serve then)
+    const bool per_equation = burgers && !(r.div_all || r.batched);
+    double *txc[9] = {p, tmp1, literal_forcing ? pressure_work(d, PW_TMP3) : nullptr, tmp2, r.stag ? pressure_work(d, PW_TMP5) : nullptr, nullptr,
+                      per_equation ? pressure_work(d, PW_TMP7) : nullptr, per_equation ? pressure_work(d, PW_TMP8) : nullptr,
+                      per_equation ? pressure_work(d, PW_TMP9) : nullptr};
+    const Ctx c(d, 1.0, q, s, tmp, nullptr, txc, nullptr, true);
+    const size_t bytes = (size_t)c.n * sizeof(double);
+    if (dcmp == TLAB_DCMP_DIFFUSION || dcmp == TLAB_DCMP_ADVECTION) {
+        // the Burgers launches with an all-zero advecting velocity (tmp9 = 0, :117): into the sums themselves (diffusion), or into tmp[3..5], which
+        // are then taken from the sums of the first pass (advection = advdiff - diffusion, :145-148)
+        hk(hipMemsetAsync(tmp[6], 0, bytes, c.st), "memset");
+        double *const zero[3] = {tmp[6], tmp[6], tmp[6]};
+        if (dcmp == TLAB_DCMP_ADVECTION) burgers_sums(c, r, equations(c, false), true);
+        const Ctx cd(d, 1.0, q, s, dcmp == TLAB_DCMP_ADVECTION ? tmp + 3 : tmp, nullptr, txc, nullptr, true, zero);
+        burgers_sums(cd, r, equations(cd, false), true);
+        if (dcmp == TLAB_DCMP_ADVECTION) hk(launch_sub3(tmp[0], tmp[1], tmp[2], tmp[3], tmp[4], tmp[5], c.n, c.st), "sub3");
+    } else if (burgers) {
+        burgers_sums(c, r, equations(c, false), true);      // (total: the body forces in the mid-sequence slot, r.forces)
+    } else {
+        // Rotation_Coriolis (:158-163) or the buoyancy (:166-196) alone on zeroed sums: one launch of k_body_force with the other term switched off
+        // in a copy of the driver's forces
+        for (int i = 0; i < 3; ++i) hk(hipMemsetAsync(tmp[i], 0, bytes, c.st), "memset");
+        tlab::BodyForce F = d->force;
+        if (dcmp == TLAB_DCMP_CORIOLIS) F.bod = 0;
+        else F.cor = 0;
+        hk(launch_body_force(F, tmp, q, s, d->bprof, c.nx, c.ny, c.nz, c.st), "body force");
+    }
+    pressure_forcing(c, r);
+    pressure_solve(c, r);
+    if (r.stag) {      // back onto the velocity nodes (:272-275)
+        ok(tlab_opr_partial(3, c.gz, TLAB_OPR_P0_INT_PV, c.nx, c.ny, c.nz, B0, p, c.tmp5, nullptr), "OPR_Partial_Z(P0_INT_PV)");
+        ok(tlab_opr_partial(1, c.gx, TLAB_OPR_P0_INT_PV, c.nx, c.ny, c.nz, B0, c.tmp5, p, nullptr), "OPR_Partial_X(P0_INT_PV)");
+    }
+}
+
 extern "C" {
+
+int tlab_dns_pressure(tlab_dns_t d, int decomposition, double *const *q, double *const *s, double *p, double *tmp1, double *tmp2, double *const *tmp,
+                      int ntmp) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {      // (the arguments are checked first: a refusal needs no device)
+        const char *who = "tlab_dns_pressure";
+        const int dc = decomposition;
+        if (dc != TLAB_DCMP_TOTAL && dc != TLAB_DCMP_ADVECTION && dc != TLAB_DCMP_ADVDIFF && dc != TLAB_DCMP_DIFFUSION && dc != TLAB_DCMP_CORIOLIS &&
+            dc != TLAB_DCMP_BUOYANCY)
+            throw Fail(TLAB_EINVAL, std::string(who) + ": decomposition must be DCMP_TOTAL, _ADVECTION, _ADVDIFF, _DIFFUSION, _CORIOLIS or _BUOYANCY");
+        const int need = dc == TLAB_DCMP_ADVECTION || dc == TLAB_DCMP_DIFFUSION ? 7 : 3;
+        if (ntmp < need) throw Fail(TLAB_EINVAL, std::string(who) + ": this decomposition needs " + std::to_string(need) + " work arrays in tmp");
+        if (!d || !q || !p || !tmp1 || !tmp2 || !tmp || (d->nscal > 0 && !s)) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
+        for (int i = 0; i < 3; ++i)
+            if (!q[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null velocity array");
+        for (int i = 0; i < need; ++i)
+            if (!tmp[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null work array");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
+        pressure_boussinesq(d, dc, q, s, p, tmp1, tmp2, tmp);
+    }, TLAB_EINVAL);
+}
 
 int tlab_rhs_global_incompressible_1(tlab_dns_t d, double dte, double *const *q, double *const *s, double *const *hq,
                                      double *const *hs, double *const *txc) {

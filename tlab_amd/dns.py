@@ -106,7 +106,8 @@ CORIOLIS_TYPES = {"none": 0, "explicit": 4, "normalized": 12}
 BUOYANCY_TYPES = {"none": 0, "explicit": 4, "homogeneous": 5, "linear": 6, "bilinear": 7, "quadratic": 8, "normalizedmean": 9, "subtractmean": 10}
 
 
-MIXTURES = {"none": 0, "airwaterlinear": 12}                                   # MIXT_TYPE_* of the reference
+PRESSURE_DECOMPOSITIONS = {"total": 0, "advection": 2, "advdiff": 3, "diffusion": 4, "coriolis": 5, "buoyancy": 6}      # DCMP_* (include/dns_const.h:30-36)
+MIXTURES = {"none": 0, "airwaterlinear": 12}                                  # MIXT_TYPE_* of the reference
 INFRARED_TYPES = {"none": 0, "grayliquid": 1, "bulk1dlocal": 1, "gray": 2, "band": 3}
 PART_TYPES = {"none": 0, "tracer": 1, "inertia": 2, "bilinearcloudthree": 4, "bilinearcloudfour": 5, "tiniaone": 6}      # PART_TYPE_* of the reference
 PART_BCS = {"none": 0, "stick": 1, "specular": 2}
@@ -650,6 +651,48 @@ class Dns:
         tags = ["u", "v", "w"] + (["p"] if p is not None else []) + ["s%d" % (i + 1) for i in range(self.nscal)]
         out = pdf1v_n(self.nx, self.ny, self.nz, fields, nbins, ibc, umin, umax, gate, igate)
         return dict(zip(tags, out))
+
+    def FI_PRESSURE_BOUSSINESQ(self, p=None, decomposition="total"):
+        """physics/fi_pressure_boussinesq.f90:8: the pressure of q (and s, through the body forces) into p, which is returned; default
+        self.txc[2], the array DNS_STATISTICS hands (dns_statistics.f90:93).  self.txc[0], [1] and [3..8] are the work space, as there; advection
+        and diffusion need a seventh sum array, which the driver allocates once.  decomposition: a key of PRESSURE_DECOMPOSITIONS or its code.
+        q, s, hq, hs and the state of the driver are unchanged; the call returns with its launches enqueued."""
+        import torch
+        code = PRESSURE_DECOMPOSITIONS.get(decomposition.strip().lower()) if isinstance(decomposition, str) else int(decomposition)
+        if code is None:
+            raise TlabError("decomposition: one of %s" % ", ".join(PRESSURE_DECOMPOSITIONS))
+        p = self.txc[2] if p is None else p
+        tmp = [t for t in self.txc[3:] if t.data_ptr() != p.data_ptr()]
+        if code in (PRESSURE_DECOMPOSITIONS["advection"], PRESSURE_DECOMPOSITIONS["diffusion"]) and len(tmp) < 7:
+            if getattr(self, "_pressure_tmp", None) is None:
+                self._pressure_tmp = torch.empty(self.isize_txc_field, dtype=torch.float64, device=self.q[0].device)
+            tmp.append(self._pressure_tmp)
+        if p.numel() < self.isize_txc_field:
+            raise TlabError("p must hold isize_txc_field = %d values" % self.isize_txc_field)
+        _use_torch_stream()
+        q, s = self._arrays()[:2]
+        ptmp = (c_vp * len(tmp))(*[t.data_ptr() for t in tmp])
+        check(load().tlab_dns_pressure(self._h, code, q, s, p.data_ptr(), self.txc[0].data_ptr(), self.txc[1].data_ptr(), ptmp, len(tmp)),
+              "tlab_dns_pressure")
+        return p
+
+    def FI_VORTICITY(self, result=None):
+        """mappings/fi_vorticity.f90:28: the squared magnitude of the vorticity of q into result (default self.txc[0], as in DNS_STATISTICS);
+        self.txc[3..8] hold the six derivatives v,x  u,y  u,z  w,x  w,y  v,z on return (self.txc[2], where FI_PRESSURE_BOUSSINESQ leaves the
+        pressure, is not touched).  Returns result."""
+        from .operators import fi_vorticity
+        return fi_vorticity(self, self.q[0], self.q[1], self.q[2], self.txc[0] if result is None else result, self.txc[3:9])
+
+    def intermittency(self):
+        """The block stats_intermittency of DNS_STATISTICS (dns_statistics.f90:99-117): FI_VORTICITY into self.txc[0], MINMAX, the gate
+        txc[0] > (1.0e-3*1.0e-3)*amax -- the reference's arithmetic; its comment says 0.1 %, its code 1e-6 -- and INTER_N_XZ with one level.
+        {"Vorticity": numpy (ny,)}, the area fraction of the gate in every plane.  No file is written."""
+        from .operators import gate_threshold, inter_n_xz
+        vort = self.FI_VORTICITY()
+        mn, mx = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(load().tlab_minmax(self._h, vort.data_ptr(), self.nx, self.ny, self.nz, ctypes.byref(mn), ctypes.byref(mx)), "tlab_minmax")
+        gate = gate_threshold(vort[: self.n], (1.0e-3 * 1.0e-3) * mx.value)
+        return {"Vorticity": inter_n_xz(self.nx, self.ny, self.nz, 1, gate)[0]}
 
     def profile_derivative(self, profiles):
         """OPR_Partial_Y(OPR_P1, 1, jmax, 1, bcs, g(2), ..) of profiles (numpy (n, ny)) with the driver's y plan: numpy (n, ny).  The line

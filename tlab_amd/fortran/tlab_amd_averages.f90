@@ -16,6 +16,11 @@
 !   TLab_AMD_Avg_Gradients_Scal             avg_scal_xz.f90:451-453, :607, :714-745 on dsdx, dsdy, dsdz: out(jmax, 15 or 18)
 !                                           With USE_MPI every pass is followed by the reference's MPI_ALLREDUCE (averages.f90:320-324), so that the
 !                                           means a later pass subtracts are the global ones, as the reference's AVG_IK_V returns them.
+!   TLab_AMD_FI_Vorticity, TLab_AMD_Inter_N_XZ  the block stats_intermittency of DNS_STATISTICS (dns_statistics.f90:99-117): FI_VORTICITY
+!                                           (mappings/fi_vorticity.f90:28-59) on the driver's plans with one pass over the six derivatives, and the
+!                                           calculation of INTER_N_XZ (statistics/avg_xz.f90:109-153) for all planes and levels in one pass over
+!                                           the gate.  With USE_MPI the avg/real(npro) and MPI_ALLREDUCE of INTER1V2D (averages.f90:233-236) follow;
+!                                           like every USE_MPI branch of this module, that one is NOT compiled by this project's build or tests.
 ! The arrays are classified by the library (tlab_pointer_on_device): host arrays take a host loop in the reference's order, so the routines serve
 ! either kind; a mix is refused.  The profiles are host memory.  The moment routines give the LOCAL averages: a decomposed host reduces them as it
 ! does the profiles of AVG_IK_V.  What the reference adds on the host afterwards (Ty1, Txyy, Tyyy, Tyzy) stays with the caller.
@@ -30,6 +35,7 @@ module TLab_AMD_Averages
     private
     public :: TLab_AMD_AVG_IK_V, TLab_AMD_AVG1V2D_V, TLab_AMD_Avg_Moments_Flow, TLab_AMD_Avg_Moments_Scal
     public :: TLab_AMD_Avg_Gradients_Flow, TLab_AMD_Avg_UGradP, TLab_AMD_Avg_Gradients_Scal
+    public :: TLab_AMD_FI_Vorticity, TLab_AMD_Inter_N_XZ
 
 contains
     subroutine TLab_AMD_AVG_IK_V(nx, ny, nz, a, avg, wrk)
@@ -170,6 +176,32 @@ contains
                                                     c_loc(fV), c_loc(fW), pm, c_loc(rS_y), py, c_loc(out), ny), 'tlab_avg_gradients_scal')
 #endif
     end subroutine TLab_AMD_Avg_Gradients_Scal
+
+    ! FI_VORTICITY(nx, ny, nz, u, v, w, result, tmp1, tmp2) with six work arrays in place of two: txc6(i) = c_loc(txc(1, .)) hold v,x u,y u,z w,x w,y
+    ! v,z on return.  dns: the driver's handle (TLab_AMD_DNS_Handle()), whose plans are g(1:3).  Device arrays.
+    subroutine TLab_AMD_FI_Vorticity(dns, nx, ny, nz, u, v, w, result, txc6)
+        type(c_ptr), intent(in) :: dns, txc6(6)
+        integer, intent(in) :: nx, ny, nz
+        real(c_double), intent(in), target :: u(nx*ny*nz), v(nx*ny*nz), w(nx*ny*nz)
+        real(c_double), intent(out), target :: result(nx*ny*nz)
+
+        call TLab_AMD_Check(tlab_fi_vorticity(dns, c_loc(u), c_loc(v), c_loc(w), c_loc(result), txc6), 'tlab_fi_vorticity')
+    end subroutine TLab_AMD_FI_Vorticity
+
+    ! The calculation of INTER_N_XZ: the reference's argument list minus fname, itime, rtime, parname and y -- the file is written by the host, from
+    ! inter, as before (avg_xz.f90:144-150).  wrk(ny, np) is used with USE_MPI only, where INTER1V2D's avg/real(npro) and MPI_ALLREDUCE follow.
+    subroutine TLab_AMD_Inter_N_XZ(nx, ny, nz, np, gate, inter, wrk)
+        integer, intent(in) :: nx, ny, nz, np
+        integer(1), intent(in), target :: gate(*)
+        real(c_double), intent(out) :: inter(ny, np)
+        real(c_double), intent(inout) :: wrk(ny, np)
+
+        call TLab_AMD_Check(tlab_inter_n_xz(nx, ny, nz, np, c_loc(gate), inter), 'tlab_inter_n_xz')
+#ifdef USE_MPI
+        wrk = inter/real(ims_npro_i*ims_npro_k, c_double)
+        call MPI_ALLREDUCE(wrk, inter, ny*np, MPI_REAL8, MPI_SUM, MPI_COMM_WORLD, ims_err)
+#endif
+    end subroutine TLab_AMD_Inter_N_XZ
 
 #ifdef USE_MPI
     ! the reduction of AVG_IK_V (averages.f90:320-324) on nc columns of local averages

@@ -342,6 +342,13 @@ module TLab_AMD_C
             type(c_ptr), value :: dns
             type(c_ptr), intent(in) :: q(*), s(*), hq(*)      ! host arrays of device pointers
         end function
+        ! FI_PRESSURE_BOUSSINESQ (tlab_amd_pressure.f90): p, tmp1, tmp2 and the ntmp arrays of tmp hold isize_txc_field values each
+        integer(c_int) function tlab_dns_pressure(dns, decomposition, q, s, p, tmp1, tmp2, tmp, ntmp) bind(C, name='tlab_dns_pressure')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, p, tmp1, tmp2
+            integer(c_int), value :: decomposition, ntmp
+            type(c_ptr), intent(in) :: q(3), s(*), tmp(*)
+        end function
         integer(c_int) function tlab_deferred_sources_flow(dns, q, s, hq) bind(C, name='tlab_deferred_sources_flow')
             import :: c_int, c_ptr
             type(c_ptr), value :: dns
@@ -666,6 +673,19 @@ module TLab_AMD_C
             type(c_ptr), value :: a, gate
             integer(c_long_long), value :: n
             real(c_double), value :: thr
+        end function
+        ! intermittency (tlab_amd_averages.f90): FI_VORTICITY on the driver's plans, txc6(6) the addresses of six work arrays; INTER_N_XZ of a gate
+        ! of either kind, inter(ny, np) in host memory
+        integer(c_int) function tlab_fi_vorticity(dns, u, v, w, result, txc6) bind(C, name='tlab_fi_vorticity')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, u, v, w, result
+            type(c_ptr), intent(in) :: txc6(6)
+        end function
+        integer(c_int) function tlab_inter_n_xz(nx, ny, nz, np, gate, inter) bind(C, name='tlab_inter_n_xz')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, np
+            type(c_ptr), value :: gate
+            real(c_double), intent(out) :: inter(*)
         end function
         integer(c_int) function tlab_boundary_bcs_neumann_y(plan, ibc, nx, ny, nz, u, bcs_hb, bcs_ht, tmp1) bind(C, name='tlab_boundary_bcs_neumann_y')
             import :: c_int, c_ptr

@@ -556,3 +556,44 @@ def gate_threshold(a, thr, gate=None):
     _stream_if_device([a])
     check(load().tlab_gate_threshold(_field_ptr(a, n, "a", keep), n, float(thr), _gate_ptr(gate, n, keep)), "tlab_gate_threshold")
     return gate
+
+
+# ---- intermittency: FI_VORTICITY and INTER_N_XZ, the block stats_intermittency of DNS_STATISTICS (dns_statistics.f90:99-117) -------------------
+def fi_vorticity(dns, u, v, w, result, txc6):
+    """FI_VORTICITY (mappings/fi_vorticity.f90:28) with the plans of the driver dns: result = (v,x - u,y)^2 + (u,z - w,x)^2 + (w,y - v,z)^2.
+    txc6: six work tensors, which hold v,x  u,y  u,z  w,x  w,y  v,z on return.  Returns result."""
+    txc6 = list(txc6)
+    if len(txc6) != 6:
+        raise TlabError("txc6 must hold six work arrays")
+    ptrs = (c_vp * 6)(*[_ptr(t, dns.n, "txc6[%d]" % i).value for i, t in enumerate(txc6)])
+    _use_torch_stream()
+    check(load().tlab_fi_vorticity(dns._h, _ptr(u, dns.n, "u"), _ptr(v, dns.n, "v"), _ptr(w, dns.n, "w"), _ptr(result, dns.n, "result"), ptrs),
+          "tlab_fi_vorticity")
+    return result
+
+
+def vorticity_from_gradients(vx, uy, uz, wx, wy, vz, result=None):
+    """The pointwise pass of FI_VORTICITY on its own: ((vx - uy)^2 + (uz - wx)^2) + (wy - vz)^2, of the kind of its arguments (torch tensors or
+    numpy arrays)."""
+    keep, fields = [], [vx, uy, uz, wx, wy, vz]
+    if isinstance(vx, np.ndarray):
+        n = vx.size
+        result = np.empty(n) if result is None else result
+    else:
+        import torch
+        n = vx.numel()
+        result = torch.empty_like(vx) if result is None else result
+    _stream_if_device(fields)
+    check(load().tlab_vorticity_from_gradients(n, *[_field_ptr(f, n, "field %d" % i, keep) for i, f in enumerate(fields)],
+                                               _field_ptr(result, n, "result", keep)), "tlab_vorticity_from_gradients")
+    return result
+
+
+def inter_n_xz(nx, ny, nz, np_, gate):
+    """The calculation of INTER_N_XZ (statistics/avg_xz.f90:109): the area fraction of the levels 1 .. np_ of an int8 gate in every plane, numpy
+    (np_, ny) -- row ip - 1 is column ip of the reference's inter(ny, np).  gate: a torch tensor or a numpy array."""
+    keep = []
+    out = np.zeros((max(int(np_), 1), ny))
+    _stream_if_device([gate])
+    check(load().tlab_inter_n_xz(nx, ny, nz, int(np_), _gate_ptr(gate, nx * ny * nz, keep), c_vp(out.ctypes.data)), "tlab_inter_n_xz")
+    return out
