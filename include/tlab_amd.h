@@ -162,7 +162,8 @@ int tlab_filter_destroy(tlab_filter_t f);
  * PENTADPSS, FLT_E6, FLT_E4 (src/filters/flt_compact.f90, flt_explitic.f90) -- one line per thread, the reference's operation order. */
 int tlab_opr_filter_1d(int dir, tlab_filter_t f, int nx, int ny, int nz, const double *u, double *result);
 /* OPR_FILTER(nx, ny, nz, f, u, txc) (opr_filter.f90:283-392), directional branch: the x, y, z filters in that order (NULL = none), each repeat[d]
- * times (NULL = once), in place; tmp: one field of scratch. */
+ * times (NULL = once), in place; tmp: one field of scratch.  A filter whose size is not the extent along its direction and a Repeat < 1 are
+ * refused (TLAB_EINVAL) before anything is launched: u is as it was. */
 int tlab_opr_filter(int nx, int ny, int nz, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat, double *u, double *tmp);
 /* [Dealiasing] Dealiasing(dir) of OPR_Burgers (physics/opr_burgers.f90:33, 71, 118-125): while a filter is set for a direction, tlab_opr_burgers
  * along it computes nu d2s - filter(u) filter(ds/dx) (:478-500), unfused; NULL: none.  The filter is not owned. */

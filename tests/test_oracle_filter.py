@@ -1,6 +1,6 @@
 """The oracle's restatement of the 1-D filters behind [Dealiasing] (oracle/tlab_oracle_filter.py) against vectors the reference's own filter
-modules produced (tests/golden/filters.npz): bitwise, for compact / explicit6 / explicit4 / compactcutoff, periodic and biased / free / zero ends;
-and the dealiasing branch of the Burgers oracle against its definition."""
+modules produced (tests/golden/filters.npz; filter_boxes.npz at the line lengths 8, 37 and 130): bitwise, for compact / explicit6 / explicit4 /
+compactcutoff, periodic and biased / free / zero ends; and the dealiasing branch of the Burgers oracle against its definition."""
 import os
 import re
 import numpy as np
@@ -9,12 +9,19 @@ import pytest
 from oracle import tlab_oracle as O
 from oracle import tlab_oracle_filter as F
 
-G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "filters.npz"))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+G = np.load(os.path.join(GOLDEN, "filters.npz"))
+GB = np.load(os.path.join(GOLDEN, "filter_boxes.npz"))         # the same cases at n = 8, 37, 130 (make_golden_filter_boxes.py)
+
+
+def fixture_of(key):
+    """the fixture that holds a case: the line lengths of the two do not overlap"""
+    return G if key + "_res" in G.files else GB
 
 
 def filter_of(key):
     n, t, per, b0, b1 = (int(v) for v in re.match(r"n(\d+)_t(\d+)_p(\d)_b(\d)(\d)", key).groups())
-    c = G[key + "_coeffs"]
+    c = fixture_of(key)[key + "_coeffs"]
     return F.Filter(t, n, bool(per), c if c.shape[1] else None, b0, b1), n
 
 
@@ -22,6 +29,17 @@ def filter_of(key):
 def test_filters_match_the_reference_bitwise(key):
     f, n = filter_of(key)
     assert np.array_equal(F.opr_filter_1d(f, G["n%d_u" % n]), G[key + "_res"])
+
+
+@pytest.mark.parametrize("key", [str(k) for k in GB["cases"]])
+def test_filters_match_the_reference_bitwise_at_box_lengths(key):
+    """n = 8 (interior loops of one to three rows, overlapping end stencils), 37 and 130: after this the numpy oracle is reference-made at every
+    length the device tests use, and serves as their expected value on whole boxes (tests/test_gpu_filter_boxes.py)"""
+    f, n = filter_of(key)
+    assert n in (8, 37, 130) and fixture_of(key) is GB
+    got = F.opr_filter_1d(f, GB["n%d_u" % n])
+    assert got.shape == (n, 6) and np.isfinite(got).all()
+    assert np.array_equal(got, GB[key + "_res"])
 
 
 def test_dealiased_burgers_is_the_filtered_product():

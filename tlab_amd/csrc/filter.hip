@@ -264,10 +264,15 @@ int tlab_opr_filter(int nx, int ny, int nz, tlab_filter_t fx, tlab_filter_t fy, 
         tlab_filter_t f[3] = {fx, fy, fz};
         hipStream_t st = tlab_current_stream();
         const size_t bytes = (size_t)nx * ny * nz * sizeof(double);
+        const int ext[3] = {nx, ny, nz};
+        for (int d = 0; d < 3; ++d) {      // every refusal before the first launch: u is in place, a call that fails must leave it as it was
+            if (!f[d]) continue;
+            if (f[d]->n != ext[d]) throw std::invalid_argument("tlab_opr_filter: filter size does not match the field size along its direction");
+            if (repeat && repeat[d] < 1) throw std::invalid_argument("tlab_opr_filter: Filter.Repeat must be positive (opr_filter.f90:198-204)");
+        }
         for (int d = 0; d < 3; ++d) {
             if (!f[d]) continue;
             const int rep = repeat ? repeat[d] : 1;
-            if (rep < 1) throw std::invalid_argument("tlab_opr_filter: Filter.Repeat must be positive (opr_filter.f90:198-204)");
             for (int r = 0; r < rep; ++r) {
                 tlab_internal_filter_1d(d + 1, f[d], nx, ny, nz, u, tmp, st);
                 if (hipMemcpyAsync(u, tmp, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) throw std::runtime_error("hipMemcpyAsync");

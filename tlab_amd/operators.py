@@ -244,6 +244,16 @@ def OPR_FILTER_1D(idir, f, nx, ny, nz, u, result):
     check(load().tlab_opr_filter_1d(int(idir), f._h, nx, ny, nz, _ptr(u), _ptr(result)), "tlab_opr_filter_1d")
 
 
+def OPR_FILTER(nx, ny, nz, fx, fy, fz, u, tmp, repeat=None):
+    """OPR_FILTER (opr_filter.f90:283-392), directional branch: the x, then the y, then the z Filter (None = DNS_FILTER_NONE), each repeat[d]
+    times (None: once), on u in place; tmp: scratch of the same size."""
+    _use_torch_stream()
+    n = int(nx) * int(ny) * int(nz)
+    rp = None if repeat is None else (ctypes.c_int * 3)(*(int(r) for r in repeat))
+    h = [f._h if f is not None else None for f in (fx, fy, fz)]
+    check(load().tlab_opr_filter(nx, ny, nz, h[0], h[1], h[2], rp, _ptr(u, n, "u"), _ptr(tmp, n, "tmp")), "tlab_opr_filter")
+
+
 def set_dealiasing(idir, f):
     """Dealiasing(idir) of OPR_Burgers ([Dealiasing], opr_burgers.f90:33, 71): a Filter, or None for DNS_FILTER_NONE.  Module state of the
     operator, as in the reference; the caller keeps the Filter alive while it is set."""
