@@ -1042,6 +1042,67 @@ int tlab_pw_get_wall_planes(const double *f, double *hb, double *ht, int nx, int
 int tlab_pw_fill_wall_planes(double *f, double vb, double vt, int nx, int ny, int nz);
 int tlab_pw_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz);      /* NULL plane = zeros */
 
+/* ---- sampling between two statistics steps: phase averages, towers, saved planes --------------------------------------------------------------
+ * What dns_main.f90 does to q, s and the pressure of a substep between two restart files beside the statistics: AvgPhaseSpace / AvgPhaseStress
+ * (statistics/avg_phase.f90), DNS_TOWER_ACCUMULATE (tools/dns/dns_tower.f90) and PLANES_SAVE (tools/dns/planes.f90).  No IO: the files stay with
+ * the host.  The state that is just arrays is the caller's (avg_flow, avg_stress, tower_buf, data_i / data_j / data_k), so the entry points are
+ * stateless but for the tower plan.  Arrays are classified like tlab_avg_ik_v: all in device memory -> the kernels of csrc/sampling.hip; all in host
+ * memory (or no tlab_init) -> a host loop that is the reference's statement; a mix: TLAB_EINVAL.  A recorded substep runs first.  No call
+ * synchronises the stream: a device accumulator is complete once the stream is (tlab_sync, or a copy on the same stream).
+ *
+ * tlab_avg_phase_space: AvgPhaseSpaceExec (:123-202) for index 1, 2 or 4 on nf fields (a HOST array of nf pointers; nx*ny*nz doubles each).  avg holds
+ *   nx*ny*(avg_planes + 1)*nf doubles in the reference's layout: plane plane_id (1-based) of field f takes localsum = sum over k in increasing k of
+ *   field(:,:,k)/g(3)%size, nz_total = g(3)%size (the local part: a z-decomposed host reduces the planes itself), and the last plane, the running
+ *   mean, gains that plane / avg_planes.  Every term is a true fp64 division, one point's sum stays in one thread: bit for bit the reference's sum.
+ *   TLAB_EINVAL: avg_planes < 1 or plane_id outside 1..avg_planes (the reference divides by zero or writes out of bounds there); avg is untouched.
+ * tlab_avg_phase_flow: AvgPhaseSpace(index 1) and AvgPhaseStress (:204-287) in ONE pass over u, v, w: avg_flow (3 fields) and avg_stress (6) in the
+ *   same layout, each product rounded before its division.  Stress ids as the calls give them (:230-235): uu 1, uv 2, uw 3, vv 4, vw 5, ww 6.
+ * tlab_avg_phase_plane_id: the arithmetic of :142-143, plane_id = mod((itr - 1) - it_first, it_save) + 1 with Fortran's sign of mod, 1 for it_save = 0;
+ *   the value is the result (no error code). */
+int tlab_avg_phase_space(int nx, int ny, int nz, int nz_total, int nf, const double *const *fields, int avg_planes, int plane_id, double *avg);
+int tlab_avg_phase_flow(int nx, int ny, int nz, int nz_total, const double *u, const double *v, const double *w, int avg_planes, int plane_id,
+                        double *avg_flow, double *avg_stress);
+int tlab_avg_phase_plane_id(int itr, int it_first, int it_save);
+/* The towers: tlab_tower_create is DNS_TOWER_INITIALIZE (:62-203) on one rank -- stride: int[3] ([SaveTowers] Stride), nitera_save the number of
+ *   time steps the buffer holds -- and keeps tower_ipos, tower_jpos, tower_kpos, tower_accumulation and tower_mode_check.  TLAB_EINVAL where (n - 1)
+ *   is a multiple of a stride > 1 in some direction: the reference counts one tower less than it places and writes past tower_ipos.
+ * tlab_tower_sizes: long long[8] = tower_imax, tower_jmax, tower_kmax, tower_isize_acc_field, tower_isize_acc_mean, tower_bufsize,
+ *   tower_accumulation, tower_mode_check.  tlab_tower_positions: tower_ipos (dir 1), tower_jpos (2) or tower_kpos (3), 1-based.
+ * tlab_tower_accumulate: DNS_TOWER_ACCUMULATE (:207-289) into the caller's tower_buf (tower_bufsize doubles, the reference's layout: u, v, w, p, s,
+ *   then the five plane means, then t and it; the host's DNS_TOWER_WRITE works on a copy unchanged).  index 1: fields = u, v, w; 2: the first scalar;
+ *   4: the pressure (fields: a HOST array of 3 | 1 pointers), which also stores rtime and itime.  The values are v(tower_ipos(ii), tower_jpos(j),
+ *   tower_kpos(kk)), j fastest -- the reference's 1:tower_jmax:tower_jstride conforms for stride_y = 1 only, where the two agree.  The means
+ *   (TOWER_AVG_IK_V, :502-546) are the sums of k_plane_partial / k_plane_final on the device, the reference's loop on the host, divided by
+ *   real(imax*kmax).  tower_accumulation advances when the indices of a step sum to 7.  TLAB_EINVAL, state and buffer untouched: an index that
+ *   takes tower_mode_check past 7, a full buffer (tower_accumulation > nitera_save).
+ * tlab_tower_reset: tower_accumulation = 1 (the end of DNS_TOWER_WRITE) and tower_mode_check = 0. */
+typedef struct tlab_tower *tlab_tower_t;
+int tlab_tower_create(tlab_tower_t *out, int nx, int ny, int nz, const int *stride, int nitera_save);
+int tlab_tower_destroy(tlab_tower_t t);
+int tlab_tower_sizes(tlab_tower_t t, long long *sizes);
+int tlab_tower_positions(tlab_tower_t t, int dir, int *pos);
+int tlab_tower_accumulate(tlab_tower_t t, int index, const double *const *fields, int itime, double rtime, double *tower_buf);
+int tlab_tower_reset(tlab_tower_t t);
+/* tlab_planes_gather: the copies of PLANES_SAVE (:279-342) for one direction in one launch.  dir 1: out = data_i(ny, nvars*n, nz) (transposed, j
+ *   fastest), 2: data_j(nx, nvars*n, nz), 3: data_k(nx, ny, nvars*n); slot v*n + m holds plane nodes[m] of field v.  nodes: HOST, 1-based, checked as
+ *   PLANES_INITIALIZE checks them (TLAB_EINVAL outside 1..the size in that direction); at most 16 fields and 20 planes (vars(16), MAX_SAVEPLANES).
+ *   single != 0: out is float, rounded to nearest (IO_TYPE_SINGLE on write); else double.
+ * tlab_fi_gradient: FI_GRADIENT (mappings/fi_gradient.f90:26-48), result = (s,x*s,x + s,y*s,y) + s,z*s,z in the reference's order, the derivatives by
+ *   the driver's plans with bcs = 0; tmp: nx*ny*nz doubles of work space.  Device arrays.  No IBM.
+ * tlab_log10_small: a = log10(a + small_wp), small_wp = 1e-20 (planes.f90:250, :256), arrays of either kind. */
+int tlab_planes_gather(int nx, int ny, int nz, int nvars, const double *const *fields, int dir, int n, const int *nodes, void *out, int single);
+int tlab_fi_gradient(tlab_dns_t d, const double *s, double *result, double *tmp);
+int tlab_log10_small(long long n, double *a);
+/* tlab_dns_arm_pressure_sampling: one-shot, like tlab_dns_begin_step.  The next tlab_rhs_global_incompressible_1 or
+ *   tlab_time_substep_incompressible_explicit of d takes its samples between the pressure solve and the pressure gradient
+ *   (rhs_global_incompressible_1.f90:292-305): tlab_tower_accumulate(tower, 4, p, itime, rtime, tower_buf) and / or tlab_avg_phase_space of p into
+ *   phase_avg (nx*ny*(avg_planes + 1) doubles) at plane_id.  Either target may be NULL (both: nothing is armed); the accumulators are DEVICE memory.
+ *   On the staggered grid p is interpolated back through OPR_P0_INT_PV in z then x into tmp4 (tmp4 and tmp5 are free there, :294-297); elsewhere the
+ *   pressure tmp1 is sampled (the reference hands the solver's work array tmp4 over).  The arm is cleared when taken, also when
+ *   that call fails; tlab_dns_pressure (the route that stops at the pressure) refuses an armed driver with TLAB_EUNSUPPORTED and clears it. */
+int tlab_dns_arm_pressure_sampling(tlab_dns_t d, tlab_tower_t tower, double *tower_buf, int itime, double rtime, double *phase_avg, int avg_planes,
+                                   int plane_id);
+
 /* TLab_Transpose(a, nra, nca, ma, b, mb)   utils/tlab_transpose.f90:14-82 : b(j,i) = a(i,j), bit-exact */
 int tlab_transpose(const double *a, int nra, int nca, double *b);
 

@@ -16,4 +16,5 @@ from .operators import (  # noqa: F401
     avg_ik_v, avg1v2d_v, avg_moments_flow, avg_moments_scal, avg_gradients_flow, avg_ugradp, avg_gradients_scal,
     pdf1v_n, pdf_minmax_planes, pdf_histogram_planes, pdf_analize, pdf2v, gate_threshold,
     fi_vorticity, vorticity_from_gradients, inter_n_xz,
+    avg_phase_space, avg_phase_flow, avg_phase_plane_id, Tower, planes_gather, fi_gradient, log10_small,
 )

@@ -122,7 +122,7 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 int plane_moments_chunks(int nz) { return (nz + AVG_ROWS_PER_GROUP - 1) / AVG_ROWS_PER_GROUP; }
 
 hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, const double *const *f, const double *means, double *partial,
-                                double *prof, hipStream_t st) {
+                                double *prof, hipStream_t st, double denom) {
     const AvgInfo info = avg_info(prog, param);
     if (nx < 1 || ny < 1 || nz < 1 || info.nfld < 1 || info.nfld > AVG_MAX_FIELDS || !f || !partial || !prof || (info.nmean > 0 && !means))
         return hipErrorInvalidValue;
@@ -147,7 +147,7 @@ hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, con
     if (!known) return hipErrorInvalidValue;
     const long long nt = (long long)ny * info.nout;
     hipLaunchKernelGGL(k_plane_final, dim3((unsigned)((nt + AVG_THREADS - 1) / AVG_THREADS)), dim3(AVG_THREADS), 0, st, partial, nchunks, ny, info.nout,
-                       (double)((long long)nx * nz), prof);
+                       denom != 0.0 ? denom : (double)((long long)nx * nz), prof);
     return hipGetLastError();
 }
 

@@ -62,6 +62,15 @@ struct tlab_dns {
     struct Infrared { int type = TLAB_IR_NONE, scalar = 0; double kappa = 0.0, flux_top = 0.0, flux_bottom = 0.0; double *tab = nullptr; tlab::InfraredCoef C{}; } ir;
     // [Particles] (tlab_dns_set_particles): made and read by particles.hip, null without particles; no launch of the flow substep depends on it
     tlab::ParticleState *particles = nullptr;
+    // tlab_dns_arm_pressure_sampling: one-shot, taken by the next substep between the pressure solve and the pressure gradient (the towers' and the
+    // phase averages' tap of rhs_global_incompressible_1.f90:292-305).  Nothing is owned: the tower plan and the accumulators are the caller's.
+    struct PressureSampling {
+        bool armed = false;
+        tlab_tower_t tower = nullptr;
+        double *tower_buf = nullptr, *phase_avg = nullptr;
+        int itime = 0, avg_planes = 0, plane_id = 0;
+        double rtime = 0.0;
+    } psample;
     int scal_arrays() const { return nscal + (mixture != TLAB_MIXT_NONE ? 1 : 0); }
     TLAB_HIDDEN bool pressure_filter_set() const { return pfilter[0] || pfilter[1] || pfilter[2]; }
     TLAB_HIDDEN bool surface(int is) const { return !sfc_jmin.empty() && (sfc_jmin[is] == 1 || sfc_jmax[is] == 1); }      // scalar is has a surface model at one end
@@ -112,6 +121,10 @@ TLAB_HIDDEN void rhs_substep(tlab_dns *d, double dte, double *const *q, double *
 // with p as the forcing array; dcmp: a checked TLAB_DCMP_*.  No driver state changes but the scratch d->pwork and the solver's two wall planes.
 TLAB_HIDDEN void pressure_boussinesq(tlab_dns *d, int dcmp, double *const *q, double *const *s, double *p, double *tmp1, double *tmp2,
                                      double *const *tmp);
+
+// ---- sampling.cpp ----
+// the samples of an armed substep: DNS_TOWER_ACCUMULATE(p, 4) and / or AvgPhaseSpace of p, p the pressure on the velocity nodes (device memory)
+TLAB_HIDDEN void pressure_sampling(tlab_dns *d, const tlab_dns::PressureSampling &ps, const double *p);
 
 // ---- dns_setup.cpp: the launches the substep shares with the entry points tlab_dns_buffer_relax_* / _sources_* / _diagnostic ----
 // RELAX_BLOCK of the blocks of one group (0: BOUNDARY_BUFFER_RELAX_FLOW on q, hq; 1: BOUNDARY_BUFFER_RELAX_SCAL on s, hs), Jmin before Jmax, four fields a launch

@@ -228,8 +228,29 @@ hipError_t launch_infrared_y(const double *l, double *hs, double *scr1, double *
 // fields, imom, or 1 with a pressure field); f: its fields; means: device, [nmean][ny] (NULL for a program without means); partial: device scratch,
 // plane_moments_chunks(nz) * ny * nout doubles; prof: device, [nout][ny], the result.  Nothing is copied or synchronised here.
 int plane_moments_chunks(int nz);
+// denom: what k_plane_final divides the sums by; 0: real(nx*nz, wp) (the towers divide by a default real, dns_tower.f90:535)
 hipError_t launch_plane_moments(int prog, int param, int nx, int ny, int nz, const double *const *f, const double *means, double *partial,
-                                double *prof, hipStream_t st);
+                                double *prof, hipStream_t st, double denom = 0.0);
+
+// sampling.hip: phase averages, towers, saved planes (k_phase_space, k_tower_gather, k_tower_means, k_planes_gather) and the pointwise passes of
+// PLANES_LOG.  Nothing is copied or synchronised here.
+//   launch_phase_space  nf = 1..3 fields of nxy * nz doubles; stress (nf = 3 only): the six products too; out, last: nf (+ 6) planes of nxy doubles
+//                       each, the plane of this sample (overwritten) and the running mean (last += out / avg_planes)
+//   launch_tower_gather dst[f][(kk * ti + ii) * tj + j] = f[f](ipos[ii], jpos[j], kpos[kk]); ipos, jpos, kpos: device, 1-based; t_slot, it_slot
+//                       (both or neither): take rtime and itime
+//   launch_tower_means  dst[f][j] = prof[f * ny + jpos[j] - 1]
+//   launch_planes_gather  dir 1: out(ny, nvars * n, nz), 2: out(nx, nvars * n, nz), 3: out(nx, ny, nvars * n), slot v * n + m = plane nodes[m]
+//                       (HOST array, 1-based, checked) of field v; single: out is float
+constexpr int PLANES_MAX_VARS = 16, PLANES_MAX_NODES = 20;      // vars(16) of PLANES_SAVE, MAX_SAVEPLANES (planes.f90:22, :224)
+hipError_t launch_phase_space(int nf, bool stress, const double *const *f, double *const *out, double *const *last, long long nxy, int nz, int nz_total,
+                              int avg_planes, hipStream_t st);
+hipError_t launch_tower_gather(int nf, const double *const *f, double *const *dst, const int *ipos, const int *jpos, const int *kpos, int ti, int tj, int tk,
+                               int nx, int ny, double *t_slot, double *it_slot, double rtime, int itime, hipStream_t st);
+hipError_t launch_tower_means(const double *prof, int ny, const int *jpos, int tj, int nf, double *const *dst, hipStream_t st);
+hipError_t launch_planes_gather(int nx, int ny, int nz, int nvars, const double *const *f, int dir, int n, const int *nodes, void *out, bool single,
+                                hipStream_t st);
+hipError_t launch_gradient_magnitude(double *r, const double *t, bool second, long long n, hipStream_t st);      // r = r*r + t*t | r = r + t*t
+hipError_t launch_log10_small(double *a, long long n, hipStream_t st);                                            // a = log10(a + small_wp)
 
 // pdfs.hip: plane PDFs (k_pdf_minmax, k_pdf_hist and their final kernels; pdfs_host.hpp holds the bin of a point).  F: at most PDF_FIELDS_PER_LAUNCH
 // fields of one box and the gate (igate != 0: only points with gate == igate take part).  Nothing is copied or synchronised here.

@@ -524,6 +524,19 @@ void pressure_solve(const Ctx &c, const Route &r) {
     }
 }
 
+// the taps of the towers and the phase averages (:292-305), armed by tlab_dns_arm_pressure_sampling: the pressure in tmp1, on the staggered grid its
+// image on the velocity nodes in tmp4 through tmp5 (both free between the solve and the gradient, :294-297).  Where the grid is not staggered the
+// reference hands over tmp4, the solver's work array; the pressure is sampled here.
+void pressure_taps(const Ctx &c, const Route &r, const tlab_dns::PressureSampling &ps) {
+    const double *p = c.tmp1;
+    if (r.stag) {
+        ok(tlab_opr_partial(3, c.gz, TLAB_OPR_P0_INT_PV, c.nx, c.ny, c.nz, B0, c.tmp1, c.tmp5, nullptr), "OPR_Partial_Z(P0_INT_PV)");
+        ok(tlab_opr_partial(1, c.gx, TLAB_OPR_P0_INT_PV, c.nx, c.ny, c.nz, B0, c.tmp5, c.tmp4, nullptr), "OPR_Partial_X(P0_INT_PV)");
+        p = c.tmp4;
+    }
+    pressure_sampling(c.d, ps, p);
+}
+
 // six planes of scratch for the weighted sums next to the walls, allocated on first use
 double *wall_planes(const Ctx &c) {
     if (!c.d->wall_planes) hk(hipMalloc((void **)&c.d->wall_planes, 6 * c.plane_bytes()), "hipMalloc");
@@ -679,6 +692,8 @@ void boundary_conditions_rhs_only(const Ctx &c, const Route &r) {
 
 void tlab::rhs_substep(tlab_dns *d, double dte, double *const *q, double *const *s, double *const *hq, double *const *hs, double *const *txc,
                        const SubstepTail *tail) {
+    const tlab_dns::PressureSampling taps = d->psample;      // one-shot: cleared when taken, so an error below clears it too
+    d->psample = tlab_dns::PressureSampling();
     const Ctx c(d, dte, q, s, hq, hs, txc, tail);
     follow_anelastic(d);
     keep_surface_planes(c);
@@ -691,6 +706,7 @@ void tlab::rhs_substep(tlab_dns *d, double dte, double *const *q, double *const 
     if (r.zone_epi) zone_wall_planes(c);
     pressure_forcing(c, r);
     pressure_solve(c, r);
+    if (taps.armed) pressure_taps(c, r, taps);
     if (r.scal_neumann_planes && !r.neu_fast) throw Fail(TLAB_EINVAL, "internal: Neumann scalars were finished without their wall planes");
     if (r.neu_fast) {
         neumann_fast_tail(c, r);
@@ -721,6 +737,10 @@ double *pressure_work(tlab_dns *d, int slot) {
 }  // namespace
 
 void tlab::pressure_boussinesq(tlab_dns *d, int dcmp, double *const *q, double *const *s, double *p, double *tmp1, double *tmp2, double *const *tmp) {
+    if (d->psample.armed) {      // the route that stops at the pressure has no tap: the arm is for a substep
+        d->psample = tlab_dns::PressureSampling();
+        throw Fail(TLAB_EUNSUPPORTED, "tlab_dns_pressure: a pressure sampling is armed (tlab_dns_arm_pressure_sampling serves the substep and the RHS)");
+    }
     follow_anelastic(d);
     const bool total = dcmp == TLAB_DCMP_TOTAL, burgers = total || dcmp == TLAB_DCMP_ADVDIFF || dcmp == TLAB_DCMP_ADVECTION || dcmp == TLAB_DCMP_DIFFUSION;
     if (dcmp == TLAB_DCMP_BUOYANCY && d->bback && (d->force.g[0] != 0.0 || d->force.g[2] != 0.0))

@@ -846,14 +846,110 @@ class Dns:
         return {"ms_first": rep[0], "ms_best": rep[1], "ms_median": rep[2], "ms_worst": rep[3], "trials": int(rep[4]), "pool": pool,
                 "seconds": time.perf_counter() - t0}
 
-    def TIME_RUNGEKUTTA(self, dtime):
+    # ---- sampling between two statistics steps: towers (dns_main.f90:300-303), phase averages (:282-298), saved planes (planes.f90) ----
+    def set_towers(self, stride, nitera_save):
+        """[SaveTowers] Stride: DNS_TOWER_INITIALIZE (tools/dns/dns_tower.f90:62).  The buffer (device, the reference's layout) holds nitera_save
+        time steps; the host writes it (DNS_TOWER_WRITE on a copy) and calls tower_reset."""
+        import torch
+        from .operators import Tower
+        if self.nscal < 1:
+            raise TlabError("the towers take the first scalar (DNS_TOWER_ACCUMULATE(s, 2)): nscal must be at least 1")
+        self.tower = Tower(self.nx, self.ny, self.nz, stride, nitera_save)
+        self.tower_buf = torch.zeros(self.tower.bufsize, dtype=torch.float64, device=self.q[0].device)
+
+    def tower_accumulate(self, itime=0, rtime=0.0):
+        """DNS_TOWER_ACCUMULATE(q, 1) and (s, 2) after a time step (dns_main.f90:300-303); the pressure (index 4) was taken inside the last substep
+        (TIME_RUNGEKUTTA with itime).  No synchronisation."""
+        self.tower.accumulate(1, self.q, itime, rtime, self.tower_buf)
+        self.tower.accumulate(2, self.s[:1], itime, rtime, self.tower_buf)
+
+    def tower_buffer(self):
+        """tower_buf (device) -- Tower.views names its parts"""
+        return self.tower_buf
+
+    def tower_reset(self):
+        self.tower.reset()
+
+    def set_phase_average(self, stride, nitera_first, nitera_save):
+        """[Iteration] PhaseAvg: AvgPhaseInitializeMemory (statistics/avg_phase.f90:54-98) -- avg_planes = nitera_save / stride, and avg_flow, avg_scal,
+        avg_p, avg_stress zeroed on the device, (fields, avg_planes + 1, ny, nx)"""
+        import torch
+        self.phase = {"stride": int(stride), "first": int(nitera_first), "save": int(nitera_save), "planes": int(nitera_save) // int(stride)}
+        if self.phase["planes"] < 1:
+            raise TlabError("nitera_save / stride must be at least 1")
+        shape = (self.phase["planes"] + 1, self.ny, self.nx)
+        z = lambda nf: torch.zeros((nf,) + shape, dtype=torch.float64, device=self.q[0].device)      # noqa: E731
+        self.avg_flow, self.avg_scal, self.avg_p, self.avg_stress = z(3), z(max(self.nscal, 1)), z(1), z(6)
+
+    def _phase_plane(self, itr):
+        from .operators import avg_phase_plane_id
+        return avg_phase_plane_id(itr, self.phase["first"], self.phase["save"] // self.phase["stride"])
+
+    def phase_average(self, itime):
+        """dns_main.f90:282-288 after time step itime: if mod(itime, stride) == 0, AvgPhaseSpace of q and s and AvgPhaseStress (u, v, w read once).
+        True when the step was sampled.  The files and AvgPhaseResetVariable (phase_reset) stay with the caller."""
+        from .operators import avg_phase_flow, avg_phase_space
+        ph = self.phase
+        if itime % ph["stride"] != 0:
+            return False
+        pid = self._phase_plane(itime // ph["stride"])
+        avg_phase_flow(self.nx, self.ny, self.nz, self.q[0], self.q[1], self.q[2], ph["planes"], pid, self.avg_flow, self.avg_stress)
+        if self.nscal:
+            avg_phase_space(self.nx, self.ny, self.nz, self.s, ph["planes"], pid, self.avg_scal)
+        return True
+
+    def phase_buffers(self):
+        return {"flow": self.avg_flow, "scal": self.avg_scal, "p": self.avg_p, "stress": self.avg_stress}
+
+    def phase_reset(self):
+        """AvgPhaseResetVariable (statistics/avg_phase.f90:453-470)"""
+        for a in (self.avg_flow, self.avg_scal, self.avg_p, self.avg_stress):
+            a.zero_()
+
+    def _arm_pressure_sampling(self, itime, rtime):
+        """rhs_global_incompressible_1.f90:292-305 for the last substep of step itime: the towers take the pressure at itime, the phase average
+        at (itime + 1) / stride when mod(itime + 1, stride) == 0"""
+        tower = getattr(self, "tower", None)
+        ph = getattr(self, "phase", None)
+        due = ph is not None and (itime + 1) % ph["stride"] == 0
+        if tower is None and not due:
+            return
+        _use_torch_stream()
+        check(load().tlab_dns_arm_pressure_sampling(
+            self._h, tower._h if tower is not None else None, self.tower_buf.data_ptr() if tower is not None else None, int(itime),
+            float(0.0 if rtime is None else rtime), self.avg_p.data_ptr() if due else None, ph["planes"] if due else 0,
+            self._phase_plane((itime + 1) // ph["stride"]) if due else 0), "tlab_dns_arm_pressure_sampling")
+
+    def PLANES_SAVE(self, iplanes=(), jplanes=(), kplanes=(), log=False, single=True):
+        """PLANES_SAVE (tools/dns/planes.f90:213) without its files: (data_i, data_j, data_k) as device tensors (nz, size, ny), (nz, size, nx), (size,
+        ny, nx), None for an empty list of nodes (1-based).  The variables run [u, v, w, scalars..., p, log10 enstrophy, log10 grad s...] (the last
+        group with log, PLANES_LOG); p from FI_PRESSURE_BOUSSINESQ, the enstrophy from FI_VORTICITY.  single: float32 (IO_TYPE_SINGLE).  self.txc is
+        the work space."""
+        from .operators import fi_gradient, log10_small, planes_gather
+        n = self.n
+        p = self.FI_PRESSURE_BOUSSINESQ()                                  # self.txc[2]
+        fields = self.q + self.s + [p[:n]]
+        if log:
+            if self.nscal > 5:
+                raise TlabError("PLANES_SAVE(log=True) has work arrays for five scalars")
+            fields.append(log10_small(self.FI_VORTICITY()[:n]))            # self.txc[0]; self.txc[3..8] are free again
+            for i in range(self.nscal):
+                fields.append(log10_small(fi_gradient(self, self.s[i], self.txc[3 + i], self.txc[8])[:n]))
+        gather = lambda idir, nodes: planes_gather(self.nx, self.ny, self.nz, fields, idir, nodes, single=single) if len(nodes) else None      # noqa: E731
+        return gather(1, iplanes), gather(2, jplanes), gather(3, kplanes)
+
+    def TIME_RUNGEKUTTA(self, dtime, itime=None, rtime=None):
         """One time step: hq = hs = 0 (and l_hq = 0), then rkm_endstep substeps, each with the particle substep first when particles are set
-        (time.f90:212-304)."""
+        (time.f90:212-304).  itime (the iteration before the step, as TLab_Time holds it inside TIME_RUNGEKUTTA) and rtime: with towers or a phase
+        average set, the last substep samples its pressure (rkm_substep == rkm_endstep, rhs_global_incompressible_1.f90:292-305).  Without itime
+        nothing is sampled."""
         self.begin_step()
         for k in range(self.rkm_endstep):
             last = k == self.rkm_endstep - 1
             if self.l_q is not None:
                 self.TIME_SUBSTEP_PARTICLE(dtime * self.kdt[k], 1.0 if last else self.kco[k], not last)
+            if last and itime is not None:
+                self._arm_pressure_sampling(itime, rtime)
             self.TIME_SUBSTEP_INCOMPRESSIBLE_EXPLICIT(dtime * self.kdt[k], 1.0 if last else self.kco[k], not last)
 
     def __del__(self):

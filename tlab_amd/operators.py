@@ -607,3 +607,131 @@ def inter_n_xz(nx, ny, nz, np_, gate):
     _stream_if_device([gate])
     check(load().tlab_inter_n_xz(nx, ny, nz, int(np_), _gate_ptr(gate, nx * ny * nz, keep), c_vp(out.ctypes.data)), "tlab_inter_n_xz")
     return out
+
+
+# ---- sampling between two statistics steps: phase averages (statistics/avg_phase.f90), towers (tools/dns/dns_tower.f90), saved planes
+# (tools/dns/planes.f90).  The accumulators are the caller's arrays, of the kind of the fields (torch tensors or numpy arrays); no call synchronises.
+def avg_phase_plane_id(itr, it_first, it_save):
+    """plane_id of AvgPhaseSpaceExec (statistics/avg_phase.f90:142-143): mod((itr - 1) - it_first, it_save) + 1 with Fortran's mod; 1 for it_save = 0"""
+    return int(load().tlab_avg_phase_plane_id(int(itr), int(it_first), int(it_save)))
+
+
+def avg_phase_space(nx, ny, nz, fields, avg_planes, plane_id, avg, nz_total=None):
+    """AvgPhaseSpace for index 1, 2 or 4 (statistics/avg_phase.f90:123): the z-average of every field into plane plane_id (1-based) of avg, laid out
+    (len(fields), avg_planes + 1, ny, nx), and avg[:, -1] += that plane / avg_planes.  nz_total: g(3)%size (default nz).  Returns avg."""
+    keep, fields = [], list(fields)
+    ptrs = (c_vp * max(len(fields), 1))(*[_field_ptr(f, nx * ny * nz, "field %d" % i, keep).value for i, f in enumerate(fields)])
+    _stream_if_device(fields + [avg])
+    check(load().tlab_avg_phase_space(nx, ny, nz, nz if nz_total is None else int(nz_total), len(fields), ptrs, int(avg_planes), int(plane_id),
+                                      _field_ptr(avg, nx * ny * (int(avg_planes) + 1) * len(fields), "avg", keep)), "tlab_avg_phase_space")
+    return avg
+
+
+def avg_phase_flow(nx, ny, nz, u, v, w, avg_planes, plane_id, avg_flow, avg_stress, nz_total=None):
+    """AvgPhaseSpace(index 1) and AvgPhaseStress (:204) in one pass over u, v, w: avg_flow (3, avg_planes + 1, ny, nx) and avg_stress (6, ...), the
+    stresses in the order uu, uv, uw, vv, vw, ww."""
+    keep, n, m = [], nx * ny * nz, nx * ny * (int(avg_planes) + 1)
+    _stream_if_device([u, v, w, avg_flow, avg_stress])
+    check(load().tlab_avg_phase_flow(nx, ny, nz, nz if nz_total is None else int(nz_total), _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep),
+                                     _field_ptr(w, n, "w", keep), int(avg_planes), int(plane_id), _field_ptr(avg_flow, 3 * m, "avg_flow", keep),
+                                     _field_ptr(avg_stress, 6 * m, "avg_stress", keep)), "tlab_avg_phase_flow")
+    return avg_flow, avg_stress
+
+
+class Tower:
+    """Module DNS_TOWER (tools/dns/dns_tower.f90) without its files: where the towers stand ([SaveTowers] Stride) and which slot of the caller's
+    buffer the next call fills.  The buffer has the reference's layout, so the host's DNS_TOWER_WRITE works on a copy of it."""
+
+    def __init__(self, nx, ny, nz, stride, nitera_save):
+        self._h = c_vp()
+        self.nx, self.ny, self.nz, self.nitera_save = int(nx), int(ny), int(nz), int(nitera_save)
+        st = (ctypes.c_int * 3)(*[int(s) for s in stride])
+        check(load().tlab_tower_create(ctypes.byref(self._h), self.nx, self.ny, self.nz, st, self.nitera_save), "tlab_tower_create")
+        s = self.sizes()
+        self.imax, self.jmax, self.kmax, self.isize_acc_field, self.isize_acc_mean, self.bufsize = s[:6]
+        self.ipos, self.jpos, self.kpos = (self._positions(d, n) for d, n in ((1, self.imax), (2, self.jmax), (3, self.kmax)))
+
+    def sizes(self):
+        out = (ctypes.c_longlong * 8)()
+        check(load().tlab_tower_sizes(self._h, out), "tlab_tower_sizes")
+        return [int(x) for x in out]
+
+    def _positions(self, idir, n):
+        out = (ctypes.c_int * max(n, 1))()
+        check(load().tlab_tower_positions(self._h, idir, out), "tlab_tower_positions")
+        return np.array(out[:n], dtype=np.int64)
+
+    accumulation = property(lambda self: self.sizes()[6])      # tower_accumulation
+    mode_check = property(lambda self: self.sizes()[7])        # tower_mode_check
+
+    def accumulate(self, index, fields, itime, rtime, buf):
+        """DNS_TOWER_ACCUMULATE(v, index): index 1 = (u, v, w), 2 = (the first scalar,), 4 = (the pressure,)"""
+        keep, fields = [], list(fields)
+        ptrs = (c_vp * max(len(fields), 1))(*[_field_ptr(f, self.nx * self.ny * self.nz, "field %d" % i, keep).value for i, f in enumerate(fields)])
+        if len(fields) != (3 if index == 1 else 1):
+            raise TlabError("index %d takes %d fields" % (index, 3 if index == 1 else 1))
+        _stream_if_device(fields + [buf])
+        check(load().tlab_tower_accumulate(self._h, int(index), ptrs, int(itime), float(rtime), _field_ptr(buf, self.bufsize, "tower_buf", keep)),
+              "tlab_tower_accumulate")
+
+    def reset(self):
+        check(load().tlab_tower_reset(self._h), "tlab_tower_reset")
+
+    def views(self, buf):
+        """the buffer by name, as DNS_TOWER_INITIALIZE points into it (:188-200): u, v, w, p, s (nitera_save, kmax, imax, jmax); um .. sm
+        (nitera_save, jmax); t, it (nitera_save,)"""
+        out, at = {}, 0
+        for name in ("u", "v", "w", "p", "s"):
+            out[name] = buf[at:at + self.isize_acc_field].reshape(self.nitera_save, self.kmax, self.imax, self.jmax)
+            at += self.isize_acc_field
+        for name in ("um", "vm", "wm", "pm", "sm"):
+            out[name] = buf[at:at + self.isize_acc_mean].reshape(self.nitera_save, self.jmax)
+            at += self.isize_acc_mean
+        for name in ("t", "it"):
+            out[name] = buf[at:at + self.nitera_save]
+            at += self.nitera_save
+        return out
+
+    def __del__(self):
+        try:
+            if self._h:
+                load().tlab_tower_destroy(self._h)
+                self._h = c_vp()
+        except Exception:       # noqa: BLE001
+            pass
+
+
+def planes_gather(nx, ny, nz, fields, idir, nodes, single=False, out=None):
+    """The copies of PLANES_SAVE (tools/dns/planes.f90:279-342) for one direction: idir 1 -> data_i as (nz, nvars * n, ny), 2 -> data_j (nz, nvars * n,
+    nx), 3 -> data_k (nvars * n, ny, nx); slot v * n + m = plane nodes[m] (1-based) of field v.  single: float32, rounded to nearest."""
+    keep, fields, nodes = [], list(fields), [int(m) for m in nodes]
+    size = len(fields) * len(nodes)
+    shape = {1: (nz, size, ny), 2: (nz, size, nx), 3: (size, ny, nx)}.get(int(idir), (0,))
+    ptrs = (c_vp * max(len(fields), 1))(*[_field_ptr(f, nx * ny * nz, "field %d" % i, keep).value for i, f in enumerate(fields)])
+    if out is None:
+        if fields and not isinstance(fields[0], np.ndarray):
+            import torch
+            out = torch.zeros(shape, dtype=torch.float32 if single else torch.float64, device=fields[0].device)
+        else:
+            out = np.zeros(shape, dtype=np.float32 if single else np.float64)
+    _stream_if_device(fields + [out])
+    optr = c_vp(out.ctypes.data) if isinstance(out, np.ndarray) else c_vp(out.data_ptr())
+    check(load().tlab_planes_gather(nx, ny, nz, len(fields), ptrs, int(idir), len(nodes), (ctypes.c_int * max(len(nodes), 1))(*nodes), optr,
+                                    1 if single else 0), "tlab_planes_gather")
+    return out
+
+
+def fi_gradient(dns, s, result, tmp):
+    """FI_GRADIENT (mappings/fi_gradient.f90:26) with the plans of the driver dns: result = (s,x^2 + s,y^2) + s,z^2.  Returns result."""
+    _use_torch_stream()
+    check(load().tlab_fi_gradient(dns._h, _ptr(s, dns.n, "s"), _ptr(result, dns.n, "result"), _ptr(tmp, dns.n, "tmp")), "tlab_fi_gradient")
+    return result
+
+
+def log10_small(a):
+    """a = log10(a + small_wp) in place (planes.f90:250), a torch tensor or a numpy array.  Returns a."""
+    keep = []
+    n = a.size if isinstance(a, np.ndarray) else a.numel()
+    _stream_if_device([a])
+    check(load().tlab_log10_small(n, _field_ptr(a, n, "a", keep)), "tlab_log10_small")
+    return a
