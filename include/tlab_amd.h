@@ -165,6 +165,13 @@ int tlab_opr_filter_1d(int dir, tlab_filter_t f, int nx, int ny, int nz, const d
  * times (NULL = once), in place; tmp: one field of scratch.  A filter whose size is not the extent along its direction and a Repeat < 1 are
  * refused (TLAB_EINVAL) before anything is launched: u is as it was. */
 int tlab_opr_filter(int nx, int ny, int nz, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat, double *u, double *tmp);
+/* The same branch of OPR_FILTER on nf device fields u[0..nf-1] (HOST array of device pointers) at once, in place and without a tmp: the streaming
+ * kernels of csrc/filter_stream.hip.  A line stays with one thread and keeps the reference's operation order, so every word equals
+ * tlab_opr_filter's; it is swept as often as its recursion forces -- once for the explicit types, twice for compact (the right-hand side is formed
+ * inside the forward sweep from a register window, TRIDPSS's wrk sum with it), twice for compactcutoff, three times for its periodic form -- and
+ * x lines are staged through LDS instead of a transposed scratch.  The same refusals as tlab_opr_filter (size mismatch, Repeat < 1, null
+ * pointers), before anything is launched: the fields are as they were. */
+int tlab_opr_filter_fields(int nx, int ny, int nz, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat, int nf, double *const *u);
 /* [Dealiasing] Dealiasing(dir) of OPR_Burgers (physics/opr_burgers.f90:33, 71, 118-125): while a filter is set for a direction, tlab_opr_burgers
  * along it computes nu d2s - filter(u) filter(ds/dx) (:478-500), unfused; NULL: none.  The filter is not owned. */
 int tlab_opr_burgers_set_dealiasing(int dir, tlab_filter_t f);
@@ -653,6 +660,17 @@ int tlab_dns_set_bcs(tlab_dns_t d, const int *flow_jmin, const int *flow_jmax, c
 /* [PressureFilter] of dns.ini: p and dp/dy pass OPR_FILTER after the Poisson solve (rhs_global_incompressible_1.f90:286-290; examples/Case92-93:
  * compact filter in y with zero ends).  Filters not owned; NULL = none. */
 int tlab_dns_set_pressure_filter(tlab_dns_t d, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat);
+/* [Filter] of dns.ini: FilterDomain(1:3) of DNS_FILTER (operators/opr_filter.f90:45, tools/dns/dns_filter.f90).  Filters not owned; NULL = none in
+ * that direction, all NULL switches the filter off; repeat may be NULL (once each).  A filter whose size is not the extent along its direction and
+ * a Repeat < 1 are refused (TLAB_EINVAL) and leave the driver as it was.  The types are those of tlab_filter_create: tophat and the 3-D types
+ * (Helmholtz, band, erf) have no handle (TLAB_EUNSUPPORTED there). */
+int tlab_dns_set_filter(tlab_dns_t d, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat);
+/* DNS_FILTER (tools/dns/dns_filter.f90) of the incompressible / anelastic equations, what dns_main.f90 calls every nitera_filter steps after
+ * TIME_RUNGEKUTTA, without its kin statistics: OPR_FILTER(FilterDomain) on u, v, w and the nscal prognostic scalars (tlab_opr_filter_fields), then
+ * DNS_BOUNDS_LIMIT on the scalars with active bounds (tlab_dns_set_scalar_bounds), then FI_DIAGNOSTIC where a mixture is set (s then holds
+ * nscal + 1 arrays, tlab_dns_diagnostic).  Without a filter the last two still act, as in the reference.  q, s: HOST arrays of device pointers.
+ * No tendency and no other state of the driver is touched. */
+int tlab_dns_filter(tlab_dns_t d, double *const *q, double *const *s);
 /* remove_divergence of dns.ini (tools/dns/dns_read_local.f90): on (default): the pressure forcing is div(hq + q/dte), which removes the residual
  * divergence of q (rhs_global_incompressible_1.f90:177-232); off: div(hq) (:234-250). */
 int tlab_dns_set_remove_divergence(tlab_dns_t d, int on);

@@ -11,7 +11,7 @@ from .operators import (  # noqa: F401
     BCS_DD, BCS_ND, BCS_DN, BCS_NN,
     FDM_COM4_JACOBIAN, FDM_COM6_JACOBIAN_PENTA, FDM_COM6_JACOBIAN, FDM_COM6_JACOBIAN_HYPER, FDM_COM6_DIRECT, FDM_COM4_DIRECT,
     OPR_Partial_X, OPR_Partial_Y, OPR_Partial_Z,
-    OPR_Burgers_X, OPR_Burgers_Y, OPR_Burgers_Z, Filter, OPR_FILTER_1D, OPR_FILTER, set_dealiasing,
+    OPR_Burgers_X, OPR_Burgers_Y, OPR_Burgers_Z, Filter, OPR_FILTER_1D, OPR_FILTER, OPR_FILTER_FIELDS, set_dealiasing,
     TLab_Transpose, PoissonPlan, OPR_Poisson, OPR_Helmholtz, poisson_set_exact, BOUNDARY_BCS_NEUMANN_Y,
     avg_ik_v, avg1v2d_v, avg_moments_flow, avg_moments_scal, avg_gradients_flow, avg_ugradp, avg_gradients_scal,
     pdf1v_n, pdf_minmax_planes, pdf_histogram_planes, pdf_analize, pdf2v, gate_threshold,

@@ -221,6 +221,36 @@ int tlab_dns_set_pressure_filter(tlab_dns_t d, tlab_filter_t fx, tlab_filter_t f
     return TLAB_OK;
 }
 
+// [Filter] (operators/opr_filter.f90:45, FilterDomain; tools/dns/dns_filter.f90): the directional filters of DNS_FILTER.  Not owned.  What
+// tlab_dns_filter would refuse is refused here, so that a driver never holds a filter it cannot apply.
+int tlab_dns_set_filter(tlab_dns_t d, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!d) throw Fail(TLAB_EINVAL, "tlab_dns_set_filter: null handle");
+        const tlab_filter_t f[3] = {fx, fy, fz};
+        tlab_internal_filter_fields(d->nx, d->ny, d->nz, f, repeat, 0, nullptr, tlab_current_stream(), "tlab_dns_set_filter");      // (no field: the checks alone)
+        for (int i = 0; i < 3; ++i) { d->dfilter[i] = f[i]; d->dfilter_rep[i] = repeat ? repeat[i] : 1; }
+    }, TLAB_EINVAL);
+}
+
+// DNS_FILTER (tools/dns/dns_filter.f90:69-104) without its kin statistics: OPR_FILTER on q and the prognostic scalars, DNS_BOUNDS_LIMIT, FI_DIAGNOSTIC
+int tlab_dns_filter(tlab_dns_t d, double *const *q, double *const *s) {
+    (void)tlab_internal_deferred_flush();
+    return guarded([&] {
+        if (!d || !q || (d->scal_arrays() > 0 && !s)) throw Fail(TLAB_EINVAL, "tlab_dns_filter: bad arguments");
+        std::vector<double *> u(q, q + 3);
+        u.insert(u.end(), s, s + d->nscal);
+        for (int is = 0; is < d->scal_arrays(); ++is)
+            if (!s[is]) throw Fail(TLAB_EINVAL, "tlab_dns_filter: null array (with a mixture s holds nscal + 1 arrays, the last the liquid)");
+        hipStream_t st = tlab_current_stream();
+        tlab_internal_filter_fields(d->nx, d->ny, d->nz, d->dfilter, d->dfilter_rep, (int)u.size(), u.data(), st, "tlab_dns_filter");
+        const long long n = (long long)d->nx * d->ny * d->nz;
+        for (int is = 0; is < d->nscal; ++is)
+            if (d->bounds.active(is)) hk(launch_clip(s[is], d->bounds.lo[is], d->bounds.hi[is], n, st), "clip");
+        diagnostic(d, s, st);
+    });
+}
+
 int tlab_dns_set_remove_divergence(tlab_dns_t d, int on) {
     (void)tlab_internal_deferred_flush();
     if (!d) return TLAB_EINVAL;

@@ -22,6 +22,8 @@ struct tlab_dns {
     bool fuse = true;                              // fold the pointwise sums into the operator kernels where the fast kernels apply
     tlab_filter_t pfilter[3] = {nullptr, nullptr, nullptr};      // PressureFilter(1:3) (not owned) and its repeat counts
     int pfilter_rep[3] = {1, 1, 1};
+    tlab_filter_t dfilter[3] = {nullptr, nullptr, nullptr};      // FilterDomain(1:3) of DNS_FILTER (not owned) and its repeat counts (tlab_dns_set_filter)
+    int dfilter_rep[3] = {1, 1, 1};
     bool stagger = false;                          // [Staggering] StaggerHorizontalPressure: taken from the x / z plans at creation (tlab_fdm_plan_set_stagger)
     bool remove_divergence = true;                 // [Main] ... forcing = div(hq + q/dte) (rhs_global_incompressible_1.f90:177-232); false: div(hq) (:234-250)
     bool fresh = false;                            // one-shot: hq, hs count as zero on entry of the next substep (tlab_dns_begin_step)

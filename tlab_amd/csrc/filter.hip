@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/tlab_amd.h"
+#include "filter_state.hpp"      // struct tlab_filter
 #include "internal.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -20,12 +21,6 @@
 
 
 using namespace tlab;
-
-struct tlab_filter {
-    int type, n, periodic, bcsmin, bcsmax, ncols;
-    DeviceArray coeffs;      // [ncols][n], column-major like f%coeffs
-    DeviceArray ws;          // two transposed copies of a field: x lines are filtered with the lines made the fastest index (tlab_internal_filter_1d)
-};
 
 namespace {
 

@@ -68,6 +68,12 @@ int tlab_internal_deferred_take_error();      // tlab_sync
 // ---- filter.hip ----
 void tlab_internal_filter_1d(int dir, tlab_filter_t f, int nx, int ny, int nz, const double *u, double *result, hipStream_t st);
 
+// ---- filter_stream.hip ----
+// OPR_FILTER's directional branch on nf device fields in place (x, y, z in that order, each repeat[d] times; repeat NULL: once) with the streaming
+// kernels.  Every refusal (tlab::Fail: size mismatch, Repeat < 1, null field) comes before the first launch.
+void tlab_internal_filter_fields(int nx, int ny, int nz, tlab_filter_t const *f, const int *repeat, int nf, double *const *u, hipStream_t st,
+                                 const char *who);
+
 // ---- poisson.hip ----
 bool tlab_internal_poisson_has_own_x(tlab_poisson_plan_t P);
 // hooks of the RHS driver (rhs.cpp)

@@ -232,6 +232,21 @@ class Dns:
         h = [f._h if f is not None else None for f in (fx, fy, fz)]
         check(load().tlab_dns_set_pressure_filter(self._h, h[0], h[1], h[2], rp), "tlab_dns_set_pressure_filter")
 
+    def set_filter(self, fx=None, fy=None, fz=None, repeat=None):
+        """[Filter] (FilterDomain of DNS_FILTER): tlab_amd.Filter objects per direction (None = no filter, all None switches it off), each applied
+        repeat[d] times; the caller keeps them alive.  A filter whose size is not the extent along its direction is refused and changes nothing."""
+        rp = None if repeat is None else (ctypes.c_int * 3)(*(int(r) for r in repeat))
+        h = [f._h if f is not None else None for f in (fx, fy, fz)]
+        check(load().tlab_dns_set_filter(self._h, h[0], h[1], h[2], rp), "tlab_dns_set_filter")
+        self._dfilters = (fx, fy, fz)
+
+    def DNS_FILTER(self):
+        """DNS_FILTER (tools/dns/dns_filter.f90) without its kin statistics, what dns_main.f90 calls every nitera_filter steps after TIME_RUNGEKUTTA:
+        the filters of set_filter on u, v, w and the scalars in place, then the scalar bounds, then the diagnostic liquid of a mixture."""
+        _use_torch_stream()
+        q, s = self._arrays()[:2]
+        check(load().tlab_dns_filter(self._h, q, s), "tlab_dns_filter")
+
     def set_remove_divergence(self, on):
         """dns.ini remove_divergence (default on): forcing = div(hq + q/dte); off: div(hq)."""
         check(load().tlab_dns_set_remove_divergence(self._h, int(bool(on))), "tlab_dns_set_remove_divergence")

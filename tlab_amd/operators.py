@@ -254,6 +254,18 @@ def OPR_FILTER(nx, ny, nz, fx, fy, fz, u, tmp, repeat=None):
     check(load().tlab_opr_filter(nx, ny, nz, h[0], h[1], h[2], rp, _ptr(u, n, "u"), _ptr(tmp, n, "tmp")), "tlab_opr_filter")
 
 
+def OPR_FILTER_FIELDS(nx, ny, nz, fx, fy, fz, fields, repeat=None):
+    """OPR_FILTER's directional branch on every tensor of `fields` at once, in place and without a tmp (tlab_opr_filter_fields: the streaming
+    kernels).  Every word of a result equals OPR_FILTER's on the same field."""
+    _use_torch_stream()
+    n = int(nx) * int(ny) * int(nz)
+    fields = list(fields)
+    rp = None if repeat is None else (ctypes.c_int * 3)(*(int(r) for r in repeat))
+    h = [f._h if f is not None else None for f in (fx, fy, fz)]
+    u = (c_vp * max(len(fields), 1))(*(_ptr(t, n, "field %d" % i) for i, t in enumerate(fields)))
+    check(load().tlab_opr_filter_fields(nx, ny, nz, h[0], h[1], h[2], rp, len(fields), u), "tlab_opr_filter_fields")
+
+
 def set_dealiasing(idir, f):
     """Dealiasing(idir) of OPR_Burgers ([Dealiasing], opr_burgers.f90:33, 71): a Filter, or None for DNS_FILTER_NONE.  Module state of the
     operator, as in the reference; the caller keeps the Filter alive while it is set."""
