@@ -860,6 +860,51 @@ int tlab_dns_avg_gradients_scal(tlab_dns_t d, const double *s, double *const *q,
  *   is exact and so is the reference's sum of 1.0, so the result is the reference's bit for bit.  The call synchronises the stream.
  *   TLAB_EINVAL: nx, ny or nz < 1, np outside 1 .. 127, a null pointer. */
 int tlab_inter_n_xz(int nx, int ny, int nz, int np, const signed char *gate, double *inter);
+
+/* ---- spectra and correlations in horizontal planes: tools/statistics/spectra.f90 with module SpectraMod (spectra_pool.f90), opt_main 1-4 -------
+ * Power and co-spectra E(kx), E(kz), E(kr), E(kx, kz) and auto- and cross-correlations C(rx), C(rz), C(r), C(rx, rz) of a pair of fields per block
+ * of nblock y-planes (the uppermost ny mod nblock planes are dropped).  A transformed field is complex (nx/2+1, ny, nz), kx fastest, in the NATURAL
+ * kz order of tlab_poisson_fft_x + tlab_poisson_fft_z; the reference's kz shuffle (fft_reordering_k, opr_fourier.f90:357-370) is an index map here,
+ * and every 2-D output keeps the reference's shuffled order.  Arrays of a call are all device memory (kernels of csrc/spectra.hip: no atomics, the
+ * same bits on every run) or all host memory (the reference's loops, in their order); a mix: TLAB_EINVAL.  Profiles -- variance, var1, var2,
+ * variance2, cov, mean: ny doubles per column -- are HOST memory, as in the plane statistics above; a call that returns one synchronises the stream.
+ * outx, outz, outr and out2d are ACCUMULATED into (+=, as the reference: a caller can average over times); out2d may be NULL.
+ * TLAB_EINVAL: odd nx, nblock < 1 or > ny, kr_total < 1, a null pointer.  TLAB_EUNSUPPORTED: nz = 1, a slab or pencil plan.  Not built: the phase
+ * half of REDUCE_SPECTRUM's out, 3-D spectra, masks, MPI.
+ * tlab_spectrum_reduce: what spectra.f90:641-650 does to the product of OPR_Fourier_CONVOLUTION_FXZ, from a_hat and b_hat (NULL: an auto pair) in
+ *   one read: P = Re(b_hat conj(a_hat)), (P*norm)*norm with norm = 1/(nx*nz); REDUCE_SPECTRUM (:232-274) and INTEGRATE_SPECTRUM (:73-185) into
+ *   outx (nx/2, ny/nblock), outz (nz/2, ny/nblock), outr (kr_total, ny/nblock), out2d (nx/2, ny/nblock, nz); variance (ny) is the Parseval control
+ *   of REDUCE_SPECTRUM, Nyquist column included, 0 for the dropped planes.
+ * tlab_correlation_reduce: spectra.f90:653 and REDUCE_CORRELATION (:313-358) on the real field in (nx, ny, nz) the inverse transforms return:
+ *   ((in*norm)*norm) / (sqrt(var1(j)) sqrt(var2(j))) (1 where that product is not positive) summed over the block into outx (nx, ny/nblock; the row
+ *   rz = 0), outz (nz, ny/nblock; the column rx = 0), out2d (nx, ny/nblock, nz) and, with icalc_radial = 1, outr (nr_total, ny/nblock);
+ *   variance2(j) = (in(1, j, 1)*norm)*norm.
+ * tlab_radial_samplesize: RADIAL_SAMPLESIZE (:381-398) counted from zero.  Host arithmetic.
+ * tlab_cross_product: c = b_hat conj(a_hat) for n complex numbers (|a_hat|^2 with b_hat NULL); c may be a_hat or b_hat.  Enqueued on the stream.
+ * tlab_fluctuation: out = in - mean(j), FI_FLUCTUATION_INPLACE (mappings/fi_dissipation.f90:119-139) into another array with the means of
+ *   tlab_avg_ik_v handed in.
+ * tlab_avg_cov2v: the three COV2V2D of spectra.f90:624-628 in one pass: cov + (0, 1, 2)*ldcov = plane means of a*b, a*a, b*b (arrays classified
+ *   like tlab_avg_ik_v).
+ * tlab_spectra_pair: the loop body of spectra.f90:620-659 for one pair of FLUCTUATION fields a, b (NULL or a: auto) on the transforms of a
+ *   single-device plan; device arrays only.  mode 1: spectra, 2: correlations (the product, the two inverse transforms, tlab_correlation_reduce with
+ *   nr_total = kr_total and the radial sums always taken).  tmp1-3: (nx+2)*ny*nz doubles each, overwritten; a and b are not.  cov (ny, 3): the
+ *   covariances a*b, a*a, b*b; variance (ny): variance of mode 1, variance2 of mode 2 -- the reference compares either with cov(:, 1).
+ * tlab_dns_spectra: the pairs of spectra.f90:482-522 on the driver's arrays: the variables are u, v, w, (p,) and the nscal scalars; cross = 0: every
+ *   variable with itself, cross = 1: uv, uw, vw and us, vs, ws per scalar.  The means are removed into txc[0], txc[1]; txc[3..5] are the work
+ *   arrays; q, s, p and the driver state are not touched.  p (NULL: none) must not be one of those five.  Outputs hold one block per pair, back to
+ *   back in pair order, each as tlab_spectra_pair writes it. */
+int tlab_spectrum_reduce(int nx, int ny, int nz, int nblock, int kr_total, const double *a_hat, const double *b_hat, double *out2d, double *outx,
+                         double *outz, double *outr, double *variance);
+int tlab_correlation_reduce(int nx, int ny, int nz, int nblock, int nr_total, const double *in, const double *var1, const double *var2, double *out2d,
+                            double *outx, double *outz, double *outr, double *variance2, int icalc_radial);
+int tlab_radial_samplesize(int nx, int nz, int nr_total, double *samplesize);
+int tlab_cross_product(long long n, const double *a_hat, const double *b_hat, double *c);
+int tlab_fluctuation(int nx, int ny, int nz, const double *in, const double *mean, double *out);
+int tlab_avg_cov2v(int nx, int ny, int nz, const double *a, const double *b, double *cov, int ldcov);
+int tlab_spectra_pair(tlab_poisson_plan_t plan, int mode, int nblock, int kr_total, const double *a, const double *b, double *tmp1, double *tmp2,
+                      double *tmp3, double *out2d, double *outx, double *outz, double *outr, double *cov, double *variance);
+int tlab_dns_spectra(tlab_dns_t h, int mode, int cross, int nblock, int kr_total, double *const *q, double *const *s, double *const *txc,
+                     const double *p, double *out2d, double *outx, double *outz, double *outr, double *cov, double *variance);
 int tlab_pdf1v_n(int nx, int ny, int nz, int nv, int nbins, const int *ibc, const double *umin, const double *umax, const double *const *u,
                  int igate, const signed char *gate, double *pdf);
 int tlab_pdf_minmax_planes(int nx, int ny, int nz, int nv, const double *const *u, int igate, const signed char *gate, double *umin, double *umax);

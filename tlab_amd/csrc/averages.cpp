@@ -122,6 +122,16 @@ int tlab_avg1v2d_v(int nx, int ny, int nz, int imom, const double *a, double *av
     }, TLAB_EINVAL);
 }
 
+int tlab_avg_cov2v(int nx, int ny, int nz, const double *a, const double *b, double *cov, int ldcov) {
+    (void)tlab_internal_deferred_flush();
+    return catch_fail([&] {
+        if (!a || !b || !cov) throw Fail(TLAB_EINVAL, "tlab_avg_cov2v: a null pointer");
+        check_box("tlab_avg_cov2v", nx, ny, nz, ldcov);
+        const double *f[2] = {a, b};
+        run(on_device("tlab_avg_cov2v", 2, f), AVG_PROG_COV2, 0, nx, ny, nz, f, nullptr, cov, ldcov);
+    }, TLAB_EINVAL);
+}
+
 int tlab_avg_moments_flow(int nx, int ny, int nz, const double *u, const double *v, const double *w, const double *p, const double *fU,
                           const double *fV, const double *fW, const double *rP, double *out, int ldout) {
     (void)tlab_internal_deferred_flush();

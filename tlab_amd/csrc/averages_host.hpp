@@ -21,6 +21,7 @@
 //   AvgGradScal1    Fy, Ess, S_x2 .. S_z4 (avg_scal_xz.f90:607, :714-738) on dsdx dsdy dsdz: mean rS_y
 //   AvgGradScal2<P> Tssy2, Tsuy2_d .. Tswy2_d (:742-745) and PIsu PIsv PIsw (:451-453) on dsdy s u v w (, p dsdx dsdz):
 //                   means Fy fS fU fV fW (, rP fS_y)
+//   AvgCov2         a*b, a*a, b*b of a pair of fields (COV2V2D, utils/averages.f90:244-267): the covariances of tools/statistics/spectra.f90
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,7 +36,7 @@ constexpr int AVG_MAX_FIELDS = 13;          // fields of one program (the kernel
 constexpr double AVG_C23 = 2.0 / 3.0;       // c23 of the reference (2.0_wp/3.0_wp)
 
 enum { AVG_PROG_MEANS = 0, AVG_PROG_POWER = 1, AVG_PROG_FLOW = 2, AVG_PROG_SCAL = 3, AVG_PROG_GRAD_FLOW1 = 4, AVG_PROG_GRAD_FLOW2 = 5,
-       AVG_PROG_GRAD_FLOW3 = 6, AVG_PROG_UGRADP = 7, AVG_PROG_GRAD_SCAL1 = 8, AVG_PROG_GRAD_SCAL2 = 9 };
+       AVG_PROG_GRAD_FLOW3 = 6, AVG_PROG_UGRADP = 7, AVG_PROG_GRAD_SCAL1 = 8, AVG_PROG_GRAD_SCAL2 = 9, AVG_PROG_COV2 = 10 };
 
 template <int NF>
 struct AvgMeans {
@@ -213,6 +214,16 @@ struct AvgGradScal2 {
     }
 };
 
+// fields: a b.  outputs: a*b | a*a | b*b -- the three COV2V2D (utils/averages.f90:244-267) that tools/statistics/spectra.f90:624-628 takes of a pair,
+// in one pass over the two fields
+struct AvgCov2 {
+    static constexpr int NFLD = 2, NMEAN = 0, NOUT = 3, ROWS = 4;
+    static constexpr const char *TAG = "k_plane_partial<COV2>";
+    static __host__ __device__ __forceinline__ void add(const double *x, const double *, double *acc) {
+        acc[0] += x[0] * x[1]; acc[1] += x[0] * x[0]; acc[2] += x[1] * x[1];
+    }
+};
+
 // Calls fn(P{}) with the program type P of (prog, param); false when there is none.
 template <class F>
 bool avg_dispatch(int prog, int param, F &&fn) {
@@ -253,6 +264,7 @@ bool avg_dispatch(int prog, int param, F &&fn) {
     case AVG_PROG_GRAD_SCAL2:
         if (param) fn(AvgGradScal2<true>{}); else fn(AvgGradScal2<false>{});
         return true;
+    case AVG_PROG_COV2: fn(AvgCov2{}); return true;
     }
     return false;
 }

@@ -18,6 +18,7 @@ using namespace tlab;
 
 long long tlab_internal_dns_points(tlab_dns_t d) { return d ? (long long)d->nx * d->ny * d->nz : 0; }
 int tlab_internal_dns_nscal(tlab_dns_t d) { return d ? d->nscal : 0; }
+tlab_poisson_plan_t tlab_internal_dns_poisson(tlab_dns_t d) { return d ? d->poisson : nullptr; }
 int tlab_internal_dns_scal_arrays(tlab_dns_t d) { return d ? d->scal_arrays() : 0; }
 bool tlab_internal_dns_has_bounds(tlab_dns_t d) { return d && d->bounds.any(); }
 bool tlab_internal_dns_has_flow_zones(tlab_dns_t d) { return d && (d->buff[0][0].size > 0 || d->buff[0][1].size > 0); }

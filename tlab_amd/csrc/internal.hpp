@@ -76,6 +76,8 @@ void tlab_internal_filter_fields(int nx, int ny, int nz, tlab_filter_t const *f,
 
 // ---- poisson.hip ----
 bool tlab_internal_poisson_has_own_x(tlab_poisson_plan_t P);
+// spectra.cpp: n = (nx, ny, nz) of a single-device plan whose x and z transforms cover the whole box; false for a slab, pencil or nz = 1 plan's layout
+bool tlab_internal_poisson_box(tlab_poisson_plan_t P, int *n);
 // hooks of the RHS driver (rhs.cpp)
 bool tlab_internal_poisson_can_v_final(tlab_poisson_plan_t P);
 void tlab_internal_poisson_arm_v_final(tlab_poisson_plan_t P, double *q, double *h, double dte, double kco, int scale);
@@ -95,6 +97,7 @@ int tlab_internal_zslab_gradient_final_z(tlab_zslab_plan_t P, int nx, int ny, co
 // ---- dns_setup.cpp: the single-domain driver apart from its substep (its state: dns_state.hpp) ----
 long long tlab_internal_dns_points(tlab_dns_t d);      // deferred.cpp
 int tlab_internal_dns_nscal(tlab_dns_t d);
+tlab_poisson_plan_t tlab_internal_dns_poisson(tlab_dns_t d);      // spectra.cpp: the plan whose transforms the driver's statistics use
 int tlab_internal_dns_scal_arrays(tlab_dns_t d);      // inb_scal_array: nscal, + 1 (the liquid) with a mixture -- the arrays every s of the entry points holds
 // what the driver holds (deferred.cpp; slab.cpp, pencil.cpp: the zones and forces of a rank live in its single-domain handle)
 bool tlab_internal_dns_has_bounds(tlab_dns_t d);

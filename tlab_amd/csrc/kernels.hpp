@@ -282,6 +282,25 @@ hipError_t launch_gate_threshold(const double *a, long long n, double thr, signe
 //                      inter: [np][ny] = count / real(nx * nz)
 hipError_t launch_gate_count(const signed char *gate, int nx, int ny, int nz, int np, unsigned *cnt, double *inter, hipStream_t st);
 
+// spectra.hip: plane spectra and correlations (index maps and ring lists: spectra_host.hpp).  Nothing is copied or synchronised here; every array is
+// device memory.  a, b: complex (nx/2+1, ny, nz), natural kz; b null: an auto pair.
+//   launch_spectrum_reduce     S: scratch, (nx/2) * (ny/nblock) * nz doubles; rowv: scratch, ny * nz doubles; ring_off [kr_total + 1], ring_mode: the
+//                              lists of spectrum_rings(nx/2, nz, kr_total); outx (nx/2, ny/nblock), outz (nz/2, ny/nblock), outr (kr_total, ny/nblock)
+//                              and out2d (nx/2, ny/nblock, nz; may be null) are accumulated into, variance (ny) is written
+//   launch_cross_product       c = b conj(a) for n complex numbers; c may be a or b
+//   launch_correlation_reduce  in (nx, ny, nz) real, normj (ny); lists of correlation_rings(nx, nz, nr_total); outx (nx, ny/nblock), outz (nz, ny/nblock),
+//                              out2d (nx, ny/nblock, nz; may be null) and outr (nr_total, ny/nblock; null: no radial sums) are accumulated into,
+//                              variance2 (ny) is written
+//   launch_fluctuation         out = in - mean(j)
+hipError_t launch_spectrum_reduce(int nx, int ny, int nz, int nblock, int kr_total, const double *a, const double *b, double *S, double *rowv,
+                                  const int *ring_off, const int *ring_mode, double *out2d, double *outx, double *outz, double *outr,
+                                  double *variance, hipStream_t st);
+hipError_t launch_cross_product(const double *a, const double *b, double *c, long long n, hipStream_t st);
+hipError_t launch_correlation_reduce(int nx, int ny, int nz, int nblock, int nr_total, const double *in, const double *normj, const int *ring_off,
+                                     const int *ring_mode, double *out2d, double *outx, double *outz, double *outr, double *variance2,
+                                     hipStream_t st);
+hipError_t launch_fluctuation(int nx, int ny, int nz, const double *in, const double *mean, double *out, hipStream_t st);
+
 hipError_t launch_wall_weighted(const double *a1, const double *a2, const double *wb, const double *wt, int K, double *ob1, double *ot1, double *ob2,
                                 double *ot2, int nx, int ny, int nz, hipStream_t st);
 hipError_t launch_wall_fix(double *q, double *h, const double *sb, const double *st, double dte, double kco, int scale, int nx, int ny, int nz,

@@ -551,6 +551,11 @@ void tlab_poisson_plan::backward_xz(double *hat, double *out, hipStream_t st, co
 }
 
 bool tlab_internal_poisson_has_own_x(tlab_poisson_plan_t P) { return P && P->fx_own; }
+bool tlab_internal_poisson_box(tlab_poisson_plan_t P, int *n) {
+    if (!P || P->nproc != 1 || P->nzt != P->nz || P->koff != 0 || P->ioff != 0 || P->nxh != P->nx / 2 + 1 || P->fx_nxh != P->nxh || P->fx_nz != P->nz) return false;
+    n[0] = P->nx; n[1] = P->ny; n[2] = P->nz;
+    return true;
+}
 
 extern "C" {
 

@@ -186,6 +186,7 @@ class Dns:
         self.nx, self.ny, self.nz = len(x), len(y), len(z)
         self.n = self.nx * self.ny * self.nz
         self.y = np.ascontiguousarray(y, dtype=np.float64)          # g(2)%nodes: the buffer zones' strength (set_buffer_zones)
+        self._dxz = tuple(float(a[1] - a[0]) if len(a) > 1 else 0.0 for a in (x, z))      # the uniform spacings of x and z (spectra)
         self.nscal = int(nscal)
         self.visc = float(visc)
         self.schmidt = np.ascontiguousarray(schmidt, dtype=np.float64)[: self.nscal]
@@ -708,6 +709,60 @@ class Dns:
         check(load().tlab_minmax(self._h, vort.data_ptr(), self.nx, self.ny, self.nz, ctypes.byref(mn), ctypes.byref(mx)), "tlab_minmax")
         gate = gate_threshold(vort[: self.n], (1.0e-3 * 1.0e-3) * mx.value)
         return {"Vorticity": inter_n_xz(self.nx, self.ny, self.nz, 1, gate)[0]}
+
+    def spectra(self, mode="spectra", cross=False, nblock=1, p=None, out2d=False):
+        """tools/statistics/spectra.f90, opt_main 1-4, for the fields of the driver, without its files: mode "spectra" (power and co-spectra)
+        or "correlations", cross False (every variable with itself: u, v, w, (p,) and the scalars) or True (uv, uw, vw and us, vs, ws per
+        scalar), sums over blocks of nblock planes.  p: a pressure field, or True to take FI_PRESSURE_BOUSSINESQ first, as the tool does.
+        A dict keyed by the reference's variable names (Euu, Evv, .., E11, or Cuv, ..); each entry holds numpy "x" (ny/nblock, nx/2 or nx),
+        "z" (ny/nblock, nz/2 or nz), "r" (ny/nblock, kr_total: min(nx, nz) for cross-correlations, min(nx/2, nz/2) otherwise) where the
+        reference writes it (nx == nz for spectra, equal x and z spacing for correlations), with
+        out2d "xz", all after the reference's 1/nblock (:683-690) and, for radial correlations, the division by the sample size (:709-722);
+        "cov" (3, ny), "variance" (ny,) and "parseval" = max |variance - cov[0]| over the planes kept (:662-666).  txc[0], [1], [3..5] are
+        the work space; q, s, hq, hs and the state of the driver are unchanged."""
+        import torch
+        from .operators import radial_samplesize
+        m = {"spectra": 1, "correlations": 2}.get(mode)
+        if m is None:
+            raise TlabError('mode: "spectra" or "correlations"')
+        if p is True:
+            p = self.FI_PRESSURE_BOUSSINESQ()
+        nx, ny, nz, nyo = self.nx, self.ny, self.nz, self.ny // max(int(nblock), 1)
+        n1, nz1 = (nx // 2, nz // 2) if m == 1 else (nx, nz)
+        kr = min(nx, nz) if (m == 2 and cross) else min(nx // 2, nz // 2)     # kr_total, :271-282: the full length for cross-correlations only
+        var = ["u", "v", "w"] + (["p"] if p is not None else []) + [str(i + 1) for i in range(self.nscal)]
+        if not cross:
+            pairs = [(a, a) for a in var]
+        else:
+            pairs = [("u", "v"), ("u", "w"), ("v", "w")] + [(a, str(i + 1)) for i in range(self.nscal) for a in "uvw"]
+        npairs = len(pairs)
+        dev = self.q[0].device
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)      # noqa: E731
+        ox, oz, orr = z(npairs, nyo, n1), z(npairs, nyo, nz1), z(npairs, nyo, kr)
+        o2 = z(npairs, nz, nyo, n1) if out2d else None
+        cov, variance = np.zeros((npairs, 3, ny)), np.zeros((npairs, ny))
+        _use_torch_stream()
+        q, s, _, _, txc = self._arrays()
+        check(load().tlab_dns_spectra(self._h, m, int(bool(cross)), int(nblock), kr, q, s, txc, p.data_ptr() if p is not None else None,
+                                      o2.data_ptr() if out2d else None, ox.data_ptr(), oz.data_ptr(), orr.data_ptr(), cov.ctypes.data,
+                                      variance.ctypes.data), "tlab_dns_spectra")
+        # icalc_radial, :406-408: g(1)%jac(1, 1) == g(3)%jac(1, 1) there; here the two uniform spacings, equal up to the rounding of the nodes
+        radial = nx == nz if m == 1 else abs(self._dxz[0] - self._dxz[1]) <= 1.0e-12 * max(abs(self._dxz[0]), abs(self._dxz[1]))
+        scale = 1.0 / float(nblock) if nblock > 1 else 1.0                  # :684-690
+        ox, oz, orr = ox.cpu().numpy() * scale, oz.cpu().numpy() * scale, orr.cpu().numpy() * scale
+        if m == 2 and radial:
+            ss = radial_samplesize(nx, nz, kr)
+            orr = orr * np.where(ss > 0.0, 1.0 / np.where(ss > 0.0, ss, 1.0), ss)[None, None, :]      # :709-722
+        res, ny_loc = {}, nyo * int(nblock)
+        for i, (a, b) in enumerate(pairs):
+            e = {"x": ox[i], "z": oz[i], "cov": cov[i], "variance": variance[i],
+                 "parseval": float(np.abs(variance[i, :ny_loc] - cov[i, 0, :ny_loc]).max())}
+            if radial:
+                e["r"] = orr[i]
+            if out2d:
+                e["xz"] = o2[i].cpu().numpy() * scale
+            res[("E" if m == 1 else "C") + a + b] = e
+        return res
 
     def profile_derivative(self, profiles):
         """OPR_Partial_Y(OPR_P1, 1, jmax, 1, bcs, g(2), ..) of profiles (numpy (n, ny)) with the driver's y plan: numpy (n, ny).  The line

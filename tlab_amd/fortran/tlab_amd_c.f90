@@ -687,6 +687,34 @@ module TLab_AMD_C
             type(c_ptr), value :: gate
             real(c_double), intent(out) :: inter(*)
         end function
+        ! plane spectra and correlations (tlab_amd_spectra.f90); a_hat .. outr: device or host arrays of one kind, the profiles host memory
+        integer(c_int) function tlab_spectrum_reduce(nx, ny, nz, nblock, kr_total, a_hat, b_hat, out2d, outx, outz, outr, variance) &
+            bind(C, name='tlab_spectrum_reduce')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nblock, kr_total
+            type(c_ptr), value :: a_hat, b_hat, out2d, outx, outz, outr
+            real(c_double), intent(out) :: variance(*)
+        end function
+        integer(c_int) function tlab_correlation_reduce(nx, ny, nz, nblock, nr_total, in, var1, var2, out2d, outx, outz, outr, variance2, &
+                                                        icalc_radial) bind(C, name='tlab_correlation_reduce')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nblock, nr_total, icalc_radial
+            type(c_ptr), value :: in, out2d, outx, outz, outr
+            real(c_double), intent(in) :: var1(*), var2(*)
+            real(c_double), intent(out) :: variance2(*)
+        end function
+        integer(c_int) function tlab_radial_samplesize(nx, nz, nr_total, samplesize) bind(C, name='tlab_radial_samplesize')
+            import :: c_int, c_double
+            integer(c_int), value :: nx, nz, nr_total
+            real(c_double), intent(out) :: samplesize(*)
+        end function
+        integer(c_int) function tlab_spectra_pair(plan, mode, nblock, kr_total, a, b, tmp1, tmp2, tmp3, out2d, outx, outz, outr, cov, variance) &
+            bind(C, name='tlab_spectra_pair')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: plan, a, b, tmp1, tmp2, tmp3, out2d, outx, outz, outr
+            integer(c_int), value :: mode, nblock, kr_total
+            real(c_double), intent(out) :: cov(*), variance(*)
+        end function
         integer(c_int) function tlab_boundary_bcs_neumann_y(plan, ibc, nx, ny, nz, u, bcs_hb, bcs_ht, tmp1) bind(C, name='tlab_boundary_bcs_neumann_y')
             import :: c_int, c_ptr
             type(c_ptr), value :: plan, u, bcs_hb, bcs_ht, tmp1

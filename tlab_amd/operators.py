@@ -621,6 +621,139 @@ def inter_n_xz(nx, ny, nz, np_, gate):
     return out
 
 
+# ---- spectra and correlations in horizontal planes: tools/statistics/spectra.f90 with module SpectraMod (include/tlab_amd.h) ------------------------
+# Arrays of a call are all torch CUDA tensors or all host arrays (numpy, or torch CPU tensors); the results are of the kind of the inputs, shaped
+# C-ordered: a Fortran out(i, j, k) is out[k, j, i].  Accumulators handed in through `out` are added to, as in the reference.
+def _complex_ptr(a, n, name, keep):
+    """the address of n complex numbers: a numpy complex128 array, a torch complex128 tensor, or either as 2 n float64 (re, im interleaved)"""
+    if a is None:
+        return c_vp(0)
+    if isinstance(a, np.ndarray):
+        if a.dtype == np.complex128:
+            a = a.view(np.float64)
+    elif a.is_complex():
+        import torch
+        a = torch.view_as_real(a)
+    return _field_ptr(a, 2 * n, name, keep)
+
+
+def _accumulators(like, shapes, out):
+    """zeroed arrays of the kind of `like` for the keys of shapes that `out` (a dict, or None) does not hold"""
+    res = dict(out) if out else {}
+    for k, shp in shapes.items():
+        if k in res:
+            continue
+        if isinstance(like, np.ndarray):
+            res[k] = np.zeros(shp)
+        else:
+            import torch
+            res[k] = torch.zeros(shp, dtype=torch.float64, device=like.device)
+    return res
+
+
+def spectrum_reduce(nx, ny, nz, nblock, kr_total, a_hat, b_hat=None, out=None, out2d=False):
+    """tlab_spectrum_reduce: REDUCE_SPECTRUM + INTEGRATE_SPECTRUM (spectra_pool.f90) from the transformed fields a_hat, b_hat (None: auto),
+    complex (nz, ny, nx/2+1) in the natural kz order.  A dict: "x" (ny/nblock, nx/2), "z" (ny/nblock, nz/2), "r" (ny/nblock, kr_total), with
+    out2d "xz" (nz, ny/nblock, nx/2) in the reference's shuffled kz order, and "variance", numpy (ny,), the Parseval control."""
+    keep, n, nyo = [], (nx // 2 + 1) * ny * nz, ny // max(int(nblock), 1)
+    shapes = {"x": (nyo, nx // 2), "z": (nyo, nz // 2), "r": (nyo, max(int(kr_total), 0))}
+    if out2d:
+        shapes["xz"] = (nz, nyo, nx // 2)
+    o = _accumulators(a_hat, shapes, out)
+    var = np.zeros(ny)
+    _stream_if_device([a_hat])
+    check(load().tlab_spectrum_reduce(nx, ny, nz, int(nblock), int(kr_total), _complex_ptr(a_hat, n, "a_hat", keep), _complex_ptr(b_hat, n, "b_hat", keep),
+                                      _field_ptr(o.get("xz"), nz * nyo * (nx // 2), "xz", keep), _field_ptr(o["x"], nyo * (nx // 2), "x", keep),
+                                      _field_ptr(o["z"], nyo * (nz // 2), "z", keep), _field_ptr(o["r"], nyo * int(kr_total), "r", keep),
+                                      c_vp(var.ctypes.data)), "tlab_spectrum_reduce")
+    o["variance"] = var
+    return o
+
+
+def correlation_reduce(nx, ny, nz, nblock, nr_total, field, var1, var2, out=None, out2d=False, icalc_radial=1):
+    """tlab_correlation_reduce: spectra.f90:653 and REDUCE_CORRELATION on the real field (nz, ny, nx) that the inverse transforms return, with
+    the variances var1, var2 (ny values, host).  A dict: "x" (ny/nblock, nx), "z" (ny/nblock, nz), with icalc_radial "r" (ny/nblock, nr_total), with
+    out2d "xz" (nz, ny/nblock, nx), and "variance", numpy (ny,): variance2."""
+    keep, nyo = [], ny // max(int(nblock), 1)
+    shapes = {"x": (nyo, nx), "z": (nyo, nz)}
+    if icalc_radial == 1:
+        shapes["r"] = (nyo, max(int(nr_total), 0))
+    if out2d:
+        shapes["xz"] = (nz, nyo, nx)
+    o = _accumulators(field, shapes, out)
+    var = np.zeros(ny)
+    _stream_if_device([field])
+    check(load().tlab_correlation_reduce(nx, ny, nz, int(nblock), int(nr_total), _field_ptr(field, nx * ny * nz, "field", keep),
+                                         _profile(var1, ny, "var1", keep), _profile(var2, ny, "var2", keep),
+                                         _field_ptr(o.get("xz"), nz * nyo * nx, "xz", keep), _field_ptr(o["x"], nyo * nx, "x", keep),
+                                         _field_ptr(o["z"], nyo * nz, "z", keep), _field_ptr(o.get("r"), nyo * int(nr_total), "r", keep),
+                                         c_vp(var.ctypes.data), int(icalc_radial)), "tlab_correlation_reduce")
+    o["variance"] = var
+    return o
+
+
+def radial_samplesize(nx, nz, nr_total):
+    """RADIAL_SAMPLESIZE (spectra_pool.f90:365): the number of separations (i, k) of a plane (nx, nz) in every ring, numpy (nr_total,)"""
+    s = np.zeros(max(int(nr_total), 1))
+    check(load().tlab_radial_samplesize(nx, nz, int(nr_total), c_vp(s.ctypes.data)), "tlab_radial_samplesize")
+    return s
+
+
+def cross_product(a_hat, b_hat=None, c=None):
+    """c = b_hat conj(a_hat) (|a_hat|**2 with b_hat None) for complex arrays of one size; c defaults to b_hat (a_hat for an auto pair): in place"""
+    keep = []
+    c = (a_hat if b_hat is None else b_hat) if c is None else c
+    is_complex = a_hat.dtype == np.complex128 if isinstance(a_hat, np.ndarray) else a_hat.is_complex()
+    n = (a_hat.size if isinstance(a_hat, np.ndarray) else a_hat.numel()) // (1 if is_complex else 2)
+    _stream_if_device([c])
+    check(load().tlab_cross_product(n, _complex_ptr(a_hat, n, "a_hat", keep), _complex_ptr(b_hat, n, "b_hat", keep), _complex_ptr(c, n, "c", keep)),
+          "tlab_cross_product")
+    return c
+
+
+def fluctuation(nx, ny, nz, a, mean, out):
+    """out = a - mean(j): FI_FLUCTUATION_INPLACE (mappings/fi_dissipation.f90:119) into another array, mean: ny host values (avg_ik_v)"""
+    keep = []
+    _stream_if_device([a])
+    check(load().tlab_fluctuation(nx, ny, nz, _field_ptr(a, nx * ny * nz, "a", keep), _profile(mean, ny, "mean", keep),
+                                  _field_ptr(out, nx * ny * nz, "out", keep)), "tlab_fluctuation")
+    return out
+
+
+def avg_cov2v(nx, ny, nz, a, b):
+    """The three COV2V2D of spectra.f90:624-628 in one pass: numpy (3, ny), the plane means of a*b, a*a, b*b"""
+    keep, n = [], nx * ny * nz
+    out = np.zeros((3, ny))
+    _stream_if_device([a, b])
+    check(load().tlab_avg_cov2v(nx, ny, nz, _field_ptr(a, n, "a", keep), _field_ptr(b, n, "b", keep), c_vp(out.ctypes.data), ny), "tlab_avg_cov2v")
+    return out
+
+
+def spectra_pair(plan, mode, nblock, kr_total, a, b=None, tmp=None, out=None, out2d=False):
+    """tlab_spectra_pair: the loop body of spectra.f90:620-659 for one pair of fluctuation fields a, b (None: auto) on the transforms of a
+    PoissonPlan.  mode: "spectra" | "correlations" (or 1 | 2).  tmp: three CUDA tensors of plan.isize_txc_field values (made when None).  The dict
+    of spectrum_reduce / correlation_reduce plus "cov", numpy (3, ny): the covariances a*b, a*a, b*b of every plane."""
+    import torch
+    mode = {"spectra": 1, "correlations": 2}.get(mode, mode)
+    nx, ny, nz = plan.nx, plan.ny, plan.nz
+    keep, n, nyo = [], nx * ny * nz, ny // max(int(nblock), 1)
+    n1, nz1 = (nx // 2, nz // 2) if mode == 1 else (nx, nz)
+    shapes = {"x": (nyo, n1), "z": (nyo, nz1), "r": (nyo, max(int(kr_total), 0))}
+    if out2d:
+        shapes["xz"] = (nz, nyo, n1)
+    o = _accumulators(a, shapes, out)
+    if tmp is None:
+        tmp = [torch.empty(plan.isize_txc_field, dtype=torch.float64, device=a.device) for _ in range(3)]
+    cov, var = np.zeros((3, ny)), np.zeros(ny)
+    _use_torch_stream()
+    check(load().tlab_spectra_pair(plan._h, int(mode), int(nblock), int(kr_total), _field_ptr(a, n, "a", keep), _field_ptr(b, n, "b", keep),
+                                   *[_ptr(t, plan.isize_txc_field, "tmp") for t in tmp], _field_ptr(o.get("xz"), nz * nyo * n1, "xz", keep),
+                                   _field_ptr(o["x"], nyo * n1, "x", keep), _field_ptr(o["z"], nyo * nz1, "z", keep),
+                                   _field_ptr(o["r"], nyo * int(kr_total), "r", keep), c_vp(cov.ctypes.data), c_vp(var.ctypes.data)), "tlab_spectra_pair")
+    o["cov"], o["variance"] = cov, var
+    return o
+
+
 # ---- sampling between two statistics steps: phase averages (statistics/avg_phase.f90), towers (tools/dns/dns_tower.f90), saved planes
 # (tools/dns/planes.f90).  The accumulators are the caller's arrays, of the kind of the fields (torch tensors or numpy arrays); no call synchronises.
 def avg_phase_plane_id(itr, it_first, it_save):
