@@ -589,7 +589,8 @@ int tlab_dns_begin_step(tlab_dns_t d);
  * exactly that of time.f90 (the tendencies and states the RHS was given, dte as the factor, one kco for all) the library runs ONE
  * tlab_time_substep_incompressible_explicit(dte, kco, scale) -- the call of the patched host, bit for bit -- and the
  * zero fills become tlab_dns_begin_step.  Anything else is executed literally in the order it came.  A recorded sequence runs before any other
- * launch of the library (every entry point that enqueues work, tlab_sync, the copies, tlab_free flush first).  NOT covered: host statements that
+ * launch of the library (every entry point that enqueues work, tlab_sync, the copies, tlab_free and the *_destroy functions flush first) and with the
+ * settings of the moment it was recorded (every setter whose state a substep reads flushes first as well).  NOT covered: host statements that
  * read a device array directly without a call into the library -- call tlab_deferred_flush() (or tlab_sync()) before them.  A recorded substep that
  * FAILS when another entry point makes it run has no caller to report to: its code is returned by the next tlab_sync / tlab_deferred_flush (the text
  * stays in tlab_last_error()).  Off by default:

@@ -423,6 +423,54 @@ def test_unchanged_time_loop_runs_the_fused_substep_bit_for_bit(tmp_path):
     assert 0.0 < d <= 1e-11, d
 
 
+def test_operator_call_after_the_time_step_sees_the_recorded_substep_executed(tmp_path):
+    """TLAB_AMD_PROBE_OPERATOR=1: after every TIME_RUNGEKUTTA() the host calls OPR_Partial_X(OPR_P1) on u through the drop-in module, with no sync
+    in front -- what DNS_BOUNDS_CONTROL -> FI_INVARIANT_P does (dns_main.f90:269).  With the deferred tail the last substep of the step is only
+    recorded at that point (no DSCAL follows it): the operator must make it run first.  Box and fields of the test above, 2 steps.  The PROBE lines
+    (sum and maximum of |du/dx|, 17 digits) of the unpatched host equal those of the patched one character for character, and the counters are
+    still those of six whole fused substeps: the probe made the record run as it was, neither early in pieces nor not at all.  The literal
+    sequence (TLAB_AMD_DEFER=0) has nothing pending; its lines are printed."""
+    import re
+    import numpy as np
+    _need_rk()
+    if not os.path.exists(RK_EXE_FUSED):
+        pytest.skip("tlab_amd/fortran/_build_rk_fused/test_rk_driver not built")
+    # the drivers are built from the reference's files: where the reference is absent build() puts back prebuilt ones (oracle/_ref/fortran), and
+    # those may predate the switch (as tests/test_gpu_monitors.py finds for TLAB_AMD_MONITORS): such drivers are not the ones this test is about
+    for exe in (RK_EXE, RK_EXE_FUSED):
+        with open(exe, "rb") as f:
+            if b"TLAB_AMD_PROBE_OPERATOR" not in f.read():
+                pytest.skip("%s is a prebuilt driver from before TLAB_AMD_PROBE_OPERATOR: rebuild it where the reference is" % os.path.relpath(exe, ROOT))
+    nx, ny, nz = 256, 64, 32
+    x = np.arange(nx) / nx * 2.0
+    z = np.arange(nz) / nz
+    y = 0.5 * (1 + np.tanh(1.5 * (2 * np.arange(ny) / (ny - 1) - 1)) / np.tanh(1.5))
+    rng = np.random.default_rng(78)
+    Z, Y, X = np.meshgrid(z, y, x, indexing="ij")
+    wall = np.sin(np.pi * Y)
+    q0 = [((np.sin(np.pi * X + k) * np.cos(2 * np.pi * Z) + 0.1 * rng.uniform(-1, 1, X.shape)) * wall).ravel() for k in range(3)]
+    s0 = [(np.cos(np.pi * X) * Y + 0.1 * rng.uniform(-1, 1, X.shape)).ravel()]
+    bcs = ["VelocityJmin=noslip", "VelocityJmax=noslip", "Scalar1Jmin=dirichlet", "Scalar1Jmax=dirichlet"]
+    fields, probes, counters = {}, {}, {}
+    for tag, exe, env in (("fused", RK_EXE_FUSED, {}), ("deferred", RK_EXE, {}), ("literal", RK_EXE, {"TLAB_AMD_DEFER": "0"})):
+        d = tmp_path / tag
+        d.mkdir()
+        q1, s1, _ = run_rk_driver(str(d), x, y, z, q0, s0, 1000.0, 0.7, 1e-3, 2, bcs, exe=exe,
+                                  env=dict(env, TLAB_AMD_TIMING="0", TLAB_AMD_PROBE_OPERATOR="1"))
+        log = open(os.path.join(str(d), "tlab.log")).read()
+        probes[tag] = re.findall(r"PROBE: itime\s+\d+\s+sum\s+\S+\s+max\s+\S+", log)
+        m = re.search(r"DEFERRED: [a-z_ ]+?((?:\s+\d+){6})\s*$", log, re.M)
+        assert m, log[-1500:]
+        fields[tag], counters[tag] = q1 + s1, [int(v) for v in m.group(1).split()]
+        print(tag, counters[tag], probes[tag])
+    assert len(probes["fused"]) == 2 and probes["fused"][0] != probes["fused"][1], probes["fused"]      # one line per step, and u moves
+    assert probes["deferred"] == probes["fused"], (probes["deferred"], probes["fused"])
+    assert counters["deferred"] == [6, 0, 2, 0, 0, 0], counters["deferred"]
+    assert all(np.array_equal(a, b) for a, b in zip(fields["deferred"], fields["fused"]))
+    # nothing is ever pending in the literal sequence: its lines are those of fields that differ by rounding (no bound is set on a derivative here)
+    assert len(probes["literal"]) == 2 and counters["literal"] == [0, 0, 0, 24, 16, 4], (probes["literal"], counters["literal"])
+
+
 @pytest.mark.parametrize("route,nx,ny,nz", [("TLAB_AMD_FORCE_SLAB", 128, 32, 64), ("TLAB_AMD_FORCE_PENCIL", 64, 32, 32)])
 def test_unchanged_time_loop_behind_the_decomposed_drivers(tmp_path, route, nx, ny, nz):
     """The deferred tail behind tlab_slab_dns / tlab_pencil_dns (tlab_deferred_slab_rhs / _pencil_rhs): the unpatched loop's RHS + DAXPY + DSCAL calls

@@ -19,7 +19,6 @@ using namespace tlab;
 namespace {
 
 thread_local std::string g_err;
-hipStream_t g_stream = nullptr;
 int g_device = -1;
 int g_last_path = 0;
 int g_force_path = 0;
@@ -80,10 +79,20 @@ double *workspace(size_t n) {
 
 }  // namespace
 
+// The library's stream.  Nothing but tlab_current_stream() and tlab_set_stream() can name it (the compiler sees to that), so every launch of this
+// file takes it through the accessor, which runs a recorded substep first (csrc/deferred.cpp).  The tlab_internal_* fused variants that the drivers
+// call from INSIDE such a replay go the same way: tlab_internal_deferred_flush() returns at once while a flush is under way (its g_busy).
+class tlab_stream_holder {
+    static hipStream_t s;
+    friend hipStream_t (::tlab_current_stream)();
+    friend int (::tlab_set_stream)(void *);
+};
+hipStream_t tlab_stream_holder::s = nullptr;
+
 // hooks for the other translation units (internal.hpp)
 hipStream_t tlab_current_stream() {
     (void)tlab_internal_deferred_flush();
-    return g_stream;
+    return tlab_stream_holder::s;
 }
 void tlab_set_error(const std::string &s) { g_err = s; }
 bool tlab_device_ready() { return g_device >= 0; }
@@ -434,7 +443,7 @@ int tlab_device_count(void) {
 
 int tlab_set_stream(void *s) {
     (void)tlab_internal_deferred_flush();
-    g_stream = (hipStream_t)s;
+    tlab_stream_holder::s = (hipStream_t)s;
     return TLAB_OK;
 }
 
@@ -443,7 +452,7 @@ int tlab_sync(void) {
     const int rco = tlab_internal_deferred_take_error();      // a recorded substep that failed when another entry point made it run
     if (rcd != TLAB_OK) return rcd;
     if (rco != TLAB_OK) return rco;
-    return guarded([&] { hip_check(hipStreamSynchronize(g_stream), "hipStreamSynchronize"); });
+    return guarded([&] { hip_check(hipStreamSynchronize(tlab_current_stream()), "hipStreamSynchronize"); });
 }
 
 int tlab_malloc(void **p, size_t bytes) {
@@ -461,16 +470,18 @@ int tlab_memcpy_h2d(void *dst, const void *src, size_t bytes) {
     const int rcd = tlab_internal_deferred_flush();
     if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
-        hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g_stream), "hipMemcpy h2d");
-        hip_check(hipStreamSynchronize(g_stream), "sync");
+        const hipStream_t st = tlab_current_stream();
+        hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "hipMemcpy h2d");
+        hip_check(hipStreamSynchronize(st), "sync");
     });
 }
 int tlab_memcpy_d2h(void *dst, const void *src, size_t bytes) {
     const int rcd = tlab_internal_deferred_flush();
     if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
-        hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, g_stream), "hipMemcpy d2h");
-        hip_check(hipStreamSynchronize(g_stream), "sync");
+        const hipStream_t st = tlab_current_stream();
+        hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy d2h");
+        hip_check(hipStreamSynchronize(st), "sync");
     });
 }
 
@@ -536,6 +547,8 @@ int tlab_fdm_plan_set_aux(tlab_fdm_plan_t p, const double *mwn1, const double *m
 
 // mode_fdm of the two derivatives of a host-built plan (FDM_COM6_DIRECT = 16, FDM_COM4_DIRECT = 17 change how rhs is read)
 int tlab_fdm_plan_set_scheme(tlab_fdm_plan_t p, int mode1, int mode2) {
+    const int rcd = tlab_internal_deferred_flush();      // the recorded substep runs with the state of before
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         if (!p) throw Invalid("tlab_fdm_plan_set_scheme: null plan");
         auto direct = [](int m) { return m == FDM_COM6_DIRECT || m == FDM_COM4_DIRECT; };
@@ -554,6 +567,8 @@ int tlab_fdm_plan_set_scheme(tlab_fdm_plan_t p, int mode1, int mode2) {
 
 // [Staggering] StaggerHorizontalPressure (TLab_WorkFlow::stagger_on): what FDM_CreatePlan adds for a periodic direction (fdm.f90:236-248)
 int tlab_fdm_plan_set_stagger(tlab_fdm_plan_t p, int mode) {
+    const int rcd = tlab_internal_deferred_flush();      // the recorded substep runs with the state of before
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         if (!p) throw Invalid("tlab_fdm_plan_set_stagger: null plan");
         if (mode < 0 || mode > 2) throw Invalid("tlab_fdm_plan_set_stagger: mode 0 off, 1 tables + interpolatory wavenumbers, 2 tables only");
@@ -566,6 +581,7 @@ int tlab_fdm_plan_set_stagger(tlab_fdm_plan_t p, int mode) {
 }
 
 int tlab_fdm_plan_destroy(tlab_fdm_plan_t p) {
+    (void)tlab_internal_deferred_flush();      // (a recorded substep may still need the plan)
     if (p)
         for (auto &f : p->interp)
             if (f) tlab_filter_destroy(f);
@@ -753,8 +769,8 @@ void run_generic(tlab_fdm_plan_t g, const LineGeom &geom, int which, int ibc, co
             t.periodic = a.periodic; t.ibc = a.ibc;
             std::copy(d.rhs_b, d.rhs_b + 32, t.rb);
             std::copy(d.rhs_t, d.rhs_t + 35, t.rt);
-            if (along_x) hip_check(launch_pentatile_x(t, g_stream), "k_pentatile<x>");
-            else hip_check(launch_pentatile(t, g_stream), "k_pentatile");
+            if (along_x) hip_check(launch_pentatile_x(t, tlab_current_stream()), "k_pentatile<x>");
+            else hip_check(launch_pentatile(t, tlab_current_stream()), "k_pentatile");
         };
         if (geom.row_stride == 1 && pentatile_x_ok(geom)) {      // x lines of 64 .. 512 points: the tile kernel through an LDS tile, no transposes
             tile(geom, in0, out, true);
@@ -768,16 +784,16 @@ void run_generic(tlab_fdm_plan_t g, const LineGeom &geom, int which, int ibc, co
             if (!g->penta_ws) g->penta_ws = std::make_unique<DeviceArray>();
             if (g->penta_ws->n < 2 * N) g->penta_ws->alloc(2 * N);
             double *t1 = g->penta_ws->p, *t2 = t1 + N;
-            hip_check(launch_transpose(in0, t1, geom.n, (int)geom.nlines, g_stream), "transpose");
+            hip_check(launch_transpose(in0, t1, geom.n, (int)geom.nlines, tlab_current_stream()), "transpose");
             a.in0 = t1; a.out0 = t2;
             a.g.row_stride = geom.nlines; a.g.lines_inner = (int)geom.nlines; a.g.outer_stride = 0;
             if (pentatile_ok(a.g)) tile(a.g, t1, t2);
-            else hip_check(launch_penta1(a, g_stream), "k_penta1");
-            hip_check(launch_transpose(t2, out, (int)geom.nlines, geom.n, g_stream), "transpose");
+            else hip_check(launch_penta1(a, tlab_current_stream()), "k_penta1");
+            hip_check(launch_transpose(t2, out, (int)geom.nlines, geom.n, tlab_current_stream()), "transpose");
             return;
         }
         if (pentatile_ok(geom)) tile(geom, in0, out);
-        else hip_check(launch_penta1(a, g_stream), "k_penta1");
+        else hip_check(launch_penta1(a, tlab_current_stream()), "k_penta1");
         return;
     }
     GenericArgs a;
@@ -785,7 +801,7 @@ void run_generic(tlab_fdm_plan_t g, const LineGeom &geom, int which, int ibc, co
     a.s = g->stencil(which, ibc);
     a.y = g->system(which, ibc, 1).dev();
     a.jc = (which == 2 && d1in) ? g->jaccorr() : JacCorrDev{nullptr};
-    hip_check(launch_generic(which == 2, a, g_stream), "k_generic");
+    hip_check(launch_generic(which == 2, a, tlab_current_stream()), "k_generic");
 }
 
 void run_rtile(tlab_fdm_plan_t g, const LineGeom &geom, int mode, int ibc, const double *in0, const double *in1,
@@ -803,7 +819,7 @@ void run_rtile(tlab_fdm_plan_t g, const LineGeom &geom, int mode, int ibc, const
     a.y1 = g->system(1, ibc, P).dev();
     a.y2 = g->system(2, 0, P).dev();
     a.jc = (mode == MODE_P2_D1IN || mode == MODE_BURGERS_D1IN) ? g->jaccorr() : JacCorrDev{nullptr};
-    hip_check(launch_rtile(mode, a, g_stream), "k_rtile");
+    hip_check(launch_rtile(mode, a, tlab_current_stream()), "k_rtile");
 }
 
 int g_htile_policy = 0;   // 0 automatic, 1 never (two-launch k_rtile path), 2 always when the size allows
@@ -830,7 +846,7 @@ void run_htile(tlab_fdm_plan_t g, const LineGeom &geom, int mode, int ibc, const
     a.jc = (mode != MODE_P1) ? g->jaccorr() : JacCorrDev{nullptr};
     a.fresh_mask = ex.fresh_mask; a.fdiv = ex.fdiv; a.fidte = ex.fidte;
     a.ari = ex.ari; a.ari_mode = ex.ari_mode; a.ari_nx = ex.ari_nx; a.ari_ny = ex.ari_ny;
-    hip_check(launch_htile(mode, a, g_stream), "k_htile");
+    hip_check(launch_htile(mode, a, tlab_current_stream()), "k_htile");
 }
 
 // One line-set (first derivative, with or without the fused epilogues) along y or z.  k_rtile's 64-line tiles are the best form while a chunk of
@@ -874,7 +890,7 @@ void run_xline(tlab_fdm_plan_t g, const LineGeom &geom, int mode, int ibc, const
     const bool lv = !(e1.lane_invariant && e2.lane_invariant);
     static const bool dbg = getenv("TLAB_DEBUG") != nullptr;
     if (dbg) fprintf(stderr, "[tlab] k_xline mode %d n %d chunks %d lane_variant %d\n", mode, geom.n, P, (int)lv);
-    hip_check(launch_xline(mode, geom.n, P, lv, a, g_stream), "k_xline");
+    hip_check(launch_xline(mode, geom.n, P, lv, a, tlab_current_stream()), "k_xline");
 }
 
 void check_common(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc) {
@@ -1103,10 +1119,14 @@ extern "C" {
 
 int tlab_last_kernel_path(void) { return g_last_path; }
 int tlab_force_kernel_path(int path) {
+    const int rcd = tlab_internal_deferred_flush();      // the recorded substep runs with the state of before
+    if (rcd != TLAB_OK) return rcd;
     g_force_path = path;
     return TLAB_OK;
 }
 int tlab_set_tuning(int key, int value) {
+    const int rcd = tlab_internal_deferred_flush();      // the recorded substep runs with the state of before
+    if (rcd != TLAB_OK) return rcd;
     if (key == 1) { rtile_force_chunk(value); return TLAB_OK; }
     if (key == 2) { g_htile_policy = value; return TLAB_OK; }
     if (key == 3 && (value == 16 || value == 32)) { htile_set_lines(value); return TLAB_OK; }
@@ -1119,6 +1139,8 @@ int tlab_set_tuning(int key, int value) {
 // rhs_global_incompressible_1.f90:106-112, :257-259): fused kernels when the sizes are on a fast path, the reference's sequence otherwise.
 int tlab_opr_burgers_add(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, double nu, const double *s, const double *vel,
                          double *result, double *tmp1, double *tmp2) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(dir, g, nx, ny, nz, ibc);
         if (!s || !vel || !result || result == s || result == vel) throw Invalid("tlab_opr_burgers_add: null or aliased arrays");
@@ -1126,12 +1148,14 @@ int tlab_opr_burgers_add(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int
         if (!tmp1 || !tmp2 || tmp1 == tmp2 || tmp1 == result || tmp2 == result) throw Invalid("tlab_opr_burgers_add: the unfused path needs tmp1, tmp2");
         const int rc = tlab_opr_burgers(dir, g, s == vel ? TLAB_OPR_B_SELF : TLAB_OPR_B_U_IN, nx, ny, nz, ibc, nu, s, vel, tmp1, tmp2, 0);
         if (rc != TLAB_OK) throw Invalid(std::string("tlab_opr_burgers_add: ") + g_err);
-        hip_check(launch_add1(result, tmp1, (long long)nx * ny * nz, g_stream), "k_add1");
+        hip_check(launch_add1(result, tmp1, (long long)nx * ny * nz, tlab_current_stream()), "k_add1");
     });
 }
 
 int tlab_opr_burgers_add_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, int nf, const double *nu, const double *const *s,
                            const double *vel, double *const *result, double *tmp1, double *tmp2, int overwrite) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(dir, g, nx, ny, nz, ibc);
         if (nf < 1 || nf > 4 || !nu || !s || !vel || !result) throw Invalid("tlab_opr_burgers_add_n: bad arguments (1 to 4 fields)");
@@ -1140,7 +1164,7 @@ int tlab_opr_burgers_add_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, i
         if (!tlab_internal_anelastic() &&
             tlab_internal_burgers_acc_n(dir, g, nx, ny, nz, ibc, nf, nu, s, vel, result, overwrite != 0, nullptr, 0.0, 1.0, 0, nullptr, 0.0, 0u, nullptr, nullptr, nullptr, nullptr)) return;
         for (int f = 0; f < nf; ++f) {
-            if (overwrite) hip_check(hipMemsetAsync(result[f], 0, (size_t)nx * ny * nz * sizeof(double), g_stream), "memset");
+            if (overwrite) hip_check(hipMemsetAsync(result[f], 0, (size_t)nx * ny * nz * sizeof(double), tlab_current_stream()), "memset");
             const int rc = tlab_opr_burgers_add(dir, g, nx, ny, nz, ibc, nu[f], s[f], vel, result[f], tmp1, tmp2);
             if (rc != TLAB_OK) throw Invalid(std::string("tlab_opr_burgers_add_n: ") + g_err);
         }
@@ -1149,6 +1173,8 @@ int tlab_opr_burgers_add_n(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, i
 
 int tlab_opr_gradient_final(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, const double *p, double *q, double *h, double dte, double kco,
                             int scale, double *tmp1) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(dir, g, nx, ny, nz, 0);
         if (!p || !q || !h || q == h || p == q || p == h) throw Invalid("tlab_opr_gradient_final: null or aliased arrays");
@@ -1156,12 +1182,14 @@ int tlab_opr_gradient_final(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, 
         if (!tmp1 || tmp1 == p || tmp1 == q || tmp1 == h) throw Invalid("tlab_opr_gradient_final: the unfused path needs tmp1");
         const int rc = tlab_opr_partial(dir, g, TLAB_OPR_P1, nx, ny, nz, 0, p, tmp1, nullptr);
         if (rc != TLAB_OK) throw Invalid(std::string("tlab_opr_gradient_final: ") + g_err);
-        hip_check(launch_final_update(q, h, tmp1, nullptr, nullptr, dte, kco, scale, nx, ny, nz, g_stream), "k_final_update");
+        hip_check(launch_final_update(q, h, tmp1, nullptr, nullptr, dte, kco, scale, nx, ny, nz, tlab_current_stream()), "k_final_update");
     });
 }
 
 int tlab_opr_partial_add(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int ibc, const double *u, const double *ub, double scale,
                          double *result, int acc, double *tmp1, double *tmp2) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(dir, g, nx, ny, nz, ibc);
         if (!u || !result || result == u || result == ub) throw Invalid("tlab_opr_partial_add: null or aliased arrays");
@@ -1170,12 +1198,12 @@ int tlab_opr_partial_add(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int
         const long long n = (long long)nx * ny * nz;
         const double *operand = u;
         if (ub) {
-            hip_check(launch_axpy1(tmp1, u, ub, scale, n, g_stream), "k_axpy1");
+            hip_check(launch_axpy1(tmp1, u, ub, scale, n, tlab_current_stream()), "k_axpy1");
             operand = tmp1;
         }
         const int rc = tlab_opr_partial(dir, g, TLAB_OPR_P1, nx, ny, nz, ibc, operand, acc ? tmp2 : result, nullptr);
         if (rc != TLAB_OK) throw Invalid(std::string("tlab_opr_partial_add: ") + g_err);
-        if (acc) hip_check(launch_add1(result, tmp2, n, g_stream), "k_add1");
+        if (acc) hip_check(launch_add1(result, tmp2, n, tlab_current_stream()), "k_add1");
     });
 }
 
@@ -1183,6 +1211,8 @@ int tlab_opr_partial_add(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz, int
 // OPR_Partial_Y under ibc; the wall values follow from the first / last row of the compact scheme in a plane kernel.
 int tlab_boundary_bcs_neumann_y(tlab_fdm_plan_t g, int ibc, int nx, int ny, int nz, const double *u, double *bcs_hb, double *bcs_ht,
                                 double *tmp1) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(2, g, nx, ny, nz, ibc);
         if (ibc != BCS_ND && ibc != BCS_DN && ibc != BCS_NN) throw Invalid("BOUNDARY_BCS_NEUMANN_Y: ibc must be 1 (jmin), 2 (jmax) or 3 (both)");
@@ -1192,12 +1222,14 @@ int tlab_boundary_bcs_neumann_y(tlab_fdm_plan_t g, int ibc, int nx, int ny, int 
         neumann_y_coefficients(g, ibc, ny, cb, ct);
         const int rc = tlab_opr_partial(2, g, TLAB_OPR_P1, nx, ny, nz, ibc, u, tmp1, nullptr);
         if (rc != TLAB_OK) throw Invalid(std::string("BOUNDARY_BCS_NEUMANN_Y: ") + tlab_last_error());
-        hip_check(launch_neumann_planes(u, tmp1, cb, ct, (ibc & 1), (ibc & 2), bcs_hb, bcs_ht, nx, ny, nz, g_stream), "k_neumann_planes");
+        hip_check(launch_neumann_planes(u, tmp1, cb, ct, (ibc & 1), (ibc & 2), bcs_hb, bcs_ht, nx, ny, nz, tlab_current_stream()), "k_neumann_planes");
     });
 }
 
 int tlab_opr_partial(int dir, tlab_fdm_plan_t g, int type, int nx, int ny, int nz, int ibc, const double *u,
                      double *result, double *tmp1) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(dir, g, nx, ny, nz, ibc);
         if (!u || !result || u == result || (tmp1 && (tmp1 == u || tmp1 == result))) throw Invalid("u, result, tmp1 must be distinct");
@@ -1223,7 +1255,7 @@ int tlab_opr_partial(int dir, tlab_fdm_plan_t g, int type, int nx, int ny, int n
                 std::copy(lu.begin(), lu.end(), tab.begin() + (size_t)5 * n);
                 ok_or_throw(tlab_filter_create(&g->interp[k], TLAB_FILTER_COMPACT, n, 1, 0, 0, 10, tab.data()));
             }
-            tlab_internal_filter_1d(dir, g->interp[k], nx, ny, nz, u, result, g_stream);
+            tlab_internal_filter_1d(dir, g->interp[k], nx, ny, nz, u, result, tlab_current_stream());
             g_last_path = PATH_GENERIC;
             return;
         }
@@ -1232,8 +1264,8 @@ int tlab_opr_partial(int dir, tlab_fdm_plan_t g, int type, int nx, int ny, int n
         const long long ntot = (long long)nx * ny * nz;
         const LineGeom geom = make_geom(dir, nx, ny, nz);
         if (geom.n == 1) {  // 2-D guard (opr_partial.f90:175-177, :287-289)
-            hip_check(launch_fill(result, 0.0, ntot, g_stream), "fill");
-            if (type == TLAB_OPR_P2_P1 && tmp1) hip_check(launch_fill(tmp1, 0.0, ntot, g_stream), "fill");
+            hip_check(launch_fill(result, 0.0, ntot, tlab_current_stream()), "fill");
+            if (type == TLAB_OPR_P2_P1 && tmp1) hip_check(launch_fill(tmp1, 0.0, ntot, tlab_current_stream()), "fill");
             return;
         }
         const bool corr = g->t.der2.need_1der;
@@ -1280,6 +1312,8 @@ static int g_anelastic_ny = 0;
 static std::vector<double> g_anelastic_rb_host, g_anelastic_ri_host;
 static unsigned long g_anelastic_version = 0;
 int tlab_opr_burgers_set_anelastic(int ny, const double *rbackground, const double *ribackground) {
+    const int rcd = tlab_internal_deferred_flush();      // the recorded substep runs with the state of before
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         if (ny <= 0 || !rbackground || !ribackground) {      // back to the incompressible operator
             g_anelastic_ri.reset();
@@ -1312,6 +1346,8 @@ int tlab_internal_anelastic_state(const double **rb, const double **rib, unsigne
 static tlab_filter_t g_dealias[3] = {nullptr, nullptr, nullptr};
 static DeviceArray *g_wsd[2] = {nullptr, nullptr};      // wrkdea(:, 1:2) (:34, :124): filtered velocity and filtered ds/dx
 int tlab_opr_burgers_set_dealiasing(int dir, tlab_filter_t f) {
+    const int rcd = tlab_internal_deferred_flush();      // the recorded substep runs with the state of before
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         if (dir < 1 || dir > 3) throw Invalid("dir must be 1, 2 or 3");
         g_dealias[dir - 1] = f;
@@ -1336,6 +1372,8 @@ static double *dealias_ws(int k, size_t n) {
 
 int tlab_opr_burgers(int dir, tlab_fdm_plan_t g, int ivel, int nx, int ny, int nz, int ibc, double nu, const double *s,
                      const double *u, double *result, double *tmp1, int write_transposed) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         check_common(dir, g, nx, ny, nz, ibc);
         if (ivel != TLAB_OPR_B_SELF && ivel != TLAB_OPR_B_U_IN) throw Invalid("ivel must be OPR_B_SELF or OPR_B_U_IN");
@@ -1345,7 +1383,7 @@ int tlab_opr_burgers(int dir, tlab_fdm_plan_t g, int ivel, int nx, int ny, int n
         const long long ntot = (long long)nx * ny * nz;
         const LineGeom geom = make_geom(dir, nx, ny, nz);
         if (geom.n == 1) {  // opr_burgers.f90:207-210
-            hip_check(launch_fill(result, 0.0, ntot, g_stream), "fill");
+            hip_check(launch_fill(result, 0.0, ntot, tlab_current_stream()), "fill");
             return;
         }
         const bool corr = g->t.der2.need_1der;
@@ -1361,14 +1399,14 @@ int tlab_opr_burgers(int dir, tlab_fdm_plan_t g, int ivel, int nx, int ny, int n
             const double *uf = vel, *dsf = d1;
             if (g_dealias[dir - 1]) {
                 double *w1 = dealias_ws(0, (size_t)ntot), *w2 = dealias_ws(1, (size_t)ntot);
-                tlab_internal_filter_1d(dir, g_dealias[dir - 1], nx, ny, nz, vel, w1, g_stream);
-                tlab_internal_filter_1d(dir, g_dealias[dir - 1], nx, ny, nz, d1, w2, g_stream);
+                tlab_internal_filter_1d(dir, g_dealias[dir - 1], nx, ny, nz, vel, w1, tlab_current_stream());
+                tlab_internal_filter_1d(dir, g_dealias[dir - 1], nx, ny, nz, d1, w2, tlab_current_stream());
                 uf = w1; dsf = w2;
             }
             if (g_anelastic_ny > 0)
-                hip_check(launch_burgers_epilogue_anelastic(result, uf, dsf, nu, g_anelastic_ri->p, nx, ny, ntot, g_stream), "burgers epilogue (anelastic)");
+                hip_check(launch_burgers_epilogue_anelastic(result, uf, dsf, nu, g_anelastic_ri->p, nx, ny, ntot, tlab_current_stream()), "burgers epilogue (anelastic)");
             else
-                hip_check(launch_burgers_epilogue(result, uf, dsf, nu, ntot, g_stream), "burgers epilogue");
+                hip_check(launch_burgers_epilogue(result, uf, dsf, nu, ntot, tlab_current_stream()), "burgers epilogue");
         } else if (path == PATH_XLINE) {
             run_xline(g, geom, MODE_BURGERS, ibc, s, vel, result, nullptr, nu);
         } else if (path == PATH_RTILE && htile_ok(geom.n, MODE_BURGERS)) {
@@ -1379,20 +1417,22 @@ int tlab_opr_burgers(int dir, tlab_fdm_plan_t g, int ivel, int nx, int ny, int n
         } else {
             run_generic(g, geom, 1, ibc, s, nullptr, d1);
             run_generic(g, geom, 2, 0, s, corr ? d1 : nullptr, result);
-            hip_check(launch_burgers_epilogue(result, vel, d1, nu, ntot, g_stream), "burgers epilogue");
+            hip_check(launch_burgers_epilogue(result, vel, d1, nu, ntot, tlab_current_stream()), "burgers epilogue");
         }
         if (wt) {  // transposed operand exactly as the reference leaves it in tmp1 (opr_burgers.f90:250, :315)
-            if (dir == 1) hip_check(launch_transpose(s, tmp1, nx, ny * nz, g_stream), "transpose");
-            else hip_check(launch_transpose(s, tmp1, nx * ny, nz, g_stream), "transpose");
+            if (dir == 1) hip_check(launch_transpose(s, tmp1, nx, ny * nz, tlab_current_stream()), "transpose");
+            else hip_check(launch_transpose(s, tmp1, nx * ny, nz, tlab_current_stream()), "transpose");
         }
     });
 }
 
 int tlab_transpose(const double *a, int nra, int nca, double *b) {
+    const int rcd = tlab_internal_deferred_flush();      // a recorded substep runs first (csrc/deferred.cpp)
+    if (rcd != TLAB_OK) return rcd;
     return guarded([&] {
         if (!a || !b || a == b || nra < 1 || nca < 1) throw Invalid("tlab_transpose: bad arguments");
         if (g_device < 0) throw HipError("tlab_init has not been called");
-        hip_check(launch_transpose(a, b, nra, nca, g_stream), "transpose");
+        hip_check(launch_transpose(a, b, nra, nca, tlab_current_stream()), "transpose");
     });
 }
 

@@ -15,9 +15,15 @@
 // The host's DNS_BOUNDS_LIMIT (time.f90:248-250; tlab_amd/fortran/dns_local_device.sed turns its loop into tlab_deferred_clip) sits between the DAXPYs
 // and the DSCALs: a clip of a recorded s after its DAXPY is recorded too and becomes the driver's bounds for the one fused call.
 //
-// What makes it safe: every launch of the library fetches its stream through tlab_current_stream(), which flushes first; tlab_sync, the copies and
-// tlab_free flush as well.  What it cannot see: a host statement that reads a device array directly (hipMalloc memory is host-addressable on
-// MI355X): such a host calls tlab_deferred_flush() or tlab_sync() first, or keeps the layer off (the default).
+// What makes it safe: every launch of the library fetches its stream through tlab_current_stream(), which flushes first -- the stream itself is private
+// to that accessor and tlab_set_stream (csrc/capi.cpp), so no launch can be written that takes it another way.  The public operators, tlab_sync, the
+// copies, tlab_free and the *_destroy functions flush as their first statement (before they size a work array or free what a record still names), and
+// so do the setters whose state a substep reads (the drivers' tlab_*_set_*, tlab_opr_burgers_set_*, tlab_fdm_plan_set_scheme / _set_stagger,
+// tlab_force_kernel_path, tlab_set_tuning): the record runs with the state it was recorded under.  Launches made from INSIDE a replay (the drivers call
+// the operators and the tlab_internal_* fused variants) come through the same accessor: g_busy makes the flush return at once there.
+// tests/deferred_entry_points.py holds one row per entry point of the header; tests/test_gpu_deferred_entry_points.py runs them with a record pending.
+// What it cannot see: a host statement that reads a device array directly (hipMalloc memory is host-addressable on MI355X): such a host calls
+// tlab_deferred_flush() or tlab_sync() first, or keeps the layer off (the default).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -206,7 +212,7 @@ int flush_impl(bool whole_ok = true) {
 }
 }      // namespace
 
-// capi.cpp: tlab_current_stream(), tlab_sync, the copies, tlab_free, tlab_set_stream
+// every entry point that flushes: tlab_current_stream(), the operators and setters of capi.cpp, tlab_sync, the copies, tlab_free, tlab_set_stream, ...
 // A recorded substep that runs because some OTHER entry point wanted the stream (the hook in tlab_current_stream()) has no caller to report a failure to:
 // the code is kept and handed to the next tlab_sync / tlab_deferred_* call (the error text stays in tlab_last_error()).
 static int g_sticky = TLAB_OK;

@@ -239,6 +239,7 @@ int tlab_filter_create(tlab_filter_t *out, int type, int size, int periodic, int
 }
 
 int tlab_filter_destroy(tlab_filter_t f) {
+    (void)tlab_internal_deferred_flush();      // (a recorded substep may still filter with it)
     if (f) tlab_internal_dealiasing_forget(f);      // (a [PressureFilter] of a live tlab_dns must be taken out by its owner first: tlab_dns_set_pressure_filter)
     delete f;
     return TLAB_OK;

@@ -785,6 +785,7 @@ int tlab_poisson_plan_create_direct_decomposed(tlab_poisson_plan_t *out, tlab_fd
 }
 
 int tlab_poisson_plan_destroy(tlab_poisson_plan_t p) {
+    (void)tlab_internal_deferred_flush();      // (a recorded substep may still solve with it)
     delete p;
     return TLAB_OK;
 }

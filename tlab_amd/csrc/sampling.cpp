@@ -253,12 +253,14 @@ int tlab_tower_create(tlab_tower_t *out, int nx, int ny, int nz, const int *stri
 }
 
 int tlab_tower_destroy(tlab_tower_t t) {
+    (void)tlab_internal_deferred_flush();      // (a recorded RHS of a driver armed with this tower still samples into it)
     if (t && t->dpos && tlab_device_ready()) (void)hipStreamSynchronize(tlab_current_stream());      // (a gather may still read the positions)
     delete t;
     return TLAB_OK;
 }
 
 int tlab_tower_sizes(tlab_tower_t t, long long *sizes) {
+    (void)tlab_internal_deferred_flush();      // (tower_accumulation and tower_mode_check are advanced by a recorded RHS that was armed)
     return catch_fail([&] {
         if (!t || !sizes) throw Fail(TLAB_EINVAL, "tlab_tower_sizes: a null pointer");
         const long long s[8] = {t->ti(), t->tj(), t->tk(), t->acc_field, t->acc_mean, t->bufsize(), t->accumulation, t->mode_check};
@@ -275,6 +277,7 @@ int tlab_tower_positions(tlab_tower_t t, int dir, int *pos) {
 }
 
 int tlab_tower_reset(tlab_tower_t t) {
+    (void)tlab_internal_deferred_flush();      // (a recorded RHS that was armed stores its sample in the slot of before)
     return catch_fail([&] {
         if (!t) throw Fail(TLAB_EINVAL, "tlab_tower_reset: a null handle");
         t->accumulation = 1;      // dns_tower.f90:486 (the end of DNS_TOWER_WRITE)

@@ -564,6 +564,7 @@ int tlab_zslab_plan_create(tlab_zslab_plan_t *out, tlab_fdm_plan_t gz, int kmax,
 }
 
 int tlab_zslab_plan_destroy(tlab_zslab_plan_t p) {
+    (void)tlab_internal_deferred_flush();      // (a recorded substep may still need the plan)
     delete p;
     return TLAB_OK;
 }

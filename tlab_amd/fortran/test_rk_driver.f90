@@ -205,6 +205,7 @@ program test_rk_driver
     use TLabMPI_Transpose
     use TLab_AMD_C, only: tlab_sync, tlab_memcpy_d2h, TLab_AMD_Check, tlab_time_courant, tlab_deferred_stats
     use TLab_AMD_Monitors, only: TLab_AMD_Courant, TLab_AMD_Dilatation
+    use OPR_Partial, only: OPR_Partial_X, OPR_P1
     use, intrinsic :: iso_c_binding
     implicit none
 
@@ -238,6 +239,12 @@ program test_rk_driver
     integer mon_stat, dil_imn(3), dil_imx(3)
     character(len=16) mon_env
     real(wp) mon_pmax(2), dil_min, dil_max, mm(4)
+    ! TLAB_AMD_PROBE_OPERATOR=1: an operator call of the host straight after every TIME_RUNGEKUTTA(), where the last substep of the step is still only
+    ! recorded (DNS_BOUNDS_CONTROL -> FI_INVARIANT_P -> OPR_Partial_X, dns_main.f90:269): d/dx of the new u, without a sync in front, one log line each
+    logical probe
+    integer probe_stat
+    integer(wi) probe_bcs(2, 2)
+    character(len=16) probe_env
 
     ! ###################################################################
     call TLab_Start()                                                          ! dns_main.f90:62
@@ -360,6 +367,9 @@ program test_rk_driver
     if (timing_stat /= 0) warm_iters = -1
     call get_environment_variable('TLAB_AMD_MONITORS', mon_env, status=mon_stat)
     monitors = mon_stat == 0 .and. trim(mon_env) == '1'
+    call get_environment_variable('TLAB_AMD_PROBE_OPERATOR', probe_env, status=probe_stat)
+    probe = probe_stat == 0 .and. trim(probe_env) == '1'
+    probe_bcs = 0
     do while (itime < nitera_last)                                             ! :246-250
         if (warm_iters >= 0 .and. itime == nitera_first + warm_iters) then
             call TLab_AMD_Check(tlab_sync(), 'tlab_sync')
@@ -375,6 +385,14 @@ program test_rk_driver
         call TIME_RUNGEKUTTA()
         itime = itime + 1
         rtime = rtime + dtime
+        if (probe) then
+            call OPR_Partial_X(OPR_P1, imax, jmax, kmax, probe_bcs, g(1), q(:, 1), txc(:, 1))
+            allocate (h1(isize_field))
+            call TLab_AMD_Check(tlab_memcpy_d2h(c_loc(h1), c_loc(txc(1, 1)), int(isize_field, c_size_t)*8_c_size_t), 'd2h')
+            write (sRes, '(a,i0,2(a,es23.16))') 'PROBE: itime ', itime, ' sum ', sum(abs(h1)), ' max ', maxval(abs(h1))
+            call TLab_Write_ASCII(lfile, trim(sRes))
+            deallocate (h1)
+        end if
         if (monitors) then
             call TLab_AMD_Courant(mon_pmax)
             call TLab_AMD_Dilatation(dil_min, dil_max, dil_imn, dil_imx)
