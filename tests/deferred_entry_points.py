@@ -13,7 +13,7 @@ the cases of tests/test_gpu_deferred_entry_points.py.
 STREAM, SETTER, DEFERRED, LIFETIME, HOST, DECOMPOSED = "stream", "setter", "deferred", "lifetime", "host", "decomposed"
 
 ENTRY_POINTS = {
-    # ---- runtime (csrc/capi.cpp)
+    # ---- runtime (csrc/runtime.cpp)
     "tlab_init": LIFETIME,
     "tlab_device_count": HOST,
     "tlab_finalize": LIFETIME,                       # tlab_deferred_enable(0) first: runs what is recorded

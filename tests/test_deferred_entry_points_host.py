@@ -6,7 +6,7 @@ from test_capi_symbols import declared_symbols
 from test_gpu_deferred_entry_points import CASES
 
 CLASSES = {E.STREAM, E.SETTER, E.DEFERRED, E.LIFETIME, E.HOST, E.DECOMPOSED}
-# the operator entry points of csrc/capi.cpp that used to take the stream without a flush
+# the operator entry points of csrc/operators.cpp that used to take the stream without a flush
 CAPI = ["tlab_opr_partial", "tlab_opr_partial_add", "tlab_opr_burgers", "tlab_opr_burgers_add", "tlab_opr_burgers_add_n", "tlab_opr_gradient_final",
         "tlab_boundary_bcs_neumann_y", "tlab_transpose"]
 ALWAYS_EXERCISED = ["tlab_device_minmax", "tlab_time_courant", "tlab_dns_dilatation_extremes", "tlab_dns_pressure", "tlab_dns_diagnostic", "tlab_dns_filter",

@@ -1,6 +1,6 @@
 """Every public entry point that enqueues work, or that changes what a substep reads, called through RAW ctypes while the last substep of a step is
 still only recorded by the deferred tail (csrc/deferred.cpp): the record must run first, whole, as ONE fused substep.  The Python wrappers of
-tlab_amd.operators hand the library torch's stream before every call, and that call flushes -- which is how the operators of csrc/capi.cpp could take the
+tlab_amd.operators hand the library torch's stream before every call, and that call flushes -- which is how the operators of csrc/operators.cpp could take the
 stream without a flush and no test saw it.  A Fortran host goes straight to the C ABI, as the calls here do; nothing in this file hands the library a
 stream, and the wrappers' helper is made to raise while a case runs.
 
@@ -80,7 +80,7 @@ def host(out, n, value=0.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# csrc/capi.cpp: the operators
+# csrc/operators.cpp: the operators
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 def _partial(dir, type, u, tmp=False):
     def call(L, d, out):

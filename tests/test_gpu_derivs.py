@@ -316,7 +316,7 @@ def test_full_size_properties(T, n):
 
 def test_x_lines_of_2048_take_the_wave_per_line_kernel(T):
     """BASELINE configs[4]: x lines of 2048 points.  32 rows per lane; the lane-variant tables (164 KB as doubles for the two systems) are
-    kept as chunk 0's value + a float difference, which the plan verifies to be exact on the host (capi.cpp xline_wide_ok).  All operator
+    kept as chunk 0's value + a float difference, which the plan verifies to be exact on the host (operators.cpp xline_wide_ok).  All operator
     types against the oracle; a non-periodic x of 2048 points (not compressible) still takes the generic kernel."""
     import torch
     from oracle import tlab_oracle as O

@@ -6,7 +6,7 @@ error <= 1e-12 (BASELINE.json north_star).
 With the tables of a uniform grid the cyclic system is circulant, and a kernel that reads another chunk's rows, transposes the dense separator
 inverse or reverses the lane order of its per-lane tables computes the same numbers; on `varying` tables it is wrong by 1e-1 (tests/
 test_periodic_tables_host.py).  The table content also decides which kernel variant runs, so every case asserts the variant it reached, the
-expectation read off the dispatch rules (capi.cpp xline_chunks / xline_wide_ok / tlab_fdm_plan::system, kernels.hip launch_xline, htile.hip
+expectation read off the dispatch rules (operators.cpp xline_chunks / xline_wide_ok, fdm_plan.cpp tlab_fdm_plan::system, kernels.hip launch_xline, htile.hip
 ptile_ok), not off the run:
 
  x lines   n     equal                                wander                               varying
@@ -132,7 +132,7 @@ def profiled(L, fn):
 # what the dispatch rules say
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 def x_expectation(n, kind):
-    """(chunks = tlab_fdm_plan_info 8, lane-invariant = info 9, kernel path) of periodic x lines (capi.cpp xline_chunks): 256 / 512 points: one wave
+    """(chunks = tlab_fdm_plan_info 8, lane-invariant = info 9, kernel path) of periodic x lines (operators.cpp xline_chunks): 256 / 512 points: one wave
     per line whatever the tables; 1024 / 2048: 2 / 4 waves while the tables can be kept as chunk 0 + float differences -- rows equal to the bit or
     apart by rounding (1e-13: the difference has about 10 significant bits), not rows 5 % apart --, else one wave at 1024 points and the generic
     kernel at 2048.  Lane-invariant: every row bit-identical (info 9 answers 0 where there are no chunks)."""
@@ -141,7 +141,7 @@ def x_expectation(n, kind):
 
 
 def z_expectation(op, n, lines, kind, policy):
-    """kernel names a z-line operator must launch under tlab_set_tuning(2, policy) (capi.cpp tlab_opr_partial / tlab_opr_burgers / run_p1_tile,
+    """kernel names a z-line operator must launch under tlab_set_tuning(2, policy) (operators.cpp tlab_opr_partial / tlab_opr_burgers / run_p1_tile,
     htile.hip launch_htile_m / ptile_ok)"""
     tile = 16 if n == 1024 else 32                   # Burgers tiles: 16 lines at 1024 points (32 chunks of 32 rows)
     ptile = policy == 2 and kind == "equal" and n in (512, 1024) and lines % tile == 0

@@ -20,18 +20,15 @@
 
 #include "../../include/tlab_amd.h"
 #include "../../include/tlab_amd_comm.h"
-#include "internal.hpp"      // tlab_current_stream, tlab_set_error, tlab_device_ready of libtlab_amd.so
+#include "errors.hpp"        // Fail, hk, catch_fail -- with tlab_set_error and tlab_device_ready of libtlab_amd.so
+#include "internal.hpp"      // tlab_current_stream of libtlab_amd.so
 
+using tlab::catch_fail;
+using tlab::Fail;
+using tlab::hk;
 
 namespace {
 
-struct Fail {
-    int code;
-    std::string msg;
-};
-void hipc(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw Fail{TLAB_EHIP, std::string(what) + ": " + hipGetErrorString(e)};
-}
 void ncc(ncclResult_t r, const char *what) {
     if (r != ncclSuccess) throw Fail{TLAB_EHIP, std::string(what) + ": " + ncclGetErrorString(r)};
 }
@@ -112,7 +109,7 @@ void copy_strided(const tlab_trp_plan *p, double *S, double *W, int to_wire, hip
     const int grid = (int)std::min<long long>(4096, std::max<long long>(1, (work + 255) / 256));
     if (vec) hipLaunchKernelGGL(k_trp_copy<2>, dim3(grid), dim3(256), 0, st, S, W, p->m, p->P, p->c, to_wire);
     else hipLaunchKernelGGL(k_trp_copy<1>, dim3(grid), dim3(256), 0, st, S, W, p->m, p->P, p->c, to_wire);
-    hipc(hipGetLastError(), "k_trp_copy");
+    hk(hipGetLastError(), "k_trp_copy");
 }
 bool strided_on_send(const tlab_trp_plan *p, int forward) { return (p->dir == 1 && !forward) || (p->dir == 3 && forward); }
 void copy_f32(const tlab_trp_plan *p, double *S, float *W, int to_wire, int strided, hipStream_t st) {
@@ -122,12 +119,7 @@ void copy_f32(const tlab_trp_plan *p, double *S, float *W, int to_wire, int stri
     const int grid = (int)std::min<long long>(4096, std::max<long long>(1, (work + 255) / 256));
     if (vec) hipLaunchKernelGGL(k_trp_copy_f32<2>, dim3(grid), dim3(256), 0, st, S, W, p->m, p->P, p->c, to_wire, strided);
     else hipLaunchKernelGGL(k_trp_copy_f32<1>, dim3(grid), dim3(256), 0, st, S, W, p->m, p->P, p->c, to_wire, strided);
-    hipc(hipGetLastError(), "k_trp_copy_f32");
-}
-
-int guard(const Fail &f) {
-    tlab_set_error(f.msg);
-    return f.code;
+    hk(hipGetLastError(), "k_trp_copy_f32");
 }
 
 }  // namespace
@@ -144,17 +136,17 @@ int slab_begin(tlab_comm *c, hipStream_t cur) {
     const int t = c->next_ticket;
     c->next_ticket = (t + 1) % tlab_comm::NEV;
     if (!c->ev_start[t]) {
-        hipc(hipEventCreateWithFlags(&c->ev_start[t], hipEventDisableTiming), "hipEventCreate");
-        hipc(hipEventCreateWithFlags(&c->ev_done[t], hipEventDisableTiming), "hipEventCreate");
+        hk(hipEventCreateWithFlags(&c->ev_start[t], hipEventDisableTiming), "hipEventCreate");
+        hk(hipEventCreateWithFlags(&c->ev_done[t], hipEventDisableTiming), "hipEventCreate");
     }
-    hipc(hipEventRecord(c->ev_start[t], cur), "hipEventRecord");
-    hipc(hipStreamWaitEvent(c->stream, c->ev_start[t], 0), "hipStreamWaitEvent");
+    hk(hipEventRecord(c->ev_start[t], cur), "hipEventRecord");
+    hk(hipStreamWaitEvent(c->stream, c->ev_start[t], 0), "hipStreamWaitEvent");
     return t;
 }
 
 int slab_ring_start(void *ctx, void *stream, int nmsg, const long long *count, double *const *to_left, double *const *to_right, double *const *from_right,
                     double *const *from_left) {
-    try {
+    return catch_fail([&]() -> int {
         tlab_comm *c = static_cast<tlab_comm *>(ctx);
         const int P = c->npro_k, me = c->pro_k, left = (me + P - 1) % P, right = (me + 1) % P;
         const int t = slab_begin(c, (hipStream_t)stream);
@@ -168,16 +160,13 @@ int slab_ring_start(void *ctx, void *stream, int nmsg, const long long *count, d
         const ncclResult_t e = ncclGroupEnd();
         ncc(r, "ncclSend / ncclRecv (ring)");
         ncc(e, "ncclGroupEnd");
-        hipc(hipEventRecord(c->ev_done[t], c->stream), "hipEventRecord");
+        hk(hipEventRecord(c->ev_done[t], c->stream), "hipEventRecord");
         return t;
-    } catch (const Fail &f) {
-        tlab_set_error(f.msg);
-        return f.code;
-    }
+    }, TLAB_EINVAL);
 }
 
 int slab_alltoallv_start(void *ctx, void *stream, double *const *send, const long long *scount, double *const *recv, const long long *rcount) {
-    try {
+    return catch_fail([&]() -> int {
         tlab_comm *c = static_cast<tlab_comm *>(ctx);
         const int P = c->npro_k, me = c->pro_k;
         const int t = slab_begin(c, (hipStream_t)stream);
@@ -199,46 +188,37 @@ int slab_alltoallv_start(void *ctx, void *stream, double *const *send, const lon
         ncc(e, "ncclGroupEnd");
         if (scount[me] != rcount[me]) throw Fail{TLAB_EINVAL, "slab transport: own block sizes differ"};
         if (scount[me] > 0)
-            hipc(hipMemcpyAsync(recv[0] + my_ro, send[0] + my_so, (size_t)scount[me] * sizeof(double), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync (own block)");
-        hipc(hipEventRecord(c->ev_done[t], c->stream), "hipEventRecord");
+            hk(hipMemcpyAsync(recv[0] + my_ro, send[0] + my_so, (size_t)scount[me] * sizeof(double), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync (own block)");
+        hk(hipEventRecord(c->ev_done[t], c->stream), "hipEventRecord");
         return t;
-    } catch (const Fail &f) {
-        tlab_set_error(f.msg);
-        return f.code;
-    }
+    }, TLAB_EINVAL);
 }
 
 int slab_wait(void *ctx, void *stream, int ticket) {
-    try {
+    return catch_fail([&]() -> int {
         tlab_comm *c = static_cast<tlab_comm *>(ctx);
         if (ticket < 0 || ticket >= tlab_comm::NEV || !c->ev_done[ticket]) throw Fail{TLAB_EINVAL, "slab transport: unknown ticket"};
-        hipc(hipStreamWaitEvent((hipStream_t)stream, c->ev_done[ticket], 0), "hipStreamWaitEvent");
+        hk(hipStreamWaitEvent((hipStream_t)stream, c->ev_done[ticket], 0), "hipStreamWaitEvent");
         return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.msg);
-        return f.code;
-    }
+    }, TLAB_EINVAL);
 }
 
 int slab_allreduce(void *ctx, double *values, int n, int op) {
-    try {
+    return catch_fail([&]() -> int {
         tlab_comm *c = static_cast<tlab_comm *>(ctx);
         if (n < 1 || n > 64) throw Fail{TLAB_EINVAL, "slab transport: all-reduce of 1..64 values"};
-        if (!c->red) hipc(hipMalloc((void **)&c->red, 64 * sizeof(double)), "hipMalloc");
+        if (!c->red) hk(hipMalloc((void **)&c->red, 64 * sizeof(double)), "hipMalloc");
         // on the communication stream like every other operation of this communicator (one stream per communicator: no ordering left to RCCL),
         // behind the work enqueued on the caller's stream so far
         hipStream_t cur = tlab_current_stream(), cs = c->stream;
         const int t = slab_begin(c, cur);
-        hipc(hipMemcpyAsync(c->red, values, (size_t)n * sizeof(double), hipMemcpyHostToDevice, cs), "hipMemcpyAsync");
+        hk(hipMemcpyAsync(c->red, values, (size_t)n * sizeof(double), hipMemcpyHostToDevice, cs), "hipMemcpyAsync");
         ncc(ncclAllReduce(c->red, c->red, (size_t)n, ncclDouble, op == 0 ? ncclMax : (op == 1 ? ncclMin : ncclSum), zcomm(c), cs), "ncclAllReduce");
-        hipc(hipMemcpyAsync(values, c->red, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
-        hipc(hipEventRecord(c->ev_done[t], cs), "hipEventRecord");
-        hipc(hipStreamSynchronize(cs), "hipStreamSynchronize");
+        hk(hipMemcpyAsync(values, c->red, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, cs), "hipMemcpyAsync");
+        hk(hipEventRecord(c->ev_done[t], cs), "hipEventRecord");
+        hk(hipStreamSynchronize(cs), "hipStreamSynchronize");
         return TLAB_OK;
-    } catch (const Fail &f) {
-        tlab_set_error(f.msg);
-        return f.code;
-    }
+    }, TLAB_EINVAL);
 }
 
 }  // namespace
@@ -260,7 +240,7 @@ int tlab_comm_slab_transport(tlab_comm_t c, tlab_slab_transport *out) {
 // the caller's stream by events like the slab transport (same tickets, same wait).
 namespace {
 int pencil_alltoallv_start(void *ctx, void *stream, int which, double *const *send, const long long *scount, double *const *recv, const long long *rcount) {
-    try {
+    return catch_fail([&]() -> int {
         tlab_comm *c = static_cast<tlab_comm *>(ctx);
         if (which < 0 || which > 2) throw Fail{TLAB_EINVAL, "pencil transport: communicator 0 (world), 1 (x) or 2 (z)"};
         ncclComm_t nc = which == 0 ? c->world : (which == 1 ? c->cx : c->cz);
@@ -287,13 +267,10 @@ int pencil_alltoallv_start(void *ctx, void *stream, int which, double *const *se
         ncc(e, "ncclGroupEnd");
         if (scount[me] != rcount[me]) throw Fail{TLAB_EINVAL, "pencil transport: own block sizes differ"};
         if (scount[me] > 0)
-            hipc(hipMemcpyAsync(recv[0] + my_ro, send[0] + my_so, (size_t)scount[me] * sizeof(double), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync (own block)");
-        hipc(hipEventRecord(c->ev_done[t], c->stream), "hipEventRecord");
+            hk(hipMemcpyAsync(recv[0] + my_ro, send[0] + my_so, (size_t)scount[me] * sizeof(double), hipMemcpyDeviceToDevice, c->stream), "hipMemcpyAsync (own block)");
+        hk(hipEventRecord(c->ev_done[t], c->stream), "hipEventRecord");
         return t;
-    } catch (const Fail &f) {
-        tlab_set_error(f.msg);
-        return f.code;
-    }
+    }, TLAB_EINVAL);
 }
 }  // namespace
 
@@ -307,18 +284,18 @@ int tlab_comm_pencil_transport(tlab_comm_t c, tlab_pencil_transport *out) {
 }
 
 int tlab_comm_get_unique_id(void *id_bytes) {
-    try {
+    return catch_fail([&]() -> int {
         if (!id_bytes) throw Fail{TLAB_EINVAL, "tlab_comm_get_unique_id: null buffer"};
         static_assert(sizeof(ncclUniqueId) == TLAB_COMM_ID_BYTES, "ncclUniqueId size");
         ncclUniqueId id;
         ncc(ncclGetUniqueId(&id), "ncclGetUniqueId");
         std::memcpy(id_bytes, &id, sizeof(id));
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_comm_init(tlab_comm_t *out, const void *id_bytes, int nranks, int rank, int npro_i, int npro_k) {
-    try {
+    return catch_fail([&]() -> int {
         if (!out || !id_bytes) throw Fail{TLAB_EINVAL, "tlab_comm_init: null argument"};
         if (!tlab_device_ready()) throw Fail{TLAB_EHIP, "tlab_comm_init: tlab_init has not been called"};
         if (nranks < 1 || rank < 0 || rank >= nranks || npro_i < 1 || npro_k < 1 || npro_i * npro_k != nranks)
@@ -333,10 +310,10 @@ int tlab_comm_init(tlab_comm_t *out, const void *id_bytes, int nranks, int rank,
         // ims_comm_x: equal ims_pro_k, ordered by ims_pro_i ; ims_comm_z: equal ims_pro_i, ordered by ims_pro_k
         if (npro_i > 1) ncc(ncclCommSplit(c->world, c->pro_k, c->pro_i, &c->cx, nullptr), "ncclCommSplit (x)");
         if (npro_k > 1) ncc(ncclCommSplit(c->world, c->pro_i, c->pro_k, &c->cz, nullptr), "ncclCommSplit (z)");
-        hipc(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
+        hk(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), "hipStreamCreate");
         *out = c;
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_comm_destroy(tlab_comm_t c) {
@@ -372,15 +349,15 @@ int tlab_comm_info(tlab_comm_t c, int what) {
 }
 
 int tlab_comm_allreduce_max(tlab_comm_t c, double *v, int n) {
-    try {
+    return catch_fail([&]() -> int {
         if (!c || !v || n < 1) throw Fail{TLAB_EINVAL, "tlab_comm_allreduce_max: bad arguments"};
         if (c->nranks > 1) ncc(ncclAllReduce(v, v, (size_t)n, ncclDouble, ncclMax, c->world, tlab_current_stream()), "ncclAllReduce");
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_plan_create(tlab_trp_plan_t *out, tlab_comm_t comm, int dir, int nmax, int npage, int elem_doubles, int rank_dir, int npro_dir) {
-    try {
+    return catch_fail([&]() -> int {
         if (!out) throw Fail{TLAB_EINVAL, "tlab_trp_plan_create: null argument"};
         if (!tlab_device_ready()) throw Fail{TLAB_EHIP, "tlab_trp_plan_create: tlab_init has not been called"};
         if ((dir != 1 && dir != 3) || nmax < 1 || npage < 1 || (elem_doubles != 1 && elem_doubles != 2))
@@ -395,7 +372,7 @@ int tlab_trp_plan_create(tlab_trp_plan_t *out, tlab_comm_t comm, int dir, int nm
         } else {
             if (npro_dir < 1 || rank_dir < 0 || rank_dir >= npro_dir) { delete p; throw Fail{TLAB_EINVAL, "tlab_trp_plan_create: rank_dir of npro_dir"}; }
             p->P = npro_dir; p->rank = rank_dir;
-            hipc(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking), "hipStreamCreate");
+            hk(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking), "hipStreamCreate");
             p->own_stream = true;
         }
         if (npage % p->P != 0) {               // tlab_mpi_transpose.f90:223, :292
@@ -407,12 +384,12 @@ int tlab_trp_plan_create(tlab_trp_plan_t *out, tlab_comm_t comm, int dir, int nm
         else { p->m = p->nlines * p->e; p->c = nmax; }
         p->blk = p->m * p->c;
         p->local = p->blk * p->P;
-        hipc(hipMalloc((void **)&p->stage, (size_t)p->local * sizeof(double)), "hipMalloc (staging buffer)");
-        hipc(hipEventCreateWithFlags(&p->ev_ready, hipEventDisableTiming), "hipEventCreate");
-        hipc(hipEventCreateWithFlags(&p->ev_done, hipEventDisableTiming), "hipEventCreate");
+        hk(hipMalloc((void **)&p->stage, (size_t)p->local * sizeof(double)), "hipMalloc (staging buffer)");
+        hk(hipEventCreateWithFlags(&p->ev_ready, hipEventDisableTiming), "hipEventCreate");
+        hk(hipEventCreateWithFlags(&p->ev_done, hipEventDisableTiming), "hipEventCreate");
         *out = p;
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_plan_destroy(tlab_trp_plan_t p) {
@@ -427,13 +404,13 @@ int tlab_trp_plan_destroy(tlab_trp_plan_t p) {
 }
 
 int tlab_trp_plan_set_wire(tlab_trp_plan_t p, int single) {
-    try {
+    return catch_fail([&]() -> int {
         if (!p) throw Fail{TLAB_EINVAL, "tlab_trp_plan_set_wire: null plan"};
         if (p->pending) throw Fail{TLAB_EINVAL, "tlab_trp_plan_set_wire: a transposition of this plan is in flight"};
         if (single && p->e != 1) throw Fail{TLAB_EUNSUPPORTED, "tlab_trp_plan_set_wire: complex plans always travel in double precision (tlab_mpi_transpose.f90:386-399)"};
         p->single = single != 0;
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_plan_info(tlab_trp_plan_t p, int what) {
@@ -450,29 +427,29 @@ int tlab_trp_plan_info(tlab_trp_plan_t p, int what) {
 }
 
 int tlab_trp_pack(tlab_trp_plan_t p, int forward, const double *in, double *sendbuf) {
-    try {
+    return catch_fail([&]() -> int {
         if (!p || !in || !sendbuf || in == sendbuf) throw Fail{TLAB_EINVAL, "tlab_trp_pack: bad arguments"};
         hipStream_t st = tlab_current_stream();
         if (p->single) copy_f32(p, const_cast<double *>(in), reinterpret_cast<float *>(sendbuf), 1, strided_on_send(p, forward) ? 1 : 0, st);
         else if (strided_on_send(p, forward)) copy_strided(p, const_cast<double *>(in), sendbuf, 1, st);
-        else hipc(hipMemcpyAsync(sendbuf, in, (size_t)p->local * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+        else hk(hipMemcpyAsync(sendbuf, in, (size_t)p->local * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_unpack(tlab_trp_plan_t p, int forward, const double *recvbuf, double *out) {
-    try {
+    return catch_fail([&]() -> int {
         if (!p || !recvbuf || !out || recvbuf == out) throw Fail{TLAB_EINVAL, "tlab_trp_unpack: bad arguments"};
         hipStream_t st = tlab_current_stream();
         if (p->single) copy_f32(p, out, reinterpret_cast<float *>(const_cast<double *>(recvbuf)), 0, strided_on_send(p, forward) ? 0 : 1, st);
         else if (!strided_on_send(p, forward)) copy_strided(p, out, const_cast<double *>(recvbuf), 0, st);
-        else hipc(hipMemcpyAsync(out, recvbuf, (size_t)p->local * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+        else hk(hipMemcpyAsync(out, recvbuf, (size_t)p->local * sizeof(double), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_start(tlab_trp_plan_t p, int forward, const double *in, double *out) {
-    try {
+    return catch_fail([&]() -> int {
         if (!p || !in || !out || in == out) throw Fail{TLAB_EINVAL, "tlab_trp_start: bad arguments (in and out must differ)"};
         if (p->pending) throw Fail{TLAB_EINVAL, "tlab_trp_start: a transposition of this plan is still in flight (tlab_trp_wait)"};
         if (p->P > 1 && !p->nc) throw Fail{TLAB_EINVAL, "tlab_trp_start: the plan has no communicator (use tlab_trp_pack / tlab_trp_unpack)"};
@@ -484,9 +461,9 @@ int tlab_trp_start(tlab_trp_plan_t p, int forward, const double *in, double *out
             // whole array before the exchange (tlab_mpi_transpose.f90:362-371).
             float *sf = reinterpret_cast<float *>(p->stage), *rf = sf + p->local;
             copy_f32(p, const_cast<double *>(in), sf, 1, pack ? 1 : 0, cur);
-            hipc(hipEventRecord(p->ev_ready, cur), "hipEventRecord");
-            hipc(hipStreamWaitEvent(cs, p->ev_ready, 0), "hipStreamWaitEvent");
-            hipc(hipMemcpyAsync(rf + (size_t)p->rank * p->blk, sf + (size_t)p->rank * p->blk, (size_t)p->blk * sizeof(float), hipMemcpyDeviceToDevice, cs),
+            hk(hipEventRecord(p->ev_ready, cur), "hipEventRecord");
+            hk(hipStreamWaitEvent(cs, p->ev_ready, 0), "hipStreamWaitEvent");
+            hk(hipMemcpyAsync(rf + (size_t)p->rank * p->blk, sf + (size_t)p->rank * p->blk, (size_t)p->blk * sizeof(float), hipMemcpyDeviceToDevice, cs),
                  "hipMemcpyAsync (own block)");
             if (p->P > 1) {
                 ncc(ncclGroupStart(), "ncclGroupStart");
@@ -500,7 +477,7 @@ int tlab_trp_start(tlab_trp_plan_t p, int forward, const double *in, double *out
                 ncc(r, "ncclSend / ncclRecv");
                 ncc(e, "ncclGroupEnd");
             }
-            hipc(hipEventRecord(p->ev_done, cs), "hipEventRecord");
+            hk(hipEventRecord(p->ev_done, cs), "hipEventRecord");
             p->pending = true; p->pending_unpack = !pack; p->pending_out = out;
             return TLAB_OK;
         }
@@ -508,10 +485,10 @@ int tlab_trp_start(tlab_trp_plan_t p, int forward, const double *in, double *out
         double *dst = out;            // blocked by peer
         if (pack) { copy_strided(p, const_cast<double *>(in), p->stage, 1, cur); src = p->stage; }
         else dst = p->stage;
-        hipc(hipEventRecord(p->ev_ready, cur), "hipEventRecord");          // in (and the packed copy) are ready; earlier readers of out are done
-        hipc(hipStreamWaitEvent(cs, p->ev_ready, 0), "hipStreamWaitEvent");
+        hk(hipEventRecord(p->ev_ready, cur), "hipEventRecord");          // in (and the packed copy) are ready; earlier readers of out are done
+        hk(hipStreamWaitEvent(cs, p->ev_ready, 0), "hipStreamWaitEvent");
         const size_t bytes = (size_t)p->blk * sizeof(double);
-        hipc(hipMemcpyAsync(dst + (size_t)p->rank * p->blk, src + (size_t)p->rank * p->blk, bytes, hipMemcpyDeviceToDevice, cs), "hipMemcpyAsync (own block)");
+        hk(hipMemcpyAsync(dst + (size_t)p->rank * p->blk, src + (size_t)p->rank * p->blk, bytes, hipMemcpyDeviceToDevice, cs), "hipMemcpyAsync (own block)");
         if (p->P > 1) {
             ncc(ncclGroupStart(), "ncclGroupStart");
             ncclResult_t r = ncclSuccess;
@@ -524,23 +501,23 @@ int tlab_trp_start(tlab_trp_plan_t p, int forward, const double *in, double *out
             ncc(r, "ncclSend / ncclRecv");
             ncc(e, "ncclGroupEnd");
         }
-        hipc(hipEventRecord(p->ev_done, cs), "hipEventRecord");
+        hk(hipEventRecord(p->ev_done, cs), "hipEventRecord");
         p->pending = true; p->pending_unpack = !pack; p->pending_out = out;
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_wait(tlab_trp_plan_t p) {
-    try {
+    return catch_fail([&]() -> int {
         if (!p) throw Fail{TLAB_EINVAL, "tlab_trp_wait: null plan"};
         if (!p->pending) return TLAB_OK;
         hipStream_t cur = tlab_current_stream();
-        hipc(hipStreamWaitEvent(cur, p->ev_done, 0), "hipStreamWaitEvent");
+        hk(hipStreamWaitEvent(cur, p->ev_done, 0), "hipStreamWaitEvent");
         if (p->single) copy_f32(p, p->pending_out, reinterpret_cast<float *>(p->stage) + p->local, 0, p->pending_unpack ? 1 : 0, cur);
         else if (p->pending_unpack) copy_strided(p, p->pending_out, p->stage, 0, cur);
         p->pending = false;
         return TLAB_OK;
-    } catch (const Fail &f) { return guard(f); }
+    }, TLAB_EINVAL);
 }
 
 int tlab_trp_exec(tlab_trp_plan_t p, int forward, const double *in, double *out) {

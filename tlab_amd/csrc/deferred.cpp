@@ -16,7 +16,7 @@
 // and the DSCALs: a clip of a recorded s after its DAXPY is recorded too and becomes the driver's bounds for the one fused call.
 //
 // What makes it safe: every launch of the library fetches its stream through tlab_current_stream(), which flushes first -- the stream itself is private
-// to that accessor and tlab_set_stream (csrc/capi.cpp), so no launch can be written that takes it another way.  The public operators, tlab_sync, the
+// to that accessor and tlab_set_stream (csrc/runtime.cpp), so no launch can be written that takes it another way.  The public operators, tlab_sync, the
 // copies, tlab_free and the *_destroy functions flush as their first statement (before they size a work array or free what a record still names), and
 // so do the setters whose state a substep reads (the drivers' tlab_*_set_*, tlab_opr_burgers_set_*, tlab_fdm_plan_set_scheme / _set_stagger,
 // tlab_force_kernel_path, tlab_set_tuning): the record runs with the state it was recorded under.  Launches made from INSIDE a replay (the drivers call
@@ -212,7 +212,7 @@ int flush_impl(bool whole_ok = true) {
 }
 }      // namespace
 
-// every entry point that flushes: tlab_current_stream(), the operators and setters of capi.cpp, tlab_sync, the copies, tlab_free, tlab_set_stream, ...
+// every entry point that flushes: tlab_current_stream(), the operators and setters of operators.cpp and fdm_plan.cpp, tlab_sync, the copies, tlab_free, tlab_set_stream, ...
 // A recorded substep that runs because some OTHER entry point wanted the stream (the hook in tlab_current_stream()) has no caller to report a failure to:
 // the code is kept and handed to the next tlab_sync / tlab_deferred_* call (the error text stays in tlab_last_error()).
 static int g_sticky = TLAB_OK;
@@ -223,7 +223,7 @@ int tlab_internal_deferred_flush() {
     if (rc != TLAB_OK && g_sticky == TLAB_OK) g_sticky = rc;
     return rc;
 }
-int tlab_internal_deferred_take_error() {      // capi.cpp: tlab_sync
+int tlab_internal_deferred_take_error() {      // runtime.cpp: tlab_sync
     const int rc = g_sticky;
     g_sticky = TLAB_OK;
     return rc;

@@ -53,5 +53,12 @@ struct LineGeom {
     int lines_inner;        // number of lines contiguous in memory (X: 1 [lines are rows], Y: nx, Z: nx*ny)
     long long outer_stride; // elements between groups of lines_inner lines (Y: nx*ny; X: nx; Z: unused)
 };
+inline LineGeom line_geom(int dir, int nx, int ny, int nz) {
+    LineGeom g;
+    if (dir == 1) { g.n = nx; g.nlines = (long long)ny * nz; g.row_stride = 1; g.lines_inner = 1; g.outer_stride = nx; }
+    else if (dir == 2) { g.n = ny; g.nlines = (long long)nx * nz; g.row_stride = nx; g.lines_inner = nx; g.outer_stride = (long long)nx * ny; }
+    else { g.n = nz; g.nlines = (long long)nx * ny; g.row_stride = (long long)nx * ny; g.lines_inner = nx * ny; g.outer_stride = 0; }
+    return g;
+}
 
 }  // namespace tlab

@@ -36,7 +36,7 @@ int tlab_time_courant(tlab_dns_t d, double *const *q, double cfla, double cfld, 
         pmax[0] = mx;                                   // max of |u|/dx + |v|/dy + |w|/dz over the local box (time.f90:402-451)
         pmax[1] = d->schmidtfactor * d->dx2i;           // time.f90:466
         if (dtime && cfla > 0.0) *dtime = courant_dtime(cfla, cfld, pmax);      // (without a CFL number the caller's dtime stands)
-    });
+    }, TLAB_EINVAL);
 }
 
 int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const double *w, double *result, double *tmp1) {
@@ -52,7 +52,7 @@ int tlab_fi_invariant_p(tlab_dns_t d, const double *u, const double *v, const do
         ok(tlab_opr_partial(3, d->g[2], TLAB_OPR_P1, nx, ny, nz, 0, w, tmp1, nullptr), "OPR_Partial_Z");
         hk(launch_add1(result, tmp1, n, st), "add");
         hk(launch_negate(result, n, st), "negate");
-    });
+    }, TLAB_EINVAL);
 }
 
 // FI_VORTICITY (mappings/fi_vorticity.f90:28-59): the six derivatives in the reference's order, kept in txc6, then one pass over them
@@ -67,7 +67,7 @@ int tlab_fi_vorticity(tlab_dns_t d, const double *u, const double *v, const doub
         for (int i = 0; i < 6; ++i) ok(tlab_opr_partial(dir[i], d->g[dir[i] - 1], TLAB_OPR_P1, nx, ny, nz, 0, fld[i], txc6[i], nullptr), "OPR_Partial");
         hk(launch_vorticity_magnitude(txc6[0], txc6[1], txc6[2], txc6[3], txc6[4], txc6[5], result, (long long)nx * ny * nz, tlab_current_stream()),
            "k_vorticity_magnitude");
-    });
+    }, TLAB_EINVAL);
 }
 
 // ... and the pass on its own, for arrays of either kind (classified like tlab_minmax_any; a mix is refused)
@@ -118,7 +118,7 @@ int tlab_dns_avg_gradients_flow(tlab_dns_t d, double *const *q, const double *p,
             for (int dir = 1; dir <= 3; ++dir)
                 ok(tlab_opr_partial(dir, d->g[dir - 1], TLAB_OPR_P1, nx, ny, nz, 0, q[c], txc[3 * c + dir - 1], nullptr), "OPR_Partial");
         ok(tlab_avg_gradients_flow(nx, ny, nz, txc, q[0], q[1], q[2], p, fU, fV, fW, rP, rU_y, rV_y, rW_y, out, ldout), "tlab_avg_gradients_flow");
-    });
+    }, TLAB_EINVAL);
 }
 
 // ... and of one scalar (statistics/avg_scal_xz.f90:446-448, :602-604): dsdx, dsdy, dsdz = txc[0..2]
@@ -132,14 +132,14 @@ int tlab_dns_avg_gradients_scal(tlab_dns_t d, const double *s, double *const *q,
         const int nx = d->nx, ny = d->ny, nz = d->nz;
         for (int dir = 1; dir <= 3; ++dir) ok(tlab_opr_partial(dir, d->g[dir - 1], TLAB_OPR_P1, nx, ny, nz, 0, s, txc[dir - 1], nullptr), "OPR_Partial");
         ok(tlab_avg_gradients_scal(nx, ny, nz, txc, s, q[0], q[1], q[2], p, fS, fU, fV, fW, rP, rS_y, fS_y, out, ldout), "tlab_avg_gradients_scal");
-    });
+    }, TLAB_EINVAL);
 }
 
 int tlab_minmax(tlab_dns_t d, const double *a, int nx, int ny, int nz, double *amn, double *amx) {
     return catch_fail([&] {
         if (!d || !a || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_minmax: bad arguments");
         minmax_impl(d, a, nullptr, nullptr, 0, nx, ny, nz, amn, amx);
-    });
+    }, TLAB_EINVAL);
 }
 
 // DNS_BOUNDS_CONTROL (dns_local.f90:157-230), incompressible and anelastic: div(q) accumulated into txc[0] by the three P1 derivatives, then one
@@ -168,7 +168,7 @@ int tlab_dns_dilatation_extremes(tlab_dns_t d, double *const *q, double *const *
         };
         loc(imn, loc_min);
         loc(imx, loc_max);
-    });
+    }, TLAB_EINVAL);
 }
 
 // the TIME_COURANT maximum of a box (nx, ny, nz) at global offsets (ioff, koff), with this driver's tables (the decomposed drivers' monitors)
@@ -178,7 +178,7 @@ int tlab_internal_dns_courant(tlab_dns_t d, const double *u, const double *v, co
         hipStream_t st = tlab_current_stream();
         hk(monitor_courant_max(u, v, w, d->od[0], d->od[1], d->od[2], nx, ny, nz, ioff, koff, d->nz_total > 1 ? 1 : 0, &pmax[0], st), "k_courant");
         pmax[1] = d->schmidtfactor * d->dx2i;
-    });
+    }, TLAB_EINVAL);
 }
 
 // MINMAX (utils/minmax.f90:6), local part, of any device array: no driver needed
@@ -187,7 +187,7 @@ int tlab_device_minmax(const double *a, long long n, double *amn, double *amx) {
         if (!a || n < 1 || !amn || !amx) throw Fail(TLAB_EINVAL, "tlab_device_minmax: bad arguments");
         if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
         hk(monitor_extremes(a, nullptr, n, amn, amx, nullptr, nullptr, tlab_current_stream()), "k_extremes");
-    });
+    }, TLAB_EINVAL);
 }
 
 // ... of an array of either kind (the drop-in MINMAX): device memory takes the kernel, host memory the host loop of minmax.f90 -- a host array

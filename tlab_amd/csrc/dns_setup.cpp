@@ -144,7 +144,7 @@ int tlab_dns_create(tlab_dns_t *out, tlab_fdm_plan_t gx, tlab_fdm_plan_t gy, tla
         }
         hk(hipMalloc((void **)&d->part, (size_t)2 * 1024 * sizeof(double)), "hipMalloc");
         *out = d.release();
-    });
+    }, TLAB_EINVAL);
 }
 
 int tlab_dns_destroy(tlab_dns_t d) {
@@ -196,7 +196,7 @@ int tlab_dns_set_surface_bcs(tlab_dns_t d, const int *sfc_jmin, const int *sfc_j
             }
         }
         if (!d->sfc_avg) hk(hipMalloc((void **)&d->sfc_avg, sizeof(double)), "hipMalloc");
-    });
+    }, TLAB_EINVAL);
 }
 
 // nse_eqns == DNS_EQNS_ANELASTIC (tools/dns/rhs_global_incompressible_1.f90:211-214, 275-277, 326-329; physics/opr_burgers.f90:128-183) with the
@@ -311,7 +311,7 @@ int tlab_dns_set_buffer_type(tlab_dns_t d, int type) {
         if (type == TLAB_BUFFER_NONE)
             for (auto &g : d->buff)
                 for (tlab_dns::BufferBlock &b : g) tlab_dns::free_block(b, true);
-    });
+    }, TLAB_EINVAL);
 }
 
 int tlab_dns_set_buffer_zone(tlab_dns_t d, int end, int group, int size, int nfields, const double *tau, const double *ref) {

@@ -1,5 +1,5 @@
-// What the three drivers (rhs.cpp with dns_setup.cpp: one domain, slab.cpp: z-slabs, pencil.cpp: x/z pencils) and zslab.hip share around their physics: the error
-// type and the guards of their entry points, and the state and argument checks that do not depend on the decomposition.  Header-only, host code.
+// What the three drivers (rhs.cpp with dns_setup.cpp: one domain, slab.cpp: z-slabs, pencil.cpp: x/z pencils) and zslab.hip share around their physics: the state
+// and argument checks that do not depend on the decomposition (the error type and the guards of their entry points: errors.hpp).  Header-only, host code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,45 +8,10 @@
 #include <string>
 #include <vector>
 
+#include "errors.hpp"
 #include "internal.hpp"
 
 namespace tlab {
-
-struct Fail : std::runtime_error {
-    int code;
-    Fail(int c, const std::string &s) : std::runtime_error(s), code(c) {}
-};
-inline void ok(int rc, const char *what) {
-    if (rc != TLAB_OK) throw Fail(rc, std::string(what) + ": " + tlab_last_error());
-}
-inline void hk(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw Fail(TLAB_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// The body of an entry point: a Fail becomes its code, with its text in tlab_last_error().  Any other std::exception becomes `other`; with
-// TLAB_OK it is not caught (the entry points whose bodies throw nothing but Fail).
-template <class F>
-int catch_fail(F f, int other = TLAB_OK) {
-    try {
-        f();
-        return TLAB_OK;
-    } catch (const Fail &e) {
-        tlab_set_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        if (other == TLAB_OK) throw;
-        tlab_set_error(e.what());
-        return other;
-    }
-}
-// ... of an entry point that is refused before tlab_init
-template <class F>
-int guarded(F f) {
-    return catch_fail([&] {
-        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
-        f();
-    }, TLAB_EINVAL);
-}
 
 // n doubles (at least one) of device memory, zeroed by a blocking hipMemset or -- on_stream -- by hipMemsetAsync on the library's current stream
 inline double *dalloc(size_t n, bool on_stream) {

@@ -8,11 +8,11 @@
 #include <hip/hip_runtime.h>
 
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/tlab_amd.h"
+#include "errors.hpp"
 #include "filter_state.hpp"      // struct tlab_filter
 #include "internal.hpp"
 #include "kernels.hpp"
@@ -162,80 +162,51 @@ __global__ void __launch_bounds__(256) k_filter1d(FilterArgs a) {
 #undef C
 }
 
-LineGeom geom_of(int dir, int nx, int ny, int nz) {
-    LineGeom g;
-    if (dir == 1) { g.n = nx; g.nlines = (long long)ny * nz; g.row_stride = 1; g.lines_inner = 1; g.outer_stride = nx; }
-    else if (dir == 2) { g.n = ny; g.nlines = (long long)nx * nz; g.row_stride = nx; g.lines_inner = nx; g.outer_stride = (long long)nx * ny; }
-    else { g.n = nz; g.nlines = (long long)nx * ny; g.row_stride = (long long)nx * ny; g.lines_inner = nx * ny; g.outer_stride = 0; }
-    return g;
-}
-
-template <class F>
-int guarded(F &&f) {
-    try {
-        f();
-        return TLAB_OK;
-    } catch (const std::invalid_argument &e) {
-        tlab_set_error(e.what());
-        return TLAB_EINVAL;
-    } catch (const std::domain_error &e) {
-        tlab_set_error(e.what());
-        return TLAB_EUNSUPPORTED;
-    } catch (const std::bad_alloc &) {
-        tlab_set_error("out of memory");
-        return TLAB_ENOMEM;
-    } catch (const std::exception &e) {
-        tlab_set_error(e.what());
-        return TLAB_EHIP;
-    }
-}
-
 }  // namespace
 
 void tlab_internal_filter_1d(int dir, tlab_filter_t f, int nx, int ny, int nz, const double *u, double *result, hipStream_t st) {
-    const LineGeom g = geom_of(dir, nx, ny, nz);
-    if (g.n != f->n) throw std::invalid_argument("filter size does not match the field size along dir");
+    const LineGeom g = line_geom(dir, nx, ny, nz);
+    if (g.n != f->n) throw Fail(TLAB_EINVAL, "filter size does not match the field size along dir");
     FilterArgs a;
     a.in = u; a.out = result; a.g = g; a.type = f->type; a.periodic = f->periodic; a.bcsmin = f->bcsmin; a.bcsmax = f->bcsmax; a.c = f->coeffs.p;
     if (dir == 1 && g.nlines >= 64) {
         // x lines: one thread per line would stride through contiguous memory (64 cache lines per wave access).  Like the reference (OPR_FILTER_X:
         // TLab_Transpose, filter, transpose back) the lines are made the fastest index first: two transposes at the copy rate + the coalesced filter
         const size_t N = (size_t)g.n * g.nlines;
-        if (f->ws.n < 2 * N) f->ws.alloc(2 * N);
-        double *t1 = f->ws.p, *t2 = t1 + N;
-        if (launch_transpose(u, t1, g.n, (int)g.nlines, st) != hipSuccess) throw std::runtime_error("transpose");
+        double *t1 = f->ws.reserve(2 * N), *t2 = t1 + N;
+        if (launch_transpose(u, t1, g.n, (int)g.nlines, st) != hipSuccess) throw Fail(TLAB_EHIP, "transpose");
         a.in = t1; a.out = t2;
         a.g.row_stride = g.nlines; a.g.lines_inner = (int)g.nlines; a.g.outer_stride = 0;
         {
             ProfScope ps("k_filter1d", st, (double)g.nlines * g.n * 16.0);
             hipLaunchKernelGGL(k_filter1d, dim3((unsigned)((g.nlines + 255) / 256)), dim3(256), 0, st, a);
         }
-        if (hipGetLastError() != hipSuccess) throw std::runtime_error("k_filter1d launch failed");
-        if (launch_transpose(t2, result, (int)g.nlines, g.n, st) != hipSuccess) throw std::runtime_error("transpose");
+        if (hipGetLastError() != hipSuccess) throw Fail(TLAB_EHIP, "k_filter1d launch failed");
+        if (launch_transpose(t2, result, (int)g.nlines, g.n, st) != hipSuccess) throw Fail(TLAB_EHIP, "transpose");
         return;
     }
     ProfScope ps("k_filter1d", st, (double)g.nlines * g.n * 16.0);
     hipLaunchKernelGGL(k_filter1d, dim3((unsigned)((g.nlines + 255) / 256)), dim3(256), 0, st, a);
-    if (hipGetLastError() != hipSuccess) throw std::runtime_error("k_filter1d launch failed");
+    if (hipGetLastError() != hipSuccess) throw Fail(TLAB_EHIP, "k_filter1d launch failed");
 }
 
 extern "C" {
 
 int tlab_filter_create(tlab_filter_t *out, int type, int size, int periodic, int bcsmin, int bcsmax, int inb_filter, const double *coeffs) {
-    return guarded([&] {
-        if (!out) throw std::invalid_argument("tlab_filter_create: null handle");
-        if (type == FLT_TOPHAT) throw std::domain_error("tophat filters (flt_tophat.f90) are not built on the device path");
+    return catch_fail([&] {
+        if (!out) throw Fail(TLAB_EINVAL, "tlab_filter_create: null handle");
+        if (type == FLT_TOPHAT) throw Fail(TLAB_EUNSUPPORTED, "tophat filters (flt_tophat.f90) are not built on the device path");
         if (type != FLT_COMPACT && type != FLT_6E && type != FLT_4E && type != FLT_CUTOFF)
-            throw std::domain_error("filter type: compact (1), explicit6 (2), explicit4 (3), compactcutoff (9) -- the spectral / Helmholtz types are 3-D filters, not OPR_FILTER_1D");
+            throw Fail(TLAB_EUNSUPPORTED, "filter type: compact (1), explicit6 (2), explicit4 (3), compactcutoff (9) -- the spectral / Helmholtz types are 3-D filters, not OPR_FILTER_1D");
         const int need = type == FLT_COMPACT ? 10 : type == FLT_4E ? 5 : type == FLT_CUTOFF ? (periodic ? 7 : 5) : 0;
-        if (size < 8) throw std::invalid_argument("tlab_filter_create: at least 8 points");
-        if (need > 0 && (!coeffs || inb_filter < need)) throw std::invalid_argument("tlab_filter_create: f%coeffs with at least inb_filter columns (opr_filter.f90:121-139)");
-        if (!tlab_device_ready()) throw std::runtime_error("tlab_init has not been called (no CPU fallback exists)");
+        if (size < 8) throw Fail(TLAB_EINVAL, "tlab_filter_create: at least 8 points");
+        if (need > 0 && (!coeffs || inb_filter < need)) throw Fail(TLAB_EINVAL, "tlab_filter_create: f%coeffs with at least inb_filter columns (opr_filter.f90:121-139)");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
         auto f = std::make_unique<tlab_filter>();
         f->type = type; f->n = size; f->periodic = periodic ? 1 : 0; f->bcsmin = bcsmin; f->bcsmax = bcsmax; f->ncols = need;
         if (need > 0) f->coeffs.upload(std::vector<double>(coeffs, coeffs + (size_t)size * need));
         *out = f.release();
-    });
+    }, TLAB_EHIP);
 }
 
 int tlab_filter_destroy(tlab_filter_t f) {
@@ -246,35 +217,35 @@ int tlab_filter_destroy(tlab_filter_t f) {
 }
 
 int tlab_opr_filter_1d(int dir, tlab_filter_t f, int nx, int ny, int nz, const double *u, double *result) {
-    return guarded([&] {
-        if (!f || !u || !result || u == result) throw std::invalid_argument("tlab_opr_filter_1d: bad arguments (out of place)");
-        if (dir < 1 || dir > 3 || nx < 1 || ny < 1 || nz < 1) throw std::invalid_argument("tlab_opr_filter_1d: bad sizes");
+    return catch_fail([&] {
+        if (!f || !u || !result || u == result) throw Fail(TLAB_EINVAL, "tlab_opr_filter_1d: bad arguments (out of place)");
+        if (dir < 1 || dir > 3 || nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, "tlab_opr_filter_1d: bad sizes");
         tlab_internal_filter_1d(dir, f, nx, ny, nz, u, result, tlab_current_stream());
-    });
+    }, TLAB_EHIP);
 }
 
 // OPR_FILTER (operators/opr_filter.f90:283-392), directional branch: x, y, z in that order, each `repeat` times, in place through tmp
 int tlab_opr_filter(int nx, int ny, int nz, tlab_filter_t fx, tlab_filter_t fy, tlab_filter_t fz, const int *repeat, double *u, double *tmp) {
-    return guarded([&] {
-        if (!u || !tmp || u == tmp || nx < 1 || ny < 1 || nz < 1) throw std::invalid_argument("tlab_opr_filter: bad arguments");
+    return catch_fail([&] {
+        if (!u || !tmp || u == tmp || nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, "tlab_opr_filter: bad arguments");
         tlab_filter_t f[3] = {fx, fy, fz};
         hipStream_t st = tlab_current_stream();
         const size_t bytes = (size_t)nx * ny * nz * sizeof(double);
         const int ext[3] = {nx, ny, nz};
         for (int d = 0; d < 3; ++d) {      // every refusal before the first launch: u is in place, a call that fails must leave it as it was
             if (!f[d]) continue;
-            if (f[d]->n != ext[d]) throw std::invalid_argument("tlab_opr_filter: filter size does not match the field size along its direction");
-            if (repeat && repeat[d] < 1) throw std::invalid_argument("tlab_opr_filter: Filter.Repeat must be positive (opr_filter.f90:198-204)");
+            if (f[d]->n != ext[d]) throw Fail(TLAB_EINVAL, "tlab_opr_filter: filter size does not match the field size along its direction");
+            if (repeat && repeat[d] < 1) throw Fail(TLAB_EINVAL, "tlab_opr_filter: Filter.Repeat must be positive (opr_filter.f90:198-204)");
         }
         for (int d = 0; d < 3; ++d) {
             if (!f[d]) continue;
             const int rep = repeat ? repeat[d] : 1;
             for (int r = 0; r < rep; ++r) {
                 tlab_internal_filter_1d(d + 1, f[d], nx, ny, nz, u, tmp, st);
-                if (hipMemcpyAsync(u, tmp, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) throw std::runtime_error("hipMemcpyAsync");
+                if (hipMemcpyAsync(u, tmp, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) throw Fail(TLAB_EHIP, "hipMemcpyAsync");
             }
         }
-    });
+    }, TLAB_EHIP);
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 #include <string>
 
 #include "../../include/tlab_amd.h"
-#include "driver_common.hpp"
+#include "errors.hpp"
 #include "filter_lines.hpp"
 #include "filter_state.hpp"
 #include "internal.hpp"
@@ -135,13 +135,6 @@ __global__ void __launch_bounds__(FS_LINES) k_filter_stream(const StreamArgs a) 
     filter_line<TYPE, PER>(g, a.c, a.n, a.bcsmin, a.bcsmax);
 }
 
-struct Geom { long long nlines, rs, outer_stride; int n, lines_inner; };
-Geom geom_of(int dir, int nx, int ny, int nz) {
-    if (dir == 1) return {(long long)ny * nz, 1, nx, nx, 1};
-    if (dir == 2) return {(long long)nx * nz, nx, (long long)nx * ny, ny, nx};
-    return {(long long)nx * ny, (long long)nx * ny, 0, nz, nx * ny};
-}
-
 template <int TYPE, bool PER>
 void launch_tp(bool x, dim3 grid, const StreamArgs &a, hipStream_t st) {
     if (x) hipLaunchKernelGGL((k_filter_stream<TYPE, PER, true>), grid, dim3(FS_LINES), 0, st, a);
@@ -152,9 +145,9 @@ void launch_tp(bool x, dim3 grid, const StreamArgs &a, hipStream_t st) {
 int sweeps_of(int type, int periodic) { return type == FLT_COMPACT ? 2 : type == FLT_CUTOFF ? (periodic ? 3 : 2) : 1; }
 
 void launch_filter(int dir, tlab_filter_t f, int nx, int ny, int nz, int nf, double *const *u, hipStream_t st) {
-    const Geom g = geom_of(dir, nx, ny, nz);
+    const LineGeom g = line_geom(dir, nx, ny, nz);
     StreamArgs a;
-    a.c = f->coeffs.p; a.nlines = g.nlines; a.rs = g.rs; a.outer_stride = g.outer_stride; a.n = g.n; a.lines_inner = g.lines_inner;
+    a.c = f->coeffs.p; a.nlines = g.nlines; a.rs = g.row_stride; a.outer_stride = g.outer_stride; a.n = g.n; a.lines_inner = g.lines_inner;
     a.bcsmin = f->bcsmin; a.bcsmax = f->bcsmax;
     static const char *const tag[3] = {"k_filter_stream_x", "k_filter_stream_y", "k_filter_stream_z"};
     for (int f0 = 0; f0 < nf; f0 += FS_MAXF) {

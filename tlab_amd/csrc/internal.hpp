@@ -15,11 +15,20 @@ struct SubstepTail;      // driver_common.hpp
 struct ParticleState;    // particles.hip
 }
 
-// ---- capi.cpp ----
+// ---- runtime.cpp ----
 // hooks for the other translation units (also libtlab_amd_comm.so: comm.hip)
 hipStream_t tlab_current_stream();      // the library's stream; a recorded substep (deferred.cpp) runs first
 void tlab_set_error(const std::string &s);
 bool tlab_device_ready();
+
+// ---- fdm_plan.cpp ----
+// coefficients of BOUNDARY_BCS_NEUMANN_Y (boundary_bcs.f90:368-473): wall value = (u(2) cb0 + u(3) cb1) + u(4) cb2 + cb3 du(2), likewise at the top
+void tlab_internal_neumann_y_coefficients(tlab_fdm_plan_t g, int ibc, int ny, double (&cb)[4], double (&ct)[4]);
+
+// ---- operators.cpp ----
+// chunks per x line of the wave-per-line kernel for this plan (0: not on that kernel): tlab_fdm_plan_info
+int xline_chunks(int n, tlab_fdm_plan_t g);
+void tlab_internal_operators_release();      // tlab_finalize
 // internal fused variants for the RHS driver; return false when the sizes are not on a fused fast path
 // result (+)= d/dx_dir (u + scale*ub)
 bool tlab_internal_partial_p1_fusable(int dir, tlab_fdm_plan_t g, int nx, int ny, int nz);

@@ -142,7 +142,7 @@ struct XSys {                    // per-lane view of one chunked system
 // LV = 0: every chunk has the same tables (scalar loads of chunk 0); 1: lane-variant tables [5][M][P] doubles in LDS; 2: lane-variant tables
 // kept as chunk 0's value (scalar load) + a float difference in LDS -- where two systems of doubles do not fit (n >= 1024 with both systems).
 // The reconstruction is exact when the chunks differ by less than 2^-29 relative (the 1e-13 wander of a "uniform" reference grid): the plan
-// checks every entry on the host (xline_wide_ok, capi.cpp) and takes another kernel otherwise.
+// checks every entry on the host (xline_wide_ok, operators.cpp) and takes another kernel otherwise.
 template <int M, int LV, int WPL>
 __device__ __forceinline__ double xcoef(const double *rowtab, ldsd_t *lds, int tab, int p, int gl, int n) {
     constexpr int P = 64 * WPL;
@@ -1123,7 +1123,7 @@ hipError_t launch_penta1(const PentaArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
-bool xline_supported(int n) { return n == 256 || n == 512 || n == 1024; }      // n = 2048, and n = 1024 on several waves: see xline_chunks (capi.cpp)
+bool xline_supported(int n) { return n == 256 || n == 512 || n == 1024; }      // n = 2048, and n = 1024 on several waves: see xline_chunks (operators.cpp)
 
 // chunks = 64: one wave per line (n = 64 M); 128 / 256: two / four waves per line with 8 rows per lane (periodic lines of 1024 / 2048 points
 // whose tables pass xline_wide_ok; float-difference tables when they are lane-variant)

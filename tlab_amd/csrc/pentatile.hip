@@ -16,9 +16,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <stdexcept>
 #include <vector>
 
+#include "errors.hpp"
 #include "kernels.hpp"
 #include "profile.hpp"
 
@@ -28,7 +28,7 @@ namespace tlab {
 // each sweep; the block matrices are [2][C][C][4]; periodic lines: the two vectors of the rank-two correction [2][n] and its 8 constants
 void pentatile_build(int n, int C, bool periodic, int ibc, const double *lu, std::vector<double> &rows, std::vector<double> &blocks, std::vector<double> &smw) {
     const int M = n / C;
-    if (C < 2 || C > 16 || M * C != n || M < 8) throw std::invalid_argument("pentatile_build: bad chunking");
+    if (C < 2 || C > 16 || M * C != n || M < 8) throw Fail(TLAB_EINVAL, "pentatile_build: bad chunking");
     const int ip = periodic ? 0 : ibc * 5;
     const bool nb = !periodic && (ibc == 1 || ibc == 3), nt = !periodic && (ibc == 2 || ibc == 3);
     const int jmin = nb ? 1 : 0, jmax = nt ? n - 2 : n - 1;

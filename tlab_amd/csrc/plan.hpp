@@ -24,6 +24,8 @@ struct DeviceArray {
     ~DeviceArray();
     void upload(const std::vector<double> &h);
     void alloc(size_t count);       // uninitialised scratch of count doubles (grows or shrinks to exactly that)
+    // at least count doubles of scratch: grows to exactly count, never shrinks, contents undefined (what: the text of a refused allocation)
+    double *reserve(size_t count, const char *what = "hipMalloc(scratch)");
 };
 
 struct SystemEntry {
@@ -50,8 +52,8 @@ struct tlab_fdm_plan {
     std::unique_ptr<tlab::DeviceArray> penta_rhs, penta_lu;   // CompactJacobian6Penta first derivative: g%der1%rhs (n,7) and g%der1%lu on the device
     struct PentaTile { tlab::DeviceArray rows, blocks, smw; };
     std::map<int, std::unique_ptr<PentaTile>> penta_tile;     // ... and the tables of k_pentatile per Neumann variant (pentatile_build)
-    tlab_filter_t interp[4] = {nullptr, nullptr, nullptr, nullptr};      // interpolatory operators P1 VP, P1 PV, P0 VP, P0 PV as periodic compact-filter objects (capi.cpp)
-    int wide_ok[3] = {-1, -1, -1};             // x lines on 64 / 128 / 256 chunks: float-difference tables exact? (-1 = not checked yet; capi.cpp xline_wide_ok)
+    tlab_filter_t interp[4] = {nullptr, nullptr, nullptr, nullptr};      // interpolatory operators P1 VP, P1 PV, P0 VP, P0 PV as periodic compact-filter objects (operators.cpp)
+    int wide_ok[3] = {-1, -1, -1};             // x lines on 64 / 128 / 256 chunks: float-difference tables exact? (-1 = not checked yet; operators.cpp xline_wide_ok)
 
     tlab::TriDiag tridiag(int which, int ibc) const;            // tridiagonal matrix of the variant (wall rows -> identity)
     tlab::StencilDev stencil(int which, int ibc);               // RHS operator of the variant

@@ -968,46 +968,45 @@ hipError_t launch_neumann_planes(const double *u, const double *du, const double
 // ---- the pointwise pieces on their own, for drivers that interleave communication (z-slab decomposition) ----
 using namespace tlab;
 
-#define PW_GUARD(expr)                                          \
-    try {                                                       \
-        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called"); \
-        hk((expr), "pointwise kernel");                         \
-        return TLAB_OK;                                         \
-    } catch (const Fail &f) {                                   \
-        tlab_set_error(f.what());                               \
-        return f.code;                                          \
-    }
+// an entry point that is one launch: refused before tlab_init, the launch's hipError_t checked
+template <class L>
+static int pw_launch(L launch) {
+    return catch_fail([&] {
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called");
+        hk(launch(), "pointwise kernel");
+    }, TLAB_EINVAL);
+}
 extern "C" {
-int tlab_pw_add3(double *h, const double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_add3(h, a, b, c, n, tlab_current_stream())) }
+int tlab_pw_add3(double *h, const double *a, const double *b, const double *c, long long n) { return pw_launch([&] { return launch_add3(h, a, b, c, n, tlab_current_stream()); }); }
 int tlab_pw_axpy3(double *o1, double *o2, double *o3, const double *h1, const double *h2, const double *h3, const double *q1, const double *q2,
-                  const double *q3, double s, long long n) { PW_GUARD(launch_axpy3(o1, o2, o3, h1, h2, h3, q1, q2, q3, s, n, tlab_current_stream())) }
-int tlab_pw_sum3(double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_sum3(a, b, c, n, tlab_current_stream())) }
-int tlab_pw_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n) { PW_GUARD(launch_sub3(h1, h2, h3, a, b, c, n, tlab_current_stream())) }
-int tlab_pw_rk_update(double *q, double *h, double dte, double kco, int scale, long long n) { PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream())) }
+                  const double *q3, double s, long long n) { return pw_launch([&] { return launch_axpy3(o1, o2, o3, h1, h2, h3, q1, q2, q3, s, n, tlab_current_stream()); }); }
+int tlab_pw_sum3(double *a, const double *b, const double *c, long long n) { return pw_launch([&] { return launch_sum3(a, b, c, n, tlab_current_stream()); }); }
+int tlab_pw_sub3(double *h1, double *h2, double *h3, const double *a, const double *b, const double *c, long long n) { return pw_launch([&] { return launch_sub3(h1, h2, h3, a, b, c, n, tlab_current_stream()); }); }
+int tlab_pw_rk_update(double *q, double *h, double dte, double kco, int scale, long long n) { return pw_launch([&] { return launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream()); }); }
 int tlab_pw_clip(double *a, double lo, double hi, long long n) {
     if (!a || n < 0 || std::isnan(lo) || std::isnan(hi) || lo > hi) { tlab_set_error("tlab_pw_clip: null array, n < 0, NaN bounds or lo > hi"); return TLAB_EINVAL; }
-    PW_GUARD(launch_clip(a, lo, hi, n, tlab_current_stream()))
+    return pw_launch([&] { return launch_clip(a, lo, hi, n, tlab_current_stream()); });
 }
-int tlab_pw_fill(double *a, double value, long long n) { PW_GUARD(launch_fill(a, value, n, tlab_current_stream())) }
-int tlab_pw_scale(double *a, double alpha, long long n) { PW_GUARD(launch_scale(a, alpha, n, tlab_current_stream())) }
+int tlab_pw_fill(double *a, double value, long long n) { return pw_launch([&] { return launch_fill(a, value, n, tlab_current_stream()); }); }
+int tlab_pw_scale(double *a, double alpha, long long n) { return pw_launch([&] { return launch_scale(a, alpha, n, tlab_current_stream()); }); }
 int tlab_pw_final_update(double *q, double *h, const double *g, const double *pb, const double *pt, double dte, double kco, int scale, int nx, int ny,
-                         int nz) { PW_GUARD(launch_final_update(q, h, g, pb, pt, dte, kco, scale, nx, ny, nz, tlab_current_stream())) }
+                         int nz) { return pw_launch([&] { return launch_final_update(q, h, g, pb, pt, dte, kco, scale, nx, ny, nz, tlab_current_stream()); }); }
 int tlab_pencil_repack(double *slab, double *buffer, int nxh, int ny, int kmax, int nproc, const int *ioff, int dir) {
     if (!slab || !buffer || !ioff || nproc < 1 || nproc > 8 || nxh < nproc) { tlab_set_error("tlab_pencil_repack: bad arguments (1..8 peers)"); return TLAB_EINVAL; }
-    PW_GUARD(launch_pencil_repack(slab, buffer, nxh, ny, kmax, nproc, ioff, nullptr, dir, tlab_current_stream()))
+    return pw_launch([&] { return launch_pencil_repack(slab, buffer, nxh, ny, kmax, nproc, ioff, nullptr, dir, tlab_current_stream()); });
 }
 int tlab_pencil_repack_blocks(double *slab, double *buffer, int nxh, int ny, int kmax, int nblocks, const int *start, const long long *base, int dir) {
     if (!slab || !buffer || !start || !base || nblocks < 1 || nblocks > 16 || start[0] != 0) { tlab_set_error("tlab_pencil_repack_blocks: bad arguments (1..16 blocks, the first at kx = 0)"); return TLAB_EINVAL; }
     for (int p = 0; p + 1 < nblocks; ++p)
         if (start[p + 1] < start[p] || start[p + 1] > nxh) { tlab_set_error("tlab_pencil_repack_blocks: block starts must increase within [0, nx/2+1]"); return TLAB_EINVAL; }
-    PW_GUARD(launch_pencil_repack(slab, buffer, nxh, ny, kmax, nblocks, start, base, dir, tlab_current_stream()))
+    return pw_launch([&] { return launch_pencil_repack(slab, buffer, nxh, ny, kmax, nblocks, start, base, dir, tlab_current_stream()); });
 }
-int tlab_pw_get_wall_planes(const double *f, double *hb, double *ht, int nx, int ny, int nz) { PW_GUARD(launch_get_wall_planes(f, hb, ht, nx, ny, nz, tlab_current_stream())) }
-int tlab_pw_fill_wall_planes(double *f, double vb, double vt, int nx, int ny, int nz) { PW_GUARD(launch_fill_wall_planes(f, vb, vt, nx, ny, nz, tlab_current_stream())) }
-int tlab_pw_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz) { PW_GUARD(launch_set_wall_planes(f, pb, pt, nx, ny, nz, tlab_current_stream())) }
+int tlab_pw_get_wall_planes(const double *f, double *hb, double *ht, int nx, int ny, int nz) { return pw_launch([&] { return launch_get_wall_planes(f, hb, ht, nx, ny, nz, tlab_current_stream()); }); }
+int tlab_pw_fill_wall_planes(double *f, double vb, double vt, int nx, int ny, int nz) { return pw_launch([&] { return launch_fill_wall_planes(f, vb, vt, nx, ny, nz, tlab_current_stream()); }); }
+int tlab_pw_set_wall_planes(double *f, const double *pb, const double *pt, int nx, int ny, int nz) { return pw_launch([&] { return launch_set_wall_planes(f, pb, pt, nx, ny, nz, tlab_current_stream()); }); }
 }  // extern "C"
 
 int tlab_internal_pw_rk_update_clip(double *q, double *h, double dte, double kco, int scale, long long n, double lo, double hi) {
     const tlab::ClipBounds c{lo, hi};
-    PW_GUARD(launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream(), &c))
+    return pw_launch([&] { return launch_rk_update(q, h, dte, kco, scale, n, tlab_current_stream(), &c); });
 }

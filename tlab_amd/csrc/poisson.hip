@@ -563,180 +563,181 @@ extern "C" {
 static int poisson_plan_create_impl(tlab_poisson_plan_t *out, tlab_fdm_plan_t gx, tlab_fdm_plan_t gy, tlab_fdm_plan_t gz, int nx, int ny,
                                     int nz, int nzt, int koff, int nproc, int ioff = 0, int nxl = 0, int fx_nz = 0,
                                     tlab_fdm_plan_t gy_ell = nullptr, bool helmholtz = false, double alpha = 0.0) {
-    POISSON_GUARD_BEGIN
-    if (!out || !gx || !gy || !gz) throw std::invalid_argument("tlab_poisson_plan_create: null argument");
-    if (!tlab_device_ready()) throw std::runtime_error("tlab_init has not been called (no CPU fallback exists)");
-    if (gx->t.n != nx || gy->t.n != ny || gz->t.n != nzt) throw std::invalid_argument("plan sizes do not match nx, ny, nz");
-    if (!gx->t.periodic || (nzt > 1 && !gz->t.periodic) || gy->t.periodic)
-        throw std::invalid_argument("OPR_Poisson_FourierXZ needs periodic x, z and non-periodic y");
-    if (nx % 2 != 0) throw std::invalid_argument("Imax must be a multiple of 2 for the FFT operations (opr_fourier.f90:72-75)");
-    {   // host-built plans (tlab_fdm_plan_create_from_arrays) carry the modified wavenumbers only after tlab_fdm_plan_set_aux
-        auto no_mwn = [](const tlab::DerTables &d) {
-            for (double v : d.mwn) if (v != 0.0) return false;
-            return true;
-        };
-        if (!gy_ell && (no_mwn(gx->t.der1) || (nzt > 1 && no_mwn(gz->t.der1))))
-            throw std::invalid_argument("the x / z plans carry no modified wavenumbers (der1%mwn): call tlab_fdm_plan_set_aux");
-        if (gy_ell && (no_mwn(gx->t.der2) || (nzt > 1 && no_mwn(gz->t.der2))))
-            throw std::invalid_argument("the x / z plans carry no second-derivative modified wavenumbers (der2%mwn): call tlab_fdm_plan_set_aux");
-        if (gy_ell && (gy_ell->t.n != ny || gy_ell->t.periodic || !gy_ell->t.der2.direct || gy_ell->t.der2.ndl != 3 || gy_ell->t.der2.ndr != 5 ||
-                       (int)gy_ell->t.nodes.size() != ny))
-            throw std::invalid_argument("direct elliptic solver: the elliptic y plan must hold a CompactDirect6 second derivative (3/5 diagonals) and its nodes");
-    }
-    if (nproc < 1 || nz * nproc != nzt || koff < 0 || koff + nz > nzt) throw std::invalid_argument("bad z-slab decomposition");
-    if (((long long)(nx / 2 + 1) * ny) % nproc != 0) throw std::invalid_argument("(imax/2+1)*jmax must be divisible by the number of z slabs (tlab_mpi_transpose.f90:292)");
-    auto P = std::make_unique<tlab_poisson_plan>();
-    if (nxl < 0 || ioff < 0 || ioff + nxl > nx / 2 + 1) throw std::invalid_argument("bad kx range");
-    P->nx = nx; P->ny = ny; P->nz = nz; P->nxh = nxl > 0 ? nxl : nx / 2 + 1;
-    P->ioff = nxl > 0 ? ioff : 0;
-    P->fx_nxh = nx / 2 + 1; P->fx_nz = fx_nz > 0 ? fx_nz : nz;
-    P->nzt = nzt; P->koff = koff; P->nproc = nproc;
-    P->nm = (long long)P->nxh * nz;
-    P->norm = 1.0 / ((double)nx * (double)nzt);                     // opr_elliptic.f90:130
-    if (gy_ell) {   // TYPE_DIRECT (opr_elliptic.f90:152-163, 228-245)
-        P->direct = true;
-        P->exact_mode = g_poisson_exact;
-        P->gy_der = gy;
-        P->ell_der2 = gy_ell->t.der2;
-        P->ell_nodes = gy_ell->t.nodes;
+    return catch_fail([&]() -> int {
+        if (!out || !gx || !gy || !gz) throw Fail(TLAB_EINVAL, "tlab_poisson_plan_create: null argument");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called (no CPU fallback exists)");
+        if (gx->t.n != nx || gy->t.n != ny || gz->t.n != nzt) throw Fail(TLAB_EINVAL, "plan sizes do not match nx, ny, nz");
+        if (!gx->t.periodic || (nzt > 1 && !gz->t.periodic) || gy->t.periodic)
+            throw Fail(TLAB_EINVAL, "OPR_Poisson_FourierXZ needs periodic x, z and non-periodic y");
+        if (nx % 2 != 0) throw Fail(TLAB_EINVAL, "Imax must be a multiple of 2 for the FFT operations (opr_fourier.f90:72-75)");
+        {   // host-built plans (tlab_fdm_plan_create_from_arrays) carry the modified wavenumbers only after tlab_fdm_plan_set_aux
+            auto no_mwn = [](const tlab::DerTables &d) {
+                for (double v : d.mwn) if (v != 0.0) return false;
+                return true;
+            };
+            if (!gy_ell && (no_mwn(gx->t.der1) || (nzt > 1 && no_mwn(gz->t.der1))))
+                throw Fail(TLAB_EINVAL, "the x / z plans carry no modified wavenumbers (der1%mwn): call tlab_fdm_plan_set_aux");
+            if (gy_ell && (no_mwn(gx->t.der2) || (nzt > 1 && no_mwn(gz->t.der2))))
+                throw Fail(TLAB_EINVAL, "the x / z plans carry no second-derivative modified wavenumbers (der2%mwn): call tlab_fdm_plan_set_aux");
+            if (gy_ell && (gy_ell->t.n != ny || gy_ell->t.periodic || !gy_ell->t.der2.direct || gy_ell->t.der2.ndl != 3 || gy_ell->t.der2.ndr != 5 ||
+                           (int)gy_ell->t.nodes.size() != ny))
+                throw Fail(TLAB_EINVAL, "direct elliptic solver: the elliptic y plan must hold a CompactDirect6 second derivative (3/5 diagonals) and its nodes");
+        }
+        if (nproc < 1 || nz * nproc != nzt || koff < 0 || koff + nz > nzt) throw Fail(TLAB_EINVAL, "bad z-slab decomposition");
+        if (((long long)(nx / 2 + 1) * ny) % nproc != 0) throw Fail(TLAB_EINVAL, "(imax/2+1)*jmax must be divisible by the number of z slabs (tlab_mpi_transpose.f90:292)");
+        auto P = std::make_unique<tlab_poisson_plan>();
+        if (nxl < 0 || ioff < 0 || ioff + nxl > nx / 2 + 1) throw Fail(TLAB_EINVAL, "bad kx range");
+        P->nx = nx; P->ny = ny; P->nz = nz; P->nxh = nxl > 0 ? nxl : nx / 2 + 1;
+        P->ioff = nxl > 0 ? ioff : 0;
+        P->fx_nxh = nx / 2 + 1; P->fx_nz = fx_nz > 0 ? fx_nz : nz;
+        P->nzt = nzt; P->koff = koff; P->nproc = nproc;
+        P->nm = (long long)P->nxh * nz;
+        P->norm = 1.0 / ((double)nx * (double)nzt);                     // opr_elliptic.f90:130
+        if (gy_ell) {   // TYPE_DIRECT (opr_elliptic.f90:152-163, 228-245)
+            P->direct = true;
+            P->exact_mode = g_poisson_exact;
+            P->gy_der = gy;
+            P->ell_der2 = gy_ell->t.der2;
+            P->ell_nodes = gy_ell->t.nodes;
+            const long long nm = P->nm;
+            std::vector<double> lam((size_t)nm);
+            for (int k = 0; k < nz; ++k)
+                for (int i = 0; i < P->nxh; ++i) {
+                    double l2 = gx->t.der2.mwn[P->ioff + i];                       // lambda = mwn2_x + mwn2_z (:230-234)
+                    if (nzt > 1) l2 += gz->t.der2.mwn[koff + k];
+                    lam[(size_t)i + (size_t)P->nxh * k] = l2;
+                }
+            if (P->ioff == 0 && koff == 0) P->sing_direct = 0;                      // i_sing = k_sing = [1, 1] (:160-161)
+            P->lam.upload(lam);
+            (void)P->dev2(TLAB_BCS_NN);
+            if (P->sing_direct >= 0) (void)P->dev2(TLAB_BCS_DN);
+            P->scratch.alloc((size_t)5 * ny * nm);
+            P->cwork.alloc((size_t)2 * P->nxh * ny * nz);
+            build_fft(*P);
+            *out = P.release();
+            return TLAB_OK;
+        }
+        if (int1_generic_applies(gy->t.der1)) {      // (3, 3) / (5, 7) diagonals: TRIDFS / HEPTADFS systems, factorized on the host (int1_generic.cpp)
+            if (gy->t.periodic) throw Fail(TLAB_EINVAL, "Poisson: the wall-normal direction must not be periodic");
+            P->generic = true;
+            P->gder = gy->t.der1;
+        } else {
+            int1_build_tables(gy->t.der1, 1, P->tmin);
+            int1_build_tables(gy->t.der1, 2, P->tmax);
+            P->d_L0[0].upload(P->tmin.L0); P->d_L1[0].upload(P->tmin.L1); P->d_R[0].upload(P->tmin.R);
+            P->d_L0[1].upload(P->tmax.L0); P->d_L1[1].upload(P->tmax.L1); P->d_R[1].upload(P->tmax.R);
+            for (int w = 0; w < 2; ++w) {
+                const Int1Tables &T = w == 0 ? P->tmin : P->tmax;
+                if (T.L0.size() < (size_t)6 * ny || T.L1.size() < (size_t)5 * ny || T.R.size() < (size_t)3 * ny) continue;      // (generic tables: k_int1g)
+                std::vector<double> pk((size_t)16 * ny, 0.0);
+                for (int j = 0; j < ny; ++j) {
+                    for (int k = 0; k < 5; ++k) { pk[(size_t)16 * j + k] = T.L0[(size_t)5 * j + k]; pk[(size_t)16 * j + 5 + k] = T.L1[(size_t)5 * j + k]; }
+                    pk[(size_t)16 * j + 10] = T.L0[(size_t)5 * ny + j];
+                    pk[(size_t)16 * j + 11] = T.R[(size_t)3 * j + 0];
+                    pk[(size_t)16 * j + 12] = T.R[(size_t)3 * j + 1];
+                    pk[(size_t)16 * j + 13] = T.R[(size_t)3 * j + 2];
+                }
+                P->d_pk[w].upload(pk);
+            }
+        }
+        // lambda(k,i) = mwn_x(i)^2 + mwn_z(k)^2 (opr_elliptic.f90:199-203), stored as sqrt (:205-209)
         const long long nm = P->nm;
         std::vector<double> lam((size_t)nm);
+        std::vector<unsigned char> skip((size_t)nm, 0);
         for (int k = 0; k < nz; ++k)
             for (int i = 0; i < P->nxh; ++i) {
-                double l2 = gx->t.der2.mwn[P->ioff + i];                       // lambda = mwn2_x + mwn2_z (:230-234)
-                if (nzt > 1) l2 += gz->t.der2.mwn[koff + k];
-                lam[(size_t)i + (size_t)P->nxh * k] = l2;
+                double l2 = std::pow(gx->t.der1.mwn[P->ioff + i], 2.0);
+                if (nzt > 1) l2 += std::pow(gz->t.der1.mwn[koff + k], 2.0);   // kglobal = k + ims_offset_k (:191)
+                if (helmholtz) {                                             // sqrt(lambda(k,i) - alpha) (:518-522)
+                    if (!(l2 - alpha > 0.0)) throw Fail(TLAB_EINVAL, "OPR_Helmholtz (factorized): lambda - alpha must be positive for every mode");
+                    l2 = l2 - alpha;
+                }
+                lam[(size_t)i + (size_t)P->nxh * k] = std::sqrt(l2);
             }
-        if (P->ioff == 0 && koff == 0) P->sing_direct = 0;                      // i_sing = k_sing = [1, 1] (:160-161)
+        // i_sing, k_sing (:148-149), 0-based, global; with the staggered pressure grid only (1, 1) is singular: the interpolatory modified
+        // wavenumbers do not vanish at the Nyquist modes (:144-146)
+        const bool stag = gx->t.stagger || (nzt > 1 && gz->t.stagger);
+        const int isg[2] = {0, stag ? 0 : nx / 2}, ksg[2] = {0, (nzt > 1 && !stag) ? nzt / 2 : 0};
+        for (int a = 0; a < 2 && !helmholtz; ++a)                           // Helmholtz: every mode is a regular one (:512-531)
+            for (int b = 0; b < 2; ++b) {
+                const int kl = ksg[b] - koff;                               // task-local index (:177-178)
+                const int il = isg[a] - P->ioff;
+                if (kl < 0 || kl >= nz || il < 0 || il >= P->nxh) continue;
+                const int t = il + P->nxh * kl;
+                if (!skip[t]) { skip[t] = 1; P->sing_modes.push_back(t); }
+            }
         P->lam.upload(lam);
-        (void)P->dev2(TLAB_BCS_NN);
-        if (P->sing_direct >= 0) (void)P->dev2(TLAB_BCS_DN);
-        P->scratch.alloc((size_t)5 * ny * nm);
-        P->cwork.alloc((size_t)2 * P->nxh * ny * nz);
-        build_fft(*P);
-        *out = P.release();
-        return TLAB_OK;
-    }
-    if (int1_generic_applies(gy->t.der1)) {      // (3, 3) / (5, 7) diagonals: TRIDFS / HEPTADFS systems, factorized on the host (int1_generic.cpp)
-        if (gy->t.periodic) throw std::invalid_argument("Poisson: the wall-normal direction must not be periodic");
-        P->generic = true;
-        P->gder = gy->t.der1;
-    } else {
-        int1_build_tables(gy->t.der1, 1, P->tmin);
-        int1_build_tables(gy->t.der1, 2, P->tmax);
-        P->d_L0[0].upload(P->tmin.L0); P->d_L1[0].upload(P->tmin.L1); P->d_R[0].upload(P->tmin.R);
-        P->d_L0[1].upload(P->tmax.L0); P->d_L1[1].upload(P->tmax.L1); P->d_R[1].upload(P->tmax.R);
-        for (int w = 0; w < 2; ++w) {
-            const Int1Tables &T = w == 0 ? P->tmin : P->tmax;
-            if (T.L0.size() < (size_t)6 * ny || T.L1.size() < (size_t)5 * ny || T.R.size() < (size_t)3 * ny) continue;      // (generic tables: k_int1g)
-            std::vector<double> pk((size_t)16 * ny, 0.0);
-            for (int j = 0; j < ny; ++j) {
-                for (int k = 0; k < 5; ++k) { pk[(size_t)16 * j + k] = T.L0[(size_t)5 * j + k]; pk[(size_t)16 * j + 5 + k] = T.L1[(size_t)5 * j + k]; }
-                pk[(size_t)16 * j + 10] = T.L0[(size_t)5 * ny + j];
-                pk[(size_t)16 * j + 11] = T.R[(size_t)3 * j + 0];
-                pk[(size_t)16 * j + 12] = T.R[(size_t)3 * j + 1];
-                pk[(size_t)16 * j + 13] = T.R[(size_t)3 * j + 2];
-            }
-            P->d_pk[w].upload(pk);
-        }
-    }
-    // lambda(k,i) = mwn_x(i)^2 + mwn_z(k)^2 (opr_elliptic.f90:199-203), stored as sqrt (:205-209)
-    const long long nm = P->nm;
-    std::vector<double> lam((size_t)nm);
-    std::vector<unsigned char> skip((size_t)nm, 0);
-    for (int k = 0; k < nz; ++k)
-        for (int i = 0; i < P->nxh; ++i) {
-            double l2 = std::pow(gx->t.der1.mwn[P->ioff + i], 2.0);
-            if (nzt > 1) l2 += std::pow(gz->t.der1.mwn[koff + k], 2.0);   // kglobal = k + ims_offset_k (:191)
-            if (helmholtz) {                                             // sqrt(lambda(k,i) - alpha) (:518-522)
-                if (!(l2 - alpha > 0.0)) throw std::invalid_argument("OPR_Helmholtz (factorized): lambda - alpha must be positive for every mode");
-                l2 = l2 - alpha;
-            }
-            lam[(size_t)i + (size_t)P->nxh * k] = std::sqrt(l2);
-        }
-    // i_sing, k_sing (:148-149), 0-based, global; with the staggered pressure grid only (1, 1) is singular: the interpolatory modified
-    // wavenumbers do not vanish at the Nyquist modes (:144-146)
-    const bool stag = gx->t.stagger || (nzt > 1 && gz->t.stagger);
-    const int isg[2] = {0, stag ? 0 : nx / 2}, ksg[2] = {0, (nzt > 1 && !stag) ? nzt / 2 : 0};
-    for (int a = 0; a < 2 && !helmholtz; ++a)                           // Helmholtz: every mode is a regular one (:512-531)
-        for (int b = 0; b < 2; ++b) {
-            const int kl = ksg[b] - koff;                               // task-local index (:177-178)
-            const int il = isg[a] - P->ioff;
-            if (kl < 0 || kl >= nz || il < 0 || il >= P->nxh) continue;
-            const int t = il + P->nxh * kl;
-            if (!skip[t]) { skip[t] = 1; P->sing_modes.push_back(t); }
-        }
-    P->lam.upload(lam);
-    hipc(hipMalloc((void **)&P->d_skip, (size_t)nm), "hipMalloc");
-    hipc(hipMemcpy(P->d_skip, skip.data(), (size_t)nm, hipMemcpyHostToDevice), "hipMemcpy");
-    const int ns = (int)P->sing_modes.size();
-    hipc(hipMalloc((void **)&P->d_sing, (ns + 1) * sizeof(int)), "hipMalloc");
-    if (ns) hipc(hipMemcpy(P->d_sing, P->sing_modes.data(), ns * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy");
-    std::vector<double> slam(ns);
-    for (int s = 0; s < ns; ++s) slam[s] = lam[P->sing_modes[s]];
-    P->s_lam.upload(slam);
-    const size_t n = ny;
-    P->hom.alloc(5 * n * nm); P->der.alloc(3 * nm); P->cst.alloc(9 * nm);
-    P->scratch.alloc(6 * n * nm);      // NL + 3 components, NL <= 3
-    P->v0.alloc(2 * n * nm); P->u0.alloc(2 * n * nm); P->du0.alloc(2 * nm); P->bcs.alloc(4 * nm);
-    P->helmholtz = helmholtz;
-    if (!helmholtz) P->cwork.alloc((size_t)2 * P->nxh * ny * nz);
-    if (nproc == 1 && nxl == 0) { P->g3[0] = gx; P->g3[1] = gy; P->g3[2] = gz; }
-    P->s_f.alloc(2 * n * ns); P->s_bct.alloc(2 * ns); P->s_v0.alloc(2 * n * ns); P->s_v1.alloc(2 * n * ns);
-    P->s_u0.alloc(2 * n * ns); P->s_u1.alloc(2 * n * ns); P->s_du0.alloc(2 * ns); P->s_du1.alloc(2 * ns); P->s_scr.alloc(5 * n * ns);
-    if (!helmholtz) build_fft(*P);
-    {   // fused 2-D (x,z) transforms are ~2x faster than r2c(x) + strided c2c(z) at 512^3, but rocFFT does not build them
-        // for every layout: fall back to the two 1-D plans when plan creation fails (TLAB_FFT2D=0 forces the 1-D path)
-        // ... and slower than r2c(x) + the own strided z-transform (fftz.hip: 0.49 + 0.53 ms against 1.14 ms at 512^3), so they are only
-        // built where that kernel does not apply (TLAB_FFTZ=0 or a length that is not 8^a * {1,2,4})
-        if (!helmholtz && nzt > 1 && nproc == 1 && nxl == 0 && !P->fz_own && env_int("TLAB_FFT2D", 1) != 0) {
-            try {
-                build_fft_2d(*P);
-                P->use_2d = true;
-            } catch (const std::exception &) {
-                P->use_2d = false;
-            }
-        }
-    }
-    create_side_stream(&P->side);
-    hipc(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming), "event");
-    hipc(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming), "event");
-    hipStream_t st = tlab_current_stream();
-    build_homogeneous(*P, st);
-    build_singular_homogeneous(*P, st);
-    {   // chunked ODE kernel (k_ode_nn) when the line splits into 8-row chunks and 32-bit indices suffice; tlab_poisson_set_exact(1)
-        // (or TLAB_ODE_CHUNKED=0) keeps the marching kernels, which repeat the reference's operations one by one
-        const bool want = !g_poisson_exact && env_int("TLAB_ODE_CHUNKED", 1) != 0;
-        const int C = ny / OM;
-        const long long big = std::max<long long>((long long)5 * ny * (nm + 64), std::max<long long>(9 * nm, (long long)P->nxh * ny * nz));
-        if (!P->generic && want && ny % OM == 0 && C >= 2 && ode_modes_per_wg(C) > 0 && big < (1LL << 31) &&
-            ode_lds_bytes(C, ode_modes_per_wg(C)) <= (size_t)160 * 1024) {
-            P->ode_nm_per_wg = ode_modes_per_wg(C);
-            {   // mirror pairs (see k_ode_nn): TLAB_ODE_PAIR=0 keeps one mode per thread
-                const int om = OM;
-                const int nzm = (int)(nm / P->nxh);
-                bool sym = env_int("TLAB_ODE_PAIR", 1) != 0 && nzm >= 4 && (om == 4 || om == 8) && ny % om == 0;
-                for (int kz = 1; sym && kz < nzm; ++kz)
-                    for (long long i = 0; i < P->nxh; ++i) sym = sym && lam[i + P->nxh * kz] == lam[i + P->nxh * (nzm - kz)];
-                const int Cp = ny / om, NMp = sym ? ode_modes_per_wg(Cp) : 0;
-                if (sym && NMp > 0 && ode_lds_bytes(Cp, NMp, om, 4) <= (size_t)160 * 1024) {
-                    P->ode_pair = true; P->ode_om = om; P->ode_nm_per_wg = NMp;
+        hipc(hipMalloc((void **)&P->d_skip, (size_t)nm), "hipMalloc");
+        hipc(hipMemcpy(P->d_skip, skip.data(), (size_t)nm, hipMemcpyHostToDevice), "hipMemcpy");
+        const int ns = (int)P->sing_modes.size();
+        hipc(hipMalloc((void **)&P->d_sing, (ns + 1) * sizeof(int)), "hipMalloc");
+        if (ns) hipc(hipMemcpy(P->d_sing, P->sing_modes.data(), ns * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy");
+        std::vector<double> slam(ns);
+        for (int s = 0; s < ns; ++s) slam[s] = lam[P->sing_modes[s]];
+        P->s_lam.upload(slam);
+        const size_t n = ny;
+        P->hom.alloc(5 * n * nm); P->der.alloc(3 * nm); P->cst.alloc(9 * nm);
+        P->scratch.alloc(6 * n * nm);      // NL + 3 components, NL <= 3
+        P->v0.alloc(2 * n * nm); P->u0.alloc(2 * n * nm); P->du0.alloc(2 * nm); P->bcs.alloc(4 * nm);
+        P->helmholtz = helmholtz;
+        if (!helmholtz) P->cwork.alloc((size_t)2 * P->nxh * ny * nz);
+        if (nproc == 1 && nxl == 0) { P->g3[0] = gx; P->g3[1] = gy; P->g3[2] = gz; }
+        P->s_f.alloc(2 * n * ns); P->s_bct.alloc(2 * ns); P->s_v0.alloc(2 * n * ns); P->s_v1.alloc(2 * n * ns);
+        P->s_u0.alloc(2 * n * ns); P->s_u1.alloc(2 * n * ns); P->s_du0.alloc(2 * ns); P->s_du1.alloc(2 * ns); P->s_scr.alloc(5 * n * ns);
+        if (!helmholtz) build_fft(*P);
+        {   // fused 2-D (x,z) transforms are ~2x faster than r2c(x) + strided c2c(z) at 512^3, but rocFFT does not build them
+            // for every layout: fall back to the two 1-D plans when plan creation fails (TLAB_FFT2D=0 forces the 1-D path)
+            // ... and slower than r2c(x) + the own strided z-transform (fftz.hip: 0.49 + 0.53 ms against 1.14 ms at 512^3), so they are only
+            // built where that kernel does not apply (TLAB_FFTZ=0 or a length that is not 8^a * {1,2,4})
+            if (!helmholtz && nzt > 1 && nproc == 1 && nxl == 0 && !P->fz_own && env_int("TLAB_FFT2D", 1) != 0) {
+                try {
+                    build_fft_2d(*P);
+                    P->use_2d = true;
+                } catch (const std::exception &) {
+                    P->use_2d = false;
                 }
             }
-            build_checkpoints(*P, st);
-            P->use_chunked = true;
-            if (ode_sing_nm(C) * C <= 512 && (int)P->sing_modes.size() <= ode_sing_nm(C) && ode_lds_bytes(C, ode_sing_nm(C)) <= (size_t)160 * 1024)
-                build_singular_checkpoints(*P, st);
-            else P->use_chunked = false;
         }
-    }
-    if (P->use_chunked) build_low_modes(*P, gy->t.nodes, lam, skip, st);
-    hipc(hipStreamSynchronize(st), "sync");
-    if (P->use_chunked) {   // the scratch of the marching kernels is not needed any more
-        P->scratch.alloc(0); P->v0.alloc(0); P->u0.alloc(0); P->hom.alloc(0);      // hom lives on in its blocked copy
-    }
-    *out = P.release();
-    POISSON_GUARD_END
+        create_side_stream(&P->side);
+        hipc(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming), "event");
+        hipc(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming), "event");
+        hipStream_t st = tlab_current_stream();
+        build_homogeneous(*P, st);
+        build_singular_homogeneous(*P, st);
+        {   // chunked ODE kernel (k_ode_nn) when the line splits into 8-row chunks and 32-bit indices suffice; tlab_poisson_set_exact(1)
+            // (or TLAB_ODE_CHUNKED=0) keeps the marching kernels, which repeat the reference's operations one by one
+            const bool want = !g_poisson_exact && env_int("TLAB_ODE_CHUNKED", 1) != 0;
+            const int C = ny / OM;
+            const long long big = std::max<long long>((long long)5 * ny * (nm + 64), std::max<long long>(9 * nm, (long long)P->nxh * ny * nz));
+            if (!P->generic && want && ny % OM == 0 && C >= 2 && ode_modes_per_wg(C) > 0 && big < (1LL << 31) &&
+                ode_lds_bytes(C, ode_modes_per_wg(C)) <= (size_t)160 * 1024) {
+                P->ode_nm_per_wg = ode_modes_per_wg(C);
+                {   // mirror pairs (see k_ode_nn): TLAB_ODE_PAIR=0 keeps one mode per thread
+                    const int om = OM;
+                    const int nzm = (int)(nm / P->nxh);
+                    bool sym = env_int("TLAB_ODE_PAIR", 1) != 0 && nzm >= 4 && (om == 4 || om == 8) && ny % om == 0;
+                    for (int kz = 1; sym && kz < nzm; ++kz)
+                        for (long long i = 0; i < P->nxh; ++i) sym = sym && lam[i + P->nxh * kz] == lam[i + P->nxh * (nzm - kz)];
+                    const int Cp = ny / om, NMp = sym ? ode_modes_per_wg(Cp) : 0;
+                    if (sym && NMp > 0 && ode_lds_bytes(Cp, NMp, om, 4) <= (size_t)160 * 1024) {
+                        P->ode_pair = true; P->ode_om = om; P->ode_nm_per_wg = NMp;
+                    }
+                }
+                build_checkpoints(*P, st);
+                P->use_chunked = true;
+                if (ode_sing_nm(C) * C <= 512 && (int)P->sing_modes.size() <= ode_sing_nm(C) && ode_lds_bytes(C, ode_sing_nm(C)) <= (size_t)160 * 1024)
+                    build_singular_checkpoints(*P, st);
+                else P->use_chunked = false;
+            }
+        }
+        if (P->use_chunked) build_low_modes(*P, gy->t.nodes, lam, skip, st);
+        hipc(hipStreamSynchronize(st), "sync");
+        if (P->use_chunked) {   // the scratch of the marching kernels is not needed any more
+            P->scratch.alloc(0); P->v0.alloc(0); P->u0.alloc(0); P->hom.alloc(0);      // hom lives on in its blocked copy
+        }
+        *out = P.release();
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 
 int tlab_poisson_plan_create(tlab_poisson_plan_t *out, tlab_fdm_plan_t gx, tlab_fdm_plan_t gy, tlab_fdm_plan_t gz, int nx, int ny,
@@ -882,7 +883,7 @@ static void poisson_dd_stage(tlab_poisson_plan_t P, double *f_hat, double *p_hat
 // ODE stage on the local modes: f_hat (complex (nxh, ny, kmax), unnormalised FFT output) -> p_hat, dp_hat.
 // p_hat may alias f_hat (the reference also overwrites); dp_hat must be a different array.
 static void poisson_ode_stage(tlab_poisson_plan_t P, double *f_hat, double *p_hat, double *dp_hat, hipStream_t st) {
-    if (P->direct) throw std::invalid_argument("direct elliptic plan: use tlab_poisson_direct_ode (there is no dp^/dy; dp/dy is OPR_Partial_Y of p)");
+    if (P->direct) throw Fail(TLAB_EINVAL, "direct elliptic plan: use tlab_poisson_direct_ode (there is no dp^/dy; dp/dy is OPR_Partial_Y of p)");
     const long long nm = P->nm;
     const int n = P->ny, nxh = P->nxh, ny = P->ny;
     hipc(hipEventRecord(P->ev_fork, st), "event record");
@@ -942,191 +943,201 @@ static void poisson_ode_stage(tlab_poisson_plan_t P, double *f_hat, double *p_ha
 
 int tlab_opr_poisson(tlab_poisson_plan_t P, int nx, int ny, int nz, int ibc, double *p, double *tmp1, double *tmp2,
                      const double *bcs_hb, const double *bcs_ht, double *dpdy) {
-    POISSON_GUARD_BEGIN
-    if (!P || !p || !tmp1 || !tmp2 || !bcs_hb || !bcs_ht) throw std::invalid_argument("tlab_opr_poisson: null argument");
-    const tlab_poisson_plan::VFinal vf = P->vfinal;      // the request holds for THIS call only, whatever its outcome
-    P->vfinal.armed = false;
-    if (vf.armed && (!dpdy || !tlab_internal_poisson_can_v_final(P))) throw std::invalid_argument("tlab_opr_poisson: internal: the fused v update was requested from a plan that cannot do it");
-    if (nx != P->nx || ny != P->ny || nz != P->nz) throw std::invalid_argument("tlab_opr_poisson: sizes do not match the plan");
-    if (P->nproc != 1 || P->nxh != P->fx_nxh || P->fx_nz != P->nz)
-        throw std::invalid_argument("tlab_opr_poisson: plan is a z-slab / kx-pencil plan; drive its stages with the transposes in between");
-    if (ibc != TLAB_BCS_NN && ibc != TLAB_BCS_DD && !P->direct) {
-        tlab_set_error("OPR_Poisson (factorized): BCS_NN and BCS_DD only, like the reference (opr_elliptic.f90:312-331)");
-        return TLAB_EUNSUPPORTED;
-    }
-    if (ibc < TLAB_BCS_DD || ibc > TLAB_BCS_NN) throw std::invalid_argument("tlab_opr_poisson: bad ibc");
-    if (p == tmp1 || p == tmp2 || tmp1 == tmp2 || dpdy == p || dpdy == tmp1 || dpdy == tmp2) throw std::invalid_argument("arrays must be distinct");
-    hipStream_t st = tlab_current_stream();
-    wall_planes(P, p, bcs_hb, bcs_ht, nz, st);      // BC planes into the forcing (opr_elliptic.f90:285-286)
-    P->forward_xz(p, tmp1, tmp2, st);
-    if (P->direct) {    // OPR_Poisson_FourierXZ_Direct (opr_elliptic.f90:368-455)
-        poisson_direct_stage(P, ibc, tmp1, tmp1, st);
-        P->backward_xz(tmp1, p, st);
-        if (dpdy) {     // :447-449, with the y plan of the derivatives
-            const int rc = tlab_opr_partial(2, P->gy_der, TLAB_OPR_P1, nx, ny, nz, 0, p, dpdy, tmp1);
-            if (rc != TLAB_OK) return rc;
+    return catch_fail([&]() -> int {
+        if (!P || !p || !tmp1 || !tmp2 || !bcs_hb || !bcs_ht) throw Fail(TLAB_EINVAL, "tlab_opr_poisson: null argument");
+        const tlab_poisson_plan::VFinal vf = P->vfinal;      // the request holds for THIS call only, whatever its outcome
+        P->vfinal.armed = false;
+        if (vf.armed && (!dpdy || !tlab_internal_poisson_can_v_final(P))) throw Fail(TLAB_EINVAL, "tlab_opr_poisson: internal: the fused v update was requested from a plan that cannot do it");
+        if (nx != P->nx || ny != P->ny || nz != P->nz) throw Fail(TLAB_EINVAL, "tlab_opr_poisson: sizes do not match the plan");
+        if (P->nproc != 1 || P->nxh != P->fx_nxh || P->fx_nz != P->nz)
+            throw Fail(TLAB_EINVAL, "tlab_opr_poisson: plan is a z-slab / kx-pencil plan; drive its stages with the transposes in between");
+        if (ibc != TLAB_BCS_NN && ibc != TLAB_BCS_DD && !P->direct) {
+            tlab_set_error("OPR_Poisson (factorized): BCS_NN and BCS_DD only, like the reference (opr_elliptic.f90:312-331)");
+            return TLAB_EUNSUPPORTED;
         }
+        if (ibc < TLAB_BCS_DD || ibc > TLAB_BCS_NN) throw Fail(TLAB_EINVAL, "tlab_opr_poisson: bad ibc");
+        if (p == tmp1 || p == tmp2 || tmp1 == tmp2 || dpdy == p || dpdy == tmp1 || dpdy == tmp2) throw Fail(TLAB_EINVAL, "arrays must be distinct");
+        hipStream_t st = tlab_current_stream();
+        wall_planes(P, p, bcs_hb, bcs_ht, nz, st);      // BC planes into the forcing (opr_elliptic.f90:285-286)
+        P->forward_xz(p, tmp1, tmp2, st);
+        if (P->direct) {    // OPR_Poisson_FourierXZ_Direct (opr_elliptic.f90:368-455)
+            poisson_direct_stage(P, ibc, tmp1, tmp1, st);
+            P->backward_xz(tmp1, p, st);
+            if (dpdy) {     // :447-449, with the y plan of the derivatives
+                const int rc = tlab_opr_partial(2, P->gy_der, TLAB_OPR_P1, nx, ny, nz, 0, p, dpdy, tmp1);
+                if (rc != TLAB_OK) return rc;
+            }
+            return TLAB_OK;
+        }
+        if (ibc == TLAB_BCS_DD) poisson_dd_stage(P, tmp1, tmp1, tmp2, st);
+        else poisson_ode_stage(P, tmp1, tmp1, tmp2, st);      // p^ -> tmp1 (over f^), dp^/dy -> tmp2
+        P->backward_xz(tmp1, p, st);
+        if (dpdy) P->backward_xz(tmp2, dpdy, st, &vf);
         return TLAB_OK;
-    }
-    if (ibc == TLAB_BCS_DD) poisson_dd_stage(P, tmp1, tmp1, tmp2, st);
-    else poisson_ode_stage(P, tmp1, tmp1, tmp2, st);      // p^ -> tmp1 (over f^), dp^/dy -> tmp2
-    P->backward_xz(tmp1, p, st);
-    if (dpdy) P->backward_xz(tmp2, dpdy, st, &vf);
-    POISSON_GUARD_END
+    }, TLAB_EHIP);
 }
 
 // ---- stages, for the z-slab (multi-GPU) driver: the K-transposes of OPR_Fourier_Z_* (opr_fourier.f90:343-376) happen between them ----
 int tlab_poisson_set_wall_planes(tlab_poisson_plan_t P, double *p, const double *bcs_hb, const double *bcs_ht) {
-    POISSON_GUARD_BEGIN
-    if (!P || !p || !bcs_hb || !bcs_ht) throw std::invalid_argument("null argument");
-    wall_planes(P, p, bcs_hb, bcs_ht, P->fx_nz, tlab_current_stream());
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        if (!P || !p || !bcs_hb || !bcs_ht) throw Fail(TLAB_EINVAL, "null argument");
+        wall_planes(P, p, bcs_hb, bcs_ht, P->fx_nz, tlab_current_stream());
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 // dir = +1: real (nx,ny,kmax) -> complex (nx/2+1,ny,kmax)  [OPR_Fourier_X_Forward]; dir = -1: the inverse [OPR_Fourier_X_Backward]
 // dir = -2: the inverse by the library's own kernel (k_fftx_c2r; the solver itself uses rocFFT's, which already runs at the copy rate) -- tests
 int tlab_poisson_fft_x(tlab_poisson_plan_t P, int dir, double *in, double *out) {
-    POISSON_GUARD_BEGIN
-    if (!P || !in || !out || in == out) throw std::invalid_argument("tlab_poisson_fft_x: bad arguments");
-    if (dir > 0) P->x_forward(in, out, tlab_current_stream());
-    else if (dir == -2) {
-        if (!P->fx_own) throw std::invalid_argument("tlab_poisson_fft_x: no own transform for this length");
-        P->fx_own->exec_inverse(in, out, tlab_current_stream());
-    } else P->fx_c2r.exec(in, out, tlab_current_stream());
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        if (!P || !in || !out || in == out) throw Fail(TLAB_EINVAL, "tlab_poisson_fft_x: bad arguments");
+        if (dir > 0) P->x_forward(in, out, tlab_current_stream());
+        else if (dir == -2) {
+            if (!P->fx_own) throw Fail(TLAB_EINVAL, "tlab_poisson_fft_x: no own transform for this length");
+            P->fx_own->exec_inverse(in, out, tlab_current_stream());
+        } else P->fx_c2r.exec(in, out, tlab_current_stream());
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 // The x-transforms with the complex side in the pack layout of tlab_pencil_repack_blocks (the repack pass folded into the transform):
 // dir = +1: real in (nx,ny,kmax) -> pack buffer out; dir = -1: pack buffer in -> real out.  Own kernels only.
 static void packed_check(tlab_poisson_plan_t P, const void *a, const void *b, int nblocks, const int *start, const long long *base, const char *who) {
-    if (!P || !a || !b || !start || !base || nblocks < 1 || nblocks > 16 || start[0] != 0) throw std::invalid_argument(std::string(who) + ": bad arguments");
+    if (!P || !a || !b || !start || !base || nblocks < 1 || nblocks > 16 || start[0] != 0) throw Fail(TLAB_EINVAL, std::string(who) + ": bad arguments");
     for (int p = 0; p + 1 < nblocks; ++p)
-        if (start[p + 1] < start[p] || start[p + 1] > P->fx_nxh) throw std::invalid_argument(std::string(who) + ": block starts must increase within [0, nx/2+1]");
+        if (start[p + 1] < start[p] || start[p + 1] > P->fx_nxh) throw Fail(TLAB_EINVAL, std::string(who) + ": block starts must increase within [0, nx/2+1]");
 }
 #define PACKED_NEEDS_OWN(P, who) if ((P) && !(P)->fx_own) { tlab_set_error(who ": no own transform for this length"); return TLAB_EUNSUPPORTED; }
 int tlab_poisson_fft_x_packed(tlab_poisson_plan_t P, int dir, double *in, double *out, int nblocks, const int *start, const long long *base) {
     PACKED_NEEDS_OWN(P, "tlab_poisson_fft_x_packed")
-    POISSON_GUARD_BEGIN
-    packed_check(P, in, out, nblocks, start, base, "tlab_poisson_fft_x_packed");
-    if (in == out) throw std::invalid_argument("tlab_poisson_fft_x_packed: out of place only");
-    const auto &m = P->kx_map(nblocks, start, base);
-    if (dir > 0) P->fx_own->exec(in, out, tlab_current_stream(), m.off, m.w);
-    else P->fx_own->exec_inverse(in, out, tlab_current_stream(), m.off, m.w);
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        packed_check(P, in, out, nblocks, start, base, "tlab_poisson_fft_x_packed");
+        if (in == out) throw Fail(TLAB_EINVAL, "tlab_poisson_fft_x_packed: out of place only");
+        const auto &m = P->kx_map(nblocks, start, base);
+        if (dir > 0) P->fx_own->exec(in, out, tlab_current_stream(), m.off, m.w);
+        else P->fx_own->exec_inverse(in, out, tlab_current_stream(), m.off, m.w);
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 // ... and the inverse of dp^/dy finishing the v equation (h = h - dp/dy, wall planes zeroed, q += dte h, h *= kco when scale) in its epilogue
 int tlab_poisson_fft_x_packed_final(tlab_poisson_plan_t P, double *in, double *q, double *h, double dte, double kco, int scale, int nblocks,
                                     const int *start, const long long *base) {
     PACKED_NEEDS_OWN(P, "tlab_poisson_fft_x_packed_final")
-    POISSON_GUARD_BEGIN
-    packed_check(P, in, q, nblocks, start, base, "tlab_poisson_fft_x_packed_final");
-    if (!h) throw std::invalid_argument("tlab_poisson_fft_x_packed_final: bad arguments");
-    const auto &m = P->kx_map(nblocks, start, base);
-    P->fx_own->exec_inverse_final(in, q, h, dte, kco, scale, (int)P->ny, tlab_current_stream(), m.off, m.w);
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        packed_check(P, in, q, nblocks, start, base, "tlab_poisson_fft_x_packed_final");
+        if (!h) throw Fail(TLAB_EINVAL, "tlab_poisson_fft_x_packed_final: bad arguments");
+        const auto &m = P->kx_map(nblocks, start, base);
+        P->fx_own->exec_inverse_final(in, q, h, dte, kco, scale, (int)P->ny, tlab_current_stream(), m.off, m.w);
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 // complex (nlines, nz_total) lines-fastest (the K-transposed layout; nlines = (nx/2+1)*ny/nproc_k), out of place; in == out with the own transform only
 int tlab_poisson_fft_z(tlab_poisson_plan_t P, int dir, double *in, double *out) {
-    POISSON_GUARD_BEGIN
-    if (!P || !in || !out || (in == out && !P->fz_own)) throw std::invalid_argument("tlab_poisson_fft_z: bad arguments");
-    if (P->nzt <= 1) throw std::invalid_argument("tlab_poisson_fft_z: no z direction");
-    P->z_exec(dir, in, out, tlab_current_stream());
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        if (!P || !in || !out || (in == out && !P->fz_own)) throw Fail(TLAB_EINVAL, "tlab_poisson_fft_z: bad arguments");
+        if (P->nzt <= 1) throw Fail(TLAB_EINVAL, "tlab_poisson_fft_z: no z direction");
+        P->z_exec(dir, in, out, tlab_current_stream());
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 // per-mode ODE solves on the local (kx, kz) modes: f_hat -> p_hat (may alias f_hat), dp_hat
 int tlab_poisson_ode(tlab_poisson_plan_t P, double *f_hat, double *p_hat, double *dp_hat) {
-    POISSON_GUARD_BEGIN
-    if (!P || !f_hat || !p_hat || !dp_hat || dp_hat == f_hat || dp_hat == p_hat) throw std::invalid_argument("tlab_poisson_ode: bad arguments");
-    poisson_ode_stage(P, f_hat, p_hat, dp_hat, tlab_current_stream());
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        if (!P || !f_hat || !p_hat || !dp_hat || dp_hat == f_hat || dp_hat == p_hat) throw Fail(TLAB_EINVAL, "tlab_poisson_ode: bad arguments");
+        poisson_ode_stage(P, f_hat, p_hat, dp_hat, tlab_current_stream());
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 
 // OPR_Helmholtz(nx, ny, nz, ibc, alpha, a, tmp1, tmp2, bcs_hb, bcs_ht): OPR_Helmholtz_FourierXZ_Direct (operators/opr_elliptic.f90:562-628) on a
 // direct plan, OPR_Helmholtz_FourierXZ_Factorize (:466-557) on a factorized one
 int tlab_opr_helmholtz(tlab_poisson_plan_t P, int nx, int ny, int nz, int ibc, double alpha, double *a, double *tmp1, double *tmp2,
                        const double *bcs_hb, const double *bcs_ht) {
-    POISSON_GUARD_BEGIN
-    if (!P || !a || !tmp1 || !tmp2 || !bcs_hb || !bcs_ht) throw std::invalid_argument("tlab_opr_helmholtz: null argument");
-    if (nx != P->nx || ny != P->ny || nz != P->nz) throw std::invalid_argument("tlab_opr_helmholtz: sizes do not match the plan");
-    if (ibc < TLAB_BCS_DD || ibc > TLAB_BCS_NN) throw std::invalid_argument("tlab_opr_helmholtz: bad ibc");
-    if (a == tmp1 || a == tmp2 || tmp1 == tmp2) throw std::invalid_argument("arrays must be distinct");
-    tlab_poisson_plan *H = nullptr;
-    if (!P->direct) {
-        if (ibc != TLAB_BCS_NN && ibc != TLAB_BCS_DD) {
-            tlab_set_error("OPR_Helmholtz (factorized): BCS_NN and BCS_DD only, like the reference (opr_elliptic.f90:524-532)");
-            return TLAB_EUNSUPPORTED;
-        }
-        if (!P->g3[0] || P->helmholtz) throw std::invalid_argument("tlab_opr_helmholtz: needs a single-device plan of tlab_poisson_plan_create");
-        for (size_t i = 0; i < P->helm.size(); ++i)
-            if (P->helm[i].first == alpha) {      // most recently used last
-                std::rotate(P->helm.begin() + i, P->helm.begin() + i + 1, P->helm.end());
-                H = P->helm.back().second.get();
-                break;
+    return catch_fail([&]() -> int {
+        if (!P || !a || !tmp1 || !tmp2 || !bcs_hb || !bcs_ht) throw Fail(TLAB_EINVAL, "tlab_opr_helmholtz: null argument");
+        if (nx != P->nx || ny != P->ny || nz != P->nz) throw Fail(TLAB_EINVAL, "tlab_opr_helmholtz: sizes do not match the plan");
+        if (ibc < TLAB_BCS_DD || ibc > TLAB_BCS_NN) throw Fail(TLAB_EINVAL, "tlab_opr_helmholtz: bad ibc");
+        if (a == tmp1 || a == tmp2 || tmp1 == tmp2) throw Fail(TLAB_EINVAL, "arrays must be distinct");
+        tlab_poisson_plan *H = nullptr;
+        if (!P->direct) {
+            if (ibc != TLAB_BCS_NN && ibc != TLAB_BCS_DD) {
+                tlab_set_error("OPR_Helmholtz (factorized): BCS_NN and BCS_DD only, like the reference (opr_elliptic.f90:524-532)");
+                return TLAB_EUNSUPPORTED;
             }
-        if (!H) {
-            tlab_poisson_plan_t h = nullptr;
-            const int rc = poisson_plan_create_impl(&h, P->g3[0], P->g3[1], P->g3[2], nx, ny, nz, nz, 0, 1, 0, 0, 0, nullptr, true, alpha);
-            if (rc != TLAB_OK) return rc;
-            if (P->helm.size() >= 4) P->helm.erase(P->helm.begin());
-            P->helm.emplace_back(alpha, std::unique_ptr<tlab_poisson_plan>(h));
-            H = h;
+            if (!P->g3[0] || P->helmholtz) throw Fail(TLAB_EINVAL, "tlab_opr_helmholtz: needs a single-device plan of tlab_poisson_plan_create");
+            for (size_t i = 0; i < P->helm.size(); ++i)
+                if (P->helm[i].first == alpha) {      // most recently used last
+                    std::rotate(P->helm.begin() + i, P->helm.begin() + i + 1, P->helm.end());
+                    H = P->helm.back().second.get();
+                    break;
+                }
+            if (!H) {
+                tlab_poisson_plan_t h = nullptr;
+                const int rc = poisson_plan_create_impl(&h, P->g3[0], P->g3[1], P->g3[2], nx, ny, nz, nz, 0, 1, 0, 0, 0, nullptr, true, alpha);
+                if (rc != TLAB_OK) return rc;
+                if (P->helm.size() >= 4) P->helm.erase(P->helm.begin());
+                P->helm.emplace_back(alpha, std::unique_ptr<tlab_poisson_plan>(h));
+                H = h;
+            }
         }
-    }
-    hipStream_t st = tlab_current_stream();
-    wall_planes(P, a, bcs_hb, bcs_ht, nz, st);
-    P->forward_xz(a, tmp1, tmp2, st);
-    if (P->direct) poisson_direct_stage(P, ibc, tmp1, tmp1, st, true, alpha);
-    else if (ibc == TLAB_BCS_DD) poisson_dd_stage(H, tmp1, tmp1, tmp2, st);      // u over f^; v = u' + sqrt(lambda - alpha) u (not returned) in tmp2
-    else poisson_ode_stage(H, tmp1, tmp1, tmp2, st);
-    P->backward_xz(tmp1, a, st);
-    POISSON_GUARD_END
+        hipStream_t st = tlab_current_stream();
+        wall_planes(P, a, bcs_hb, bcs_ht, nz, st);
+        P->forward_xz(a, tmp1, tmp2, st);
+        if (P->direct) poisson_direct_stage(P, ibc, tmp1, tmp1, st, true, alpha);
+        else if (ibc == TLAB_BCS_DD) poisson_dd_stage(H, tmp1, tmp1, tmp2, st);      // u over f^; v = u' + sqrt(lambda - alpha) u (not returned) in tmp2
+        else poisson_ode_stage(H, tmp1, tmp1, tmp2, st);
+        P->backward_xz(tmp1, a, st);
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 
 // direct plans: FDM_Int2_Solve of the local modes, f_hat -> p_hat (may alias)
 int tlab_poisson_direct_ode(tlab_poisson_plan_t P, int ibc, double *f_hat, double *p_hat) {
-    POISSON_GUARD_BEGIN
-    if (!P || !f_hat || !p_hat) throw std::invalid_argument("tlab_poisson_direct_ode: bad arguments");
-    if (!P->direct) throw std::invalid_argument("tlab_poisson_direct_ode: not a direct plan");
-    if (ibc < TLAB_BCS_DD || ibc > TLAB_BCS_NN) throw std::invalid_argument("tlab_poisson_direct_ode: bad ibc");
-    poisson_direct_stage(P, ibc, f_hat, p_hat, tlab_current_stream());
-    POISSON_GUARD_END
+    return catch_fail([&]() -> int {
+        if (!P || !f_hat || !p_hat) throw Fail(TLAB_EINVAL, "tlab_poisson_direct_ode: bad arguments");
+        if (!P->direct) throw Fail(TLAB_EINVAL, "tlab_poisson_direct_ode: not a direct plan");
+        if (ibc < TLAB_BCS_DD || ibc > TLAB_BCS_NN) throw Fail(TLAB_EINVAL, "tlab_poisson_direct_ode: bad ibc");
+        poisson_direct_stage(P, ibc, f_hat, p_hat, tlab_current_stream());
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 
 
 // include/tlab_amd.h: debug aid -- one FDM_Int1_Solve of the 3- / 7-diagonal path on the device (k_int1g), two lines per mode, for tests
 int tlab_debug_int1_solve(tlab_fdm_plan_t gy, int ibc, int variant, int nm, const double *lam, const double *f, const double *bv, double *res, double *du) {
-    POISSON_GUARD_BEGIN
-    if (!gy || !lam || !f || !bv || !res || !du || nm < 1 || (ibc != 1 && ibc != 2)) throw std::invalid_argument("tlab_debug_int1_solve: bad arguments");
-    if (!tlab_device_ready()) throw std::runtime_error("tlab_init has not been called");
-    const int n = gy->t.n;
-    Int1Gen G;
-    int1_generic_build(gy->t.der1, ibc, lam, nm, 1.0, G);
-    DBuf fac, rb, rt, R, df, dbv, dres, ddu, scr;
-    fac.upload(G.fac); rb.upload(G.rb); rt.upload(G.rt); R.upload(G.R);
-    df.upload(std::vector<double>(f, f + (size_t)2 * n * nm));
-    dbv.upload(std::vector<double>(bv, bv + (size_t)2 * nm));
-    dres.alloc((size_t)2 * n * nm); ddu.alloc((size_t)2 * nm); scr.alloc((size_t)5 * n * nm);
-    Int1Args a{};
-    a.T.n = n; a.nm = nm; a.fscale = 1.0; a.fsrc = df.p; a.nlf = 2; a.bv_ptr = dbv.p; a.dst = dres.p; a.du = ddu.p; a.scratch = scr.p;
-    a.g_fac = fac.p; a.g_rb = rb.p; a.g_rt = rt.p; a.g_R = R.p; a.g_ndi = G.ndi; a.g_nri = G.nri;
-    hipStream_t st = tlab_current_stream();
-    if (variant == 1) {                 // FS_UNIT variants of build_homogeneous / build_singular_homogeneous
-        a.bv_ptr = nullptr; a.bv[0] = 0.0; a.bv[1] = 1.0; a.bv[2] = 0.0;
-        if (ibc == 1) { a.unit_row = n - 1; launch_int1<1, 2, FS_UNIT>(a, st); }
-        else { a.unit_row = 0; launch_int1<2, 2, FS_UNIT>(a, st); }
-    } else if (variant == 2) {          // three lines, two stored (build_homogeneous, u-solve); ibc = 2
-        DBuf d3, u3;
-        d3.alloc((size_t)3 * n * nm); u3.alloc((size_t)3 * nm);
-        a.bv_ptr = nullptr; a.bv[0] = 0.0; a.bv[1] = 0.0; a.bv[2] = 1.0;
-        a.dst = d3.p; a.du = u3.p;
-        launch_int1<2, 3, FS_LINEAR>(a, st);
+    return catch_fail([&]() -> int {
+        if (!gy || !lam || !f || !bv || !res || !du || nm < 1 || (ibc != 1 && ibc != 2)) throw Fail(TLAB_EINVAL, "tlab_debug_int1_solve: bad arguments");
+        if (!tlab_device_ready()) throw Fail(TLAB_EHIP, "tlab_init has not been called");
+        const int n = gy->t.n;
+        Int1Gen G;
+        int1_generic_build(gy->t.der1, ibc, lam, nm, 1.0, G);
+        DBuf fac, rb, rt, R, df, dbv, dres, ddu, scr;
+        fac.upload(G.fac); rb.upload(G.rb); rt.upload(G.rt); R.upload(G.R);
+        df.upload(std::vector<double>(f, f + (size_t)2 * n * nm));
+        dbv.upload(std::vector<double>(bv, bv + (size_t)2 * nm));
+        dres.alloc((size_t)2 * n * nm); ddu.alloc((size_t)2 * nm); scr.alloc((size_t)5 * n * nm);
+        Int1Args a{};
+        a.T.n = n; a.nm = nm; a.fscale = 1.0; a.fsrc = df.p; a.nlf = 2; a.bv_ptr = dbv.p; a.dst = dres.p; a.du = ddu.p; a.scratch = scr.p;
+        a.g_fac = fac.p; a.g_rb = rb.p; a.g_rt = rt.p; a.g_R = R.p; a.g_ndi = G.ndi; a.g_nri = G.nri;
+        hipStream_t st = tlab_current_stream();
+        if (variant == 1) {                 // FS_UNIT variants of build_homogeneous / build_singular_homogeneous
+            a.bv_ptr = nullptr; a.bv[0] = 0.0; a.bv[1] = 1.0; a.bv[2] = 0.0;
+            if (ibc == 1) { a.unit_row = n - 1; launch_int1<1, 2, FS_UNIT>(a, st); }
+            else { a.unit_row = 0; launch_int1<2, 2, FS_UNIT>(a, st); }
+        } else if (variant == 2) {          // three lines, two stored (build_homogeneous, u-solve); ibc = 2
+            DBuf d3, u3;
+            d3.alloc((size_t)3 * n * nm); u3.alloc((size_t)3 * nm);
+            a.bv_ptr = nullptr; a.bv[0] = 0.0; a.bv[1] = 0.0; a.bv[2] = 1.0;
+            a.dst = d3.p; a.du = u3.p;
+            launch_int1<2, 3, FS_LINEAR>(a, st);
+            hipc(hipStreamSynchronize(st), "sync");
+            hipc(hipMemcpy(dres.p, d3.p + (size_t)n * nm, (size_t)2 * n * nm * sizeof(double), hipMemcpyDeviceToDevice), "copy");      // lines 1, 2
+            hipc(hipMemcpy(ddu.p, u3.p + (size_t)nm, (size_t)2 * nm * sizeof(double), hipMemcpyDeviceToDevice), "copy");
+        } else if (ibc == 1) launch_int1<1, 2, FS_LINEAR>(a, st);
+        else launch_int1<2, 2, FS_LINEAR>(a, st);
         hipc(hipStreamSynchronize(st), "sync");
-        hipc(hipMemcpy(dres.p, d3.p + (size_t)n * nm, (size_t)2 * n * nm * sizeof(double), hipMemcpyDeviceToDevice), "copy");      // lines 1, 2
-        hipc(hipMemcpy(ddu.p, u3.p + (size_t)nm, (size_t)2 * nm * sizeof(double), hipMemcpyDeviceToDevice), "copy");
-    } else if (ibc == 1) launch_int1<1, 2, FS_LINEAR>(a, st);
-    else launch_int1<2, 2, FS_LINEAR>(a, st);
-    hipc(hipStreamSynchronize(st), "sync");
-    hipc(hipMemcpy(res, dres.p, (size_t)2 * n * nm * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy");
-    hipc(hipMemcpy(du, ddu.p, (size_t)2 * nm * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy");
-    POISSON_GUARD_END
+        hipc(hipMemcpy(res, dres.p, (size_t)2 * n * nm * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy");
+        hipc(hipMemcpy(du, ddu.p, (size_t)2 * nm * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy");
+        return TLAB_OK;
+    }, TLAB_EHIP);
 }
 
 }  // extern "C"

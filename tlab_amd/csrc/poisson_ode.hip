@@ -724,7 +724,7 @@ void launch_ode(tlab_poisson_plan &P, double *f_hat, double *p_hat, double *dp_h
     ProfScope ps(dd ? "k_ode_nn<DD>" : "k_ode_nn", st, (double)P.nm * P.ny * 48.0);      // algorithmic bytes: f^ in, p^ and dp^/dy out (its own tables -- checkpoints 12 B, the band of the homogeneous solutions -- come on top)
     // The pair form: 8 rows x 4 lines per thread (256 VGPRs, ~20 of them spilled) beats 4 rows x 4 lines in twice as many chunks (217 VGPRs, but 512-thread
     // workgroups that do not share a CU and a scan twice as long): 1.86 against 2.83 ms at 512^3, one mode per thread 2.30 (profiles/r03)
-    if (P.ode_pair && P.ode_om != OM) throw std::logic_error("k_ode_nn: no pair form for this geometry");
+    if (P.ode_pair && P.ode_om != OM) throw Fail(TLAB_EHIP, "k_ode_nn: no pair form for this geometry");
     dispatch_nm(P.ode_nm_per_wg, [&](auto nm_c) {
         constexpr int NM = decltype(nm_c)::value;
         if (P.ode_pair) dd ? launch_ode_nm<NM, true, 4>(a, lds, st) : launch_ode_nm<NM, false, 4>(a, lds, st);

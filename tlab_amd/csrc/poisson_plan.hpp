@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/tlab_amd.h"
+#include "errors.hpp"
 #include "internal.hpp"
 #include "plan.hpp"
 #include "fftz.hpp"
@@ -93,10 +94,10 @@ struct Int2Dev {
 // host helpers
 // ------------------------------------------------------------------------------------------------
 inline void hipc(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("HIP ") + what + ": " + hipGetErrorString(e));
+    if (e != hipSuccess) throw Fail(TLAB_EHIP, std::string("HIP ") + what + ": " + hipGetErrorString(e));
 }
 inline void fftc(rocfft_status s, const char *what) {
-    if (s != rocfft_status_success) throw std::runtime_error(std::string("rocFFT ") + what + " failed (status " + std::to_string((int)s) + ")");
+    if (s != rocfft_status_success) throw Fail(TLAB_EHIP, std::string("rocFFT ") + what + " failed (status " + std::to_string((int)s) + ")");
 }
 // an integer switch of the environment; the caller decides when it is read (per call, per plan creation, or once per process through a static)
 inline int env_int(const char *name, int dflt) {
@@ -191,7 +192,7 @@ struct tlab_poisson_plan {
         for (const auto &e : gen)
             if (e->which == which && e->lam == lam_dev && e->nm == nm_) return *e;
         std::vector<double> hl((size_t)nm_);
-        if (hipMemcpy(hl.data(), lam_dev, (size_t)nm_ * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("hipMemcpy (lambda)");
+        if (hipMemcpy(hl.data(), lam_dev, (size_t)nm_ * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) throw Fail(TLAB_EHIP, "hipMemcpy (lambda)");
         Int1Gen G;
         int1_generic_build(gder, which == 0 ? 1 : 2, hl.data(), nm_, which == 0 ? 1.0 : -1.0, G);
         auto e = std::make_unique<GenSet>();
@@ -267,7 +268,7 @@ struct tlab_poisson_plan {
         for (const KxMap &m : kxmaps) if (m.key == key) return m;
         std::vector<long long> off((size_t)fx_nxh);
         std::vector<int> w((size_t)fx_nxh);
-        if (tlab_debug_pack_map(fx_nxh, nblocks, start, base, off.data(), w.data()) != TLAB_OK) throw std::invalid_argument("pack map: bad block map");
+        if (tlab_debug_pack_map(fx_nxh, nblocks, start, base, off.data(), w.data()) != TLAB_OK) throw Fail(TLAB_EINVAL, "pack map: bad block map");
         KxMap m;
         m.key = key;
         hipc(hipMalloc((void **)&m.off, off.size() * sizeof(long long)), "hipMalloc");
@@ -369,17 +370,3 @@ void launch_ode_sing(tlab_poisson_plan &P, double *f_hat, double *p_hat, double 
 void poisson_direct_stage(tlab_poisson_plan_t P, int ibc, double *f_hat, double *p_hat, hipStream_t st, bool helmholtz = false, double alpha = 0.0);
 
 }  // namespace tlab
-
-// every C entry point of the solver: exceptions become the error string and a status
-#define POISSON_GUARD_BEGIN try {
-#define POISSON_GUARD_END                           \
-    return TLAB_OK;                                 \
-    }                                               \
-    catch (const std::invalid_argument &e) {        \
-        tlab_set_error(e.what());                   \
-        return TLAB_EINVAL;                         \
-    }                                               \
-    catch (const std::exception &e) {               \
-        tlab_set_error(e.what());                   \
-        return TLAB_EHIP;                           \
-    }

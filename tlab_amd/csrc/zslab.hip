@@ -554,11 +554,14 @@ int tlab_zslab_plan_create(tlab_zslab_plan_t *out, tlab_fdm_plan_t gz, int kmax,
         if ((M != 16 && M != 32) || kmax % M || kmax / M > 8 || kmax / M < 1)
             throw Fail(TLAB_EUNSUPPORTED, "z-slab operators: kmax must be a multiple of 16 or 32 with at most 8 sub-chunks");
         P->M = M; P->C = kmax / M;
-        const StencilDev s1 = gz->stencil(1, 0), s2 = gz->stencil(2, 0);
+        StencilDev s1, s2;
+        TriDiag T1, T2;
+        const int rc = catch_fail([&] { s1 = gz->stencil(1, 0); s2 = gz->stencil(2, 0); T1 = gz->tridiag(1, 0); T2 = gz->tridiag(2, 0); }, TLAB_EINVAL);
+        if (rc != TLAB_OK) throw Fail(TLAB_EINVAL, tlab_last_error());      // a scheme these operators do not take is a bad argument HERE
         P->c2_1 = s1.c2;
         P->c0_2 = s2.c0; P->c2_2 = s2.c2; P->c3_2 = s2.c3;
-        build_system(*P, gz->tridiag(1, 0), P->sys[0]);
-        build_system(*P, gz->tridiag(2, 0), P->sys[1]);
+        build_system(*P, T1, P->sys[0]);
+        build_system(*P, T2, P->sys[1]);
         *out = P.release();
     });
 }
