@@ -15,7 +15,15 @@ becomes its middle row in every row, bit-identical (the periodic kernels take th
            tables: 2.5e-27 and 8.4e-24 for three slabs of 64 planes, far less for thicker ones); the systems stay well conditioned (condition
            number 7.0 at most, tests/test_periodic_tables_host.py),
 
-and is factorized again with the oracle's TRIDPFS into lu.  device_plan hands the very same arrays to tlab_fdm_plan_create_from_arrays."""
+and is factorized again with the oracle's TRIDPFS into lu.  device_plan hands the very same arrays to tlab_fdm_plan_create_from_arrays.
+
+Scheme m = (5, 7) (CompactJacobian6Penta; tests/test_gpu_penta_lines.py: k_pentatile, k_penta1): the first derivative has five left-hand
+diagonals and seven right-hand ones.  The same three kinds act on its five coefficients per row (`varying`: five independent factors), the
+right-hand side is its middle row in every row, lu comes from the oracle's PENTADPFS (7 columns: five factors and the two vectors of the
+rank-two correction), and the library factorizes the lhs it is given itself; the second derivative stays tridiagonal and is treated as above.
+With AMPLITUDE = 0.05 the condition number of the cyclic matrix is 72.4 at most (37.5 uniform) and the response to unit inflow after a chunk
+of 32 rows 6e-10 .. 5e-8.  PENTADPFS inverts a matrix that differs from the cyclic one in two corner entries as soon as rows differ (DESIGN.md
+section 2, defect 15): the oracle, never a dense solve, is the reference on these tables."""
 import numpy as np
 
 KINDS = ("equal", "wander", "varying")
@@ -30,12 +38,12 @@ def nodes(n):
 
 
 def refactor(dp):
-    """dp.lu from dp.lhs (TRIDPFS on copies of the three diagonals)"""
+    """dp.lu from dp.lhs: TRIDPFS on copies of the three diagonals (5 columns), PENTADPFS on copies of the five (7 columns)"""
     from oracle import tlab_oracle as O
     n, ndl = dp.lhs.shape[0], dp.nb_diag[0]
-    assert ndl == 3, "tridiagonal left-hand sides only"
+    assert ndl in (3, 5), "tridiagonal and pentadiagonal left-hand sides only"
     cols = [dp.lhs[:, k].copy() if k < ndl else np.zeros(n) for k in range(ndl + 2)]
-    O.tridpfs(*cols)
+    (O.tridpfs if ndl == 3 else O.pentadpfs)(*cols)
     dp.lu = np.stack(cols, axis=1)
 
 
@@ -48,15 +56,16 @@ def make_plan(n, kind, m=(6, 7), amplitude=AMPLITUDE, roll=0, swap=None):
     mid = n // 2
     for which, dp in ((1, og.der1), (2, og.der2)):
         rng = np.random.default_rng([n, which, KINDS.index(kind), m[0], m[1]])
-        row = dp.lhs[mid, :3].copy()
+        ndl = dp.nb_diag[0]                      # 3; 5 for the first derivative of scheme (5, 7)
+        row = dp.lhs[mid, :ndl].copy()
         if kind == "equal":
-            f = np.ones((n, 3))
+            f = np.ones((n, ndl))
         elif kind == "wander":
-            f = np.repeat(1.0 + WANDER * rng.uniform(-1, 1, (n, 1)), 3, axis=1)
+            f = np.repeat(1.0 + WANDER * rng.uniform(-1, 1, (n, 1)), ndl, axis=1)
         else:
-            f = 1.0 + amplitude * rng.uniform(-1, 1, (n, 3))
+            f = 1.0 + amplitude * rng.uniform(-1, 1, (n, ndl))
         lhs = np.zeros_like(dp.lhs)
-        lhs[:, :3] = row[None, :] * f
+        lhs[:, :ndl] = row[None, :] * f
         if roll:
             lhs = np.roll(lhs, roll, axis=0)
         if swap is not None:
@@ -83,26 +92,27 @@ def host_tables(og):
 
 
 def device_plan(T, og):
-    """tlab_amd.FdmPlan from the oracle plan's arrays (operators only: no wavenumbers)"""
-    return T.FdmPlan.from_arrays(og.size, True, 0, *host_tables(og))
+    """tlab_amd.FdmPlan from the oracle plan's arrays (operators only: no wavenumbers).  A pentadiagonal lhs1 is factorized by the library itself
+    (tlab_fdm_plan_create_from_arrays: the reference's PENTADPFS restated in C++)."""
+    return T.FdmPlan.from_arrays(og.size, True, 0, *host_tables(og), ndl1=og.der1.nb_diag[0])
 
 
 def device_plan_for_driver(T, og):
     """... with what the Poisson solver and the monitors take from a plan besides: the uniform plan's modified wavenumbers, Jacobian and nodes"""
+    assert og.der1.nb_diag[0] == 3, "the drivers take tridiagonal first derivatives only"
     lhs1, rhs1, lhs2, rhs2 = host_tables(og)
     tab = {"ndr1": og.der1.nb_diag[1], "ndr2": og.der2.nb_diag[1], "need_1der": 0, "lhs1": lhs1, "rhs1": rhs1, "lhs2": lhs2, "rhs2": rhs2,
            "mwn1": og.der1.mwn, "mwn2": og.der2.mwn, "jac": og.jac, "nodes": og.nodes}
     return T.FdmPlan.from_tables(tab, periodic=True, scheme1=og.der1.mode_fdm, scheme2=og.der2.mode_fdm)
 
 
-def cyclic_matrix(lhs):
-    """dense matrix of the cyclic tridiagonal system: row i holds lhs[i, 0] at column i - 1, lhs[i, 1] at i, lhs[i, 2] at i + 1 (mod n)"""
+def cyclic_matrix(lhs, ndl=3):
+    """dense matrix of the cyclic system with ndl = 3 or 5 diagonals: row i holds lhs[i, k] at column i + k - ndl // 2 (mod n)"""
     n = lhs.shape[0]
     A = np.zeros((n, n))
     i = np.arange(n)
-    A[i, (i - 1) % n] = lhs[:, 0]
-    A[i, i] = lhs[:, 1]
-    A[i, (i + 1) % n] = lhs[:, 2]
+    for k in range(ndl):
+        A[i, (i + k - ndl // 2) % n] = lhs[:, k]
     return A
 
 
@@ -120,7 +130,7 @@ def right_hand_side(og, which, u):
 
 
 def solve(og, which, u):
-    """derivative `which` of the lines u (n, lines) by the oracle: right-hand side + TRIDPSS on og's lu"""
+    """derivative `which` of the lines u (n, lines) by the oracle: right-hand side + TRIDPSS (PENTADPSS for five diagonals) on og's lu"""
     from oracle import tlab_oracle as O
     if which == 1:
         return O.der1_solve(og.der1, 0, u)

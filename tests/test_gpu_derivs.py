@@ -96,7 +96,9 @@ def test_penta_first_derivative(T, nx, ny, nz):
     """SpaceOrder1 = CompactJacobian6Penta (fdm_com1_jacobian.f90:136-192; k_pentatile on lines of 64 .. 512 points in 32-row chunks -- 96, 64, 256, 512,
     128 here --, k_penta1, one line per thread, on the others) in the three directions, all
     operator types and the Burgers operator, against the oracle (itself bitwise equal to the reference for this scheme, tests/golden/
-    derivs_penta_*.npz); the plan also built from the host's tables (tlab_fdm_plan_create_from_arrays, ndl1 = 5)."""
+    derivs_penta_*.npz); the plan also built from the host's tables (tlab_fdm_plan_create_from_arrays, ndl1 = 5).
+    Uniform periodic grids, whole tiles, 2 / 3 / 4 / 8 / 16 chunks only: tables whose rows differ, odd chunk counts, partial tiles, non-periodic
+    x and z lines, k_penta1 along x, guard zones and the forms behind environment switches are in tests/test_gpu_penta_lines.py."""
     from oracle import tlab_oracle as O
     x, y, z = grids(nx, ny, nz, ystretch=True)
     u, v = fields(nx, ny, nz, 5 * nx + ny)

@@ -351,7 +351,7 @@ int tlab_fdm_plan_create_from_arrays(tlab_fdm_plan_t *out, int n, int periodic, 
                                      const double *rhs2) {
     return catch_fail([&] {
         if (!out || n < 8 || !lhs1 || !rhs1 || !lhs2 || !rhs2) throw Fail(TLAB_EINVAL, "tlab_fdm_plan_create_from_arrays: bad arguments");
-        const bool penta = (ndl1 == 5 && ndr1 == 7);      // CompactJacobian6Penta first derivative (generic kernel, reference operation order)
+        const bool penta = (ndl1 == 5 && ndr1 == 7);      // CompactJacobian6Penta first derivative (k_pentatile on lines of 64 .. 512 points in 32-row chunks, else k_penta1 in the reference's operation order)
         if ((ndl1 != 3 && !penta) || ndl2 != 3) throw Fail(TLAB_EUNSUPPORTED, "LHS: 3 diagonals (first derivative: or 5 with 7 RHS diagonals, CompactJacobian6Penta)");
         if ((!penta && ndr1 != 3 && ndr1 != 5) || (ndr2 != 5 && ndr2 != 7)) throw Fail(TLAB_EUNSUPPORTED, "unsupported number of RHS diagonals");
         auto p = std::make_unique<tlab_fdm_plan>();

@@ -97,7 +97,7 @@ namespace {
 
 int choose_path(int dir, int n, tlab_fdm_plan_t g = nullptr) {
     int path = PATH_GENERIC;
-    if (g && g->t.der1.ndl == 5) return PATH_GENERIC;      // CompactJacobian6Penta: the first derivative runs on k_penta1, nothing is fused
+    if (g && g->t.der1.ndl == 5) return PATH_GENERIC;      // CompactJacobian6Penta: run_generic sends the first derivative to k_pentatile / k_penta1, nothing is fused
     if (g && g->t.der1.direct && dir == 1) return PATH_GENERIC;      // per-row first-derivative RHS: not in the wave-per-line kernel
     if (dir == 1 && xline_chunks(n, g) > 0) path = PATH_XLINE;
     if (dir != 1 && (rtile_chunk(n) > 0 || htile_chunk(n, MODE_P1) > 0)) path = PATH_RTILE;
