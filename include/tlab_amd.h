@@ -914,6 +914,9 @@ int tlab_pdf_histogram_planes(int nx, int ny, int nz, int nv, int nbins, const i
 int tlab_pdf_analize(int ibc, int nbins, const double *pdf, double *umin, double *umax, double plim, int *nplim);
 int tlab_pdf2v(int nx, int ny, int nz, const int *nbins, const double *u, const double *v, double *pdf);
 int tlab_gate_threshold(const double *a, long long n, double thr, signed char *gate);
+/* The conditional statistics that continue this block -- the partition of FI_GATE, AVG_N_XZ with a gate, RAW_TO_CENTRAL, CAVG1V_N and CAVG2V:
+ * tlab_gate_levels, tlab_gate_flux, tlab_dns_gate, tlab_avg_n_xz, tlab_raw_to_central, tlab_cavg1v_n, tlab_cavg2v -- are entry points of the same
+ * library, declared with their contract in tlab_amd/csrc/tlab_amd_conditional.h, which includes this header. */
 
 /* RHS_GLOBAL_INCOMPRESSIBLE_1()  tools/dns/rhs_global_incompressible_1.f90:15-405 (argument-less in the reference:
  * it works on the module arrays q, s, hq, hs, txc and on dte).  q[3] = u,v,w; s[nscal]; hq[3], hs[nscal] are

@@ -282,6 +282,27 @@ hipError_t launch_gate_threshold(const double *a, long long n, double thr, signe
 //                      inter: [np][ny] = count / real(nx * nz)
 hipError_t launch_gate_count(const signed char *gate, int nx, int ny, int nz, int np, unsigned *cnt, double *inter, hipStream_t st);
 
+// conditional.hip: the partition of FI_GATE, the gated moments and the conditional averages (conditional_host.hpp holds the level of a point, the
+// integer power and the limits).  Nothing is copied or synchronised here; F as above (launch_gated_moments: gate null = every point has level 1,
+// igate is not read).
+//   launch_gate_levels    thr: HOST, igate_size - 1 ascending thresholds, copied by value
+//   launch_gated_moments  the levels g0 .. g0 + COND_LEVELS_PER_LAUNCH - 1 (those above L are dropped) and the moments 1 .. nm of the F.nv fields
+//                         that are the fields v0 .. of nvt: partial: scratch, F.nv * pdf_chunks(nz) * ny * COND_LEVELS_PER_LAUNCH *
+//                         gated_moments_width(nm) doubles; cnt: scratch, pdf_chunks(nz) * ny * COND_LEVELS_PER_LAUNCH 32-bit words; sums
+//                         (ny, nm, nvt, L) and nsample (ny, L) in Fortran order: the raw undivided sums and the counts
+//   launch_cavg_sum       the sums of a and the counts per bin of every F.f[v] (nb2 == 0: nb1 bins, intervals iv as launch_pdf_hist) or of
+//                         (F.f[0], v2) (nb2 > 0: viv as launch_pdf2v_hist, bin (up, vp) at vp * nb1 + up); psum: scratch, F.nv * pdf_chunks(nz) *
+//                         ny * 2 * nbins doubles, pcnt: as many 32-bit words; volsum: scratch, F.nv * ny * nbins doubles, volcnt: as many 64-bit
+//                         words; sum, cnt: [F.nv][ny + 1][nbins] doubles (plane ny: the volume, written when ny > 1)
+int gated_moments_width(int nm);
+hipError_t launch_gate_levels(const double *a, long long n, int igate_size, const double *thr, signed char *gate, hipStream_t st);
+hipError_t launch_gate_flux(const double *a, const double *v, long long n, signed char *gate, hipStream_t st);
+hipError_t launch_gated_moments(const PdfFields &F, int nm, int g0, int L, int v0, int nvt, double *partial, unsigned *cnt, double *sums,
+                                long long *nsample, hipStream_t st);
+hipError_t launch_cavg_sum(const PdfFields &F, const double *v2, const double *a, int nb1, int nb2, unsigned ext_mask, const double *iv,
+                           const double *viv, double *psum, unsigned *pcnt, double *volsum, unsigned long long *volcnt, double *sum, double *cnt,
+                           hipStream_t st);
+
 // spectra.hip: plane spectra and correlations (index maps and ring lists: spectra_host.hpp).  Nothing is copied or synchronised here; every array is
 // device memory.  a, b: complex (nx/2+1, ny, nz), natural kz; b null: an auto pair.
 //   launch_spectrum_reduce     S: scratch, (nx/2) * (ny/nblock) * nz doubles; rowv: scratch, ny * nz doubles; ring_off [kr_total + 1], ring_mode: the

@@ -710,6 +710,38 @@ class Dns:
         gate = gate_threshold(vort[: self.n], (1.0e-3 * 1.0e-3) * mx.value)
         return {"Vorticity": inter_n_xz(self.nx, self.ny, self.nz, 1, gate)[0]}
 
+    def FI_GATE(self, opt_cond, thresholds, relative=False, scal=None):
+        """mappings/fi_gate.f90:3 for opt_cond 2 .. 7: the partition of the box as an int8 tensor.  2: scalar `scal` (1-based, default 1), 3: the
+        vorticity, 4: the scalar gradient, 5: the vertical velocity, 6: the scalar fluctuation, 7: the quadrants of the scalar fluctuation and v
+        (no thresholds).  thresholds: ascending, one fewer than levels; relative: multiplied by (umax - umin) of the indicator first.  The
+        indicator of 3, 4, 6, 7 is left in self.txc[0]; self.txc[3..8] are the work space of 3 and self.txc[3] of 4.  q, s, hq, hs and the state
+        of the driver are unchanged."""
+        from .operators import dns_gate
+        return dns_gate(self, opt_cond, thresholds, self.q, self.s, [self.txc[0]] + self.txc[3:9], relative, 1 if scal is None else scal)
+
+    def conditional_moments(self, gate, np, nm=4, p=None):
+        """The conditional block of tools/statistics/averages.f90 (opt_main = 4): AVG_N_XZ of U V W (P) Scalar1 .. for every level 1 .. np of
+        the int8 tensor gate, from one pass over the gate and the fields.  A dict keyed by the reference's tags: numpy (np, nm, ny) each -- the
+        mean and the central moments 2 .. nm per level and plane -- plus "nsample" (np, ny), the points of every level.  No file is written."""
+        from .operators import avg_n_xz
+        fields = self.q + ([p] if p is not None else []) + self.s
+        tags = ["U", "V", "W"] + (["P"] if p is not None else []) + ["Scalar%d" % (i + 1) for i in range(self.nscal)]
+        avg, _, ns = avg_n_xz(self.nx, self.ny, self.nz, fields, nm, np, gate, raw=True)
+        out = {t: avg[:, i] for i, t in enumerate(tags)}
+        out["nsample"] = ns
+        return out
+
+    def conditional_averages(self, a, fields=None, nbins=32, ibc=1, gate=None, igate=0, umin=0.0, umax=0.0):
+        """CAVG1V_N (statistics/cavg.f90:7) of the field a given each of u, v, w and every scalar (fields: another dict tag -> tensor): a dict
+        tag -> numpy (ny + 1, nbins + 2), the averages of a over the nbins bins of the variable and the centres of the first and the last bin
+        per plane, the volume last.  ibc = 0: the external interval(s) umin, umax; gate with igate != 0: only points with gate == igate.  No file
+        is written."""
+        from .operators import cavg1v_n
+        if fields is None:
+            fields = dict(zip(["u", "v", "w"] + ["s%d" % (i + 1) for i in range(self.nscal)], self.q + self.s))
+        out = cavg1v_n(self.nx, self.ny, self.nz, list(fields.values()), a, nbins, ibc, umin, umax, gate, igate)
+        return dict(zip(fields, out))
+
     def spectra(self, mode="spectra", cross=False, nblock=1, p=None, out2d=False):
         """tools/statistics/spectra.f90, opt_main 1-4, for the fields of the driver, without its files: mode "spectra" (power and co-spectra)
         or "correlations", cross False (every variable with itself: u, v, w, (p,) and the scalars) or True (uv, uw, vw and us, vs, ws per

@@ -21,6 +21,10 @@
 !                                           calculation of INTER_N_XZ (statistics/avg_xz.f90:109-153) for all planes and levels in one pass over
 !                                           the gate.  With USE_MPI the avg/real(npro) and MPI_ALLREDUCE of INTER1V2D (averages.f90:233-236) follow;
 !                                           like every USE_MPI branch of this module, that one is NOT compiled by this project's build or tests.
+!   TLab_AMD_FI_Gate, TLab_AMD_AVG_N_XZ     the conditional block of tools/statistics/averages.f90 (opt_main 3-18): the partition of FI_GATE
+!                                           (mappings/fi_gate.f90, opt_cond 2-7) on the driver's plans and the moments of AVG_N_XZ
+!                                           (statistics/avg_xz.f90:10-70) of one gate level from one pass over the gate and the fields.  Single
+!                                           rank: the decomposed form reduces the sums and nsample of tlab_avg_n_xz, then tlab_raw_to_central.
 ! The arrays are classified by the library (tlab_pointer_on_device): host arrays take a host loop in the reference's order, so the routines serve
 ! either kind; a mix is refused.  The profiles are host memory.  The moment routines give the LOCAL averages: a decomposed host reduces them as it
 ! does the profiles of AVG_IK_V.  What the reference adds on the host afterwards (Ty1, Txyy, Tyyy, Tyzy) stays with the caller.
@@ -35,7 +39,7 @@ module TLab_AMD_Averages
     private
     public :: TLab_AMD_AVG_IK_V, TLab_AMD_AVG1V2D_V, TLab_AMD_Avg_Moments_Flow, TLab_AMD_Avg_Moments_Scal
     public :: TLab_AMD_Avg_Gradients_Flow, TLab_AMD_Avg_UGradP, TLab_AMD_Avg_Gradients_Scal
-    public :: TLab_AMD_FI_Vorticity, TLab_AMD_Inter_N_XZ
+    public :: TLab_AMD_FI_Vorticity, TLab_AMD_Inter_N_XZ, TLab_AMD_FI_Gate, TLab_AMD_AVG_N_XZ, TLab_AMD_AVG_N_XZ_Levels
 
 contains
     subroutine TLab_AMD_AVG_IK_V(nx, ny, nz, a, avg, wrk)
@@ -202,6 +206,53 @@ contains
         call MPI_ALLREDUCE(wrk, inter, ny*np, MPI_REAL8, MPI_SUM, MPI_COMM_WORLD, ims_err)
 #endif
     end subroutine TLab_AMD_Inter_N_XZ
+
+    ! FI_GATE: the reference's argument list with the driver's handle in front (its plans are g(1:3)) and the arrays as addresses: q(3), s(*) and
+    ! txc(7) = c_loc(q(1, .)) .. of device arrays.  The indicator is left in txc(1) as in the reference (opt_cond 2 and 5 read their field in
+    ! place); opt_cond 3 takes txc(2:7) as work arrays, 4 takes txc(2).  gate_threshold(igate_size - 1) is not changed.
+    subroutine TLab_AMD_FI_Gate(dns, opt_cond, opt_cond_relative, opt_cond_scal, nx, ny, nz, igate_size, gate_threshold, q, s, txc, gate)
+        type(c_ptr), intent(in) :: dns, q(3), s(*), txc(7)
+        integer, intent(in) :: opt_cond, opt_cond_relative, opt_cond_scal, nx, ny, nz, igate_size
+        real(c_double), intent(in) :: gate_threshold(igate_size)
+        integer(1), intent(out), target :: gate(nx*ny*nz)
+
+        call TLab_AMD_Check(tlab_dns_gate(dns, opt_cond, opt_cond_relative, opt_cond_scal, igate_size, gate_threshold, q, s, txc, c_loc(gate)), &
+                            'tlab_dns_gate')
+    end subroutine TLab_AMD_FI_Gate
+
+    ! The calculation of AVG_N_XZ: the reference's argument list minus fname, itime, rtime and y -- the file is written by the host, from avg, as
+    ! before (avg_xz.f90:55-66).  vars(nv) are the addresses of the fields, c_loc(vars(iv)%field) of the reference's pointers_dt.  igate = 0: the
+    ! ungated moments; igate > 0: those of the level igate alone.  The library computes the levels 1 .. igate on the way (four a launch) and this
+    ! routine keeps the last: a tool that LOOPS over the levels, as tools/statistics/averages.f90 does, calls TLab_AMD_AVG_N_XZ_Levels once
+    ! instead and pays one pass for all of them, not one per level.  Single rank.
+    subroutine TLab_AMD_AVG_N_XZ(nx, ny, nz, nv, nm, vars, igate, gate, avg)
+        integer, intent(in) :: nx, ny, nz, nv, nm
+        type(c_ptr), intent(in) :: vars(nv)
+        integer(1), intent(in), target :: gate(*), igate
+        real(c_double), intent(out) :: avg(ny, nm, nv)
+        real(c_double), allocatable, target :: levels(:, :, :, :)
+        type(c_ptr) :: pg
+
+        pg = c_null_ptr
+        if (igate > 0) pg = c_loc(gate)
+        allocate (levels(ny, nm, nv, max(int(igate), 1)))
+        call TLab_AMD_Check(tlab_avg_n_xz(nx, ny, nz, nv, nm, vars, max(int(igate), 0), pg, c_loc(levels), c_null_ptr, c_null_ptr), 'tlab_avg_n_xz')
+        avg = levels(:, :, :, max(int(igate), 1))
+    end subroutine TLab_AMD_AVG_N_XZ
+
+    ! AVG_N_XZ for igate = 1 .. np in ONE pass over the gate and the fields: avg(:, :, :, igate) is what the reference's call returns for that
+    ! level; np = 0: the ungated moments in avg(:, :, :, 1) (the gate is not read).  Single rank.
+    subroutine TLab_AMD_AVG_N_XZ_Levels(nx, ny, nz, nv, nm, vars, np, gate, avg)
+        integer, intent(in) :: nx, ny, nz, nv, nm, np
+        type(c_ptr), intent(in) :: vars(nv)
+        integer(1), intent(in), target :: gate(*)
+        real(c_double), intent(out), target :: avg(ny, nm, nv, max(np, 1))
+        type(c_ptr) :: pg
+
+        pg = c_null_ptr
+        if (np > 0) pg = c_loc(gate)
+        call TLab_AMD_Check(tlab_avg_n_xz(nx, ny, nz, nv, nm, vars, np, pg, c_loc(avg), c_null_ptr, c_null_ptr), 'tlab_avg_n_xz')
+    end subroutine TLab_AMD_AVG_N_XZ_Levels
 
 #ifdef USE_MPI
     ! the reduction of AVG_IK_V (averages.f90:320-324) on nc columns of local averages

@@ -687,6 +687,56 @@ module TLab_AMD_C
             type(c_ptr), value :: gate
             real(c_double), intent(out) :: inter(*)
         end function
+        ! conditional statistics (declared in tlab_amd/csrc/tlab_amd_conditional.h; wrappers in tlab_amd_averages.f90, tlab_amd_pdfs.f90):
+        ! the partition of FI_GATE, AVG_N_XZ for the levels 1 .. np of a gate in one
+        ! pass (np = 0: ungated; avg, sums, nsample may be c_null_ptr, not all three), RAW_TO_CENTRAL, CAVG1V_N and CAVG2V; results in host memory
+        integer(c_int) function tlab_gate_levels(a, n, igate_size, thr, gate) bind(C, name='tlab_gate_levels')
+            import :: c_int, c_ptr, c_double, c_long_long
+            type(c_ptr), value :: a, gate
+            integer(c_long_long), value :: n
+            integer(c_int), value :: igate_size
+            real(c_double), intent(in) :: thr(*)
+        end function
+        integer(c_int) function tlab_gate_flux(a, v, n, gate) bind(C, name='tlab_gate_flux')
+            import :: c_int, c_ptr, c_long_long
+            type(c_ptr), value :: a, v, gate
+            integer(c_long_long), value :: n
+        end function
+        integer(c_int) function tlab_dns_gate(dns, opt_cond, opt_cond_relative, opt_cond_scal, igate_size, gate_threshold, q, s, txc, gate) &
+            bind(C, name='tlab_dns_gate')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: dns, gate
+            integer(c_int), value :: opt_cond, opt_cond_relative, opt_cond_scal, igate_size
+            real(c_double), intent(in) :: gate_threshold(*)
+            type(c_ptr), intent(in) :: q(*), s(*), txc(*)
+        end function
+        integer(c_int) function tlab_avg_n_xz(nx, ny, nz, nv, nm, u, np, gate, avg, sums, nsample) bind(C, name='tlab_avg_n_xz')
+            import :: c_int, c_ptr
+            integer(c_int), value :: nx, ny, nz, nv, nm, np
+            type(c_ptr), intent(in) :: u(*)
+            type(c_ptr), value :: gate, avg, sums, nsample
+        end function
+        integer(c_int) function tlab_raw_to_central(nm, moments) bind(C, name='tlab_raw_to_central')
+            import :: c_int, c_double
+            integer(c_int), value :: nm
+            real(c_double), intent(inout) :: moments(*)
+        end function
+        integer(c_int) function tlab_cavg1v_n(nx, ny, nz, nv, nbins, ibc, umin, umax, u, igate, gate, a, avg, sum, pdf) bind(C, name='tlab_cavg1v_n')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz, nv, nbins, igate
+            integer(c_int), intent(in) :: ibc(*)
+            real(c_double), intent(in) :: umin(*), umax(*)
+            type(c_ptr), intent(in) :: u(*)
+            type(c_ptr), value :: gate, a, sum, pdf
+            real(c_double), intent(out) :: avg(*)
+        end function
+        integer(c_int) function tlab_cavg2v(nx, ny, nz, nbins, u, v, a, avg) bind(C, name='tlab_cavg2v')
+            import :: c_int, c_ptr, c_double
+            integer(c_int), value :: nx, ny, nz
+            integer(c_int), intent(in) :: nbins(2)
+            type(c_ptr), value :: u, v, a
+            real(c_double), intent(out) :: avg(*)
+        end function
         ! plane spectra and correlations (tlab_amd_spectra.f90); a_hat .. outr: device or host arrays of one kind, the profiles host memory
         integer(c_int) function tlab_spectrum_reduce(nx, ny, nz, nblock, kr_total, a_hat, b_hat, out2d, outx, outz, outr, variance) &
             bind(C, name='tlab_spectrum_reduce')

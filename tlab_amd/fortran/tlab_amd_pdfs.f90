@@ -6,6 +6,8 @@
 !                      All fields share three passes (min/max; histogram; histogram on the intervals of PDF_ANALIZE) instead of four strided
 !                      passes per field and plane.
 !   TLab_AMD_PDF2V     the calculation of PDF2V (:123-159), single rank.
+!   TLab_AMD_CAVG1V_N, TLab_AMD_CAVG2V   the calculations of CAVG1V_N and CAVG2V (statistics/cavg.f90:7-89, :93-155): the reference's argument
+!                      lists minus fname, time and y; single rank (the decomposed form reduces the sum and pdf outputs of tlab_cavg1v_n).
 ! The arrays are classified by the library (tlab_pointer_on_device): host arrays take the reference's loops on the host, so the routines serve
 ! either kind; a mix is refused.  pdf is host memory.
 ! With USE_MPI the reference's MPI_ALLREDUCEs (utils/pdfs.f90:59-64, :92-95) stand between the passes: min and max of every plane are reduced,
@@ -19,7 +21,7 @@ module TLab_AMD_PDFs
 #endif
     implicit none
     private
-    public :: TLab_AMD_PDF1V_N, TLab_AMD_PDF2V
+    public :: TLab_AMD_PDF1V_N, TLab_AMD_PDF2V, TLab_AMD_CAVG1V_N, TLab_AMD_CAVG2V
 
 contains
     subroutine TLab_AMD_PDF1V_N(nx, ny, nz, nv, nbins, ibc, umin, umax, u, igate, gate, pdf)
@@ -86,6 +88,30 @@ contains
 
         call TLab_AMD_Check(tlab_pdf2v(nx, ny, nz, nbins, c_loc(u), c_loc(v), pdf), 'tlab_pdf2v')
     end subroutine TLab_AMD_PDF2V
+
+    ! avg(1:nbins, j, iv) = <a | u(iv)> in the nbins bins of plane j, then the centres of the first and the last bin; the volume as plane ny + 1
+    subroutine TLab_AMD_CAVG1V_N(nx, ny, nz, nv, nbins, ibc, umin, umax, u, igate, gate, a, avg)
+        integer, intent(in) :: nx, ny, nz, nv, nbins, ibc(nv)
+        real(c_double), intent(in) :: umin(nv), umax(nv)
+        type(c_ptr), intent(in) :: u(nv)
+        integer(1), intent(in), target :: gate(*), igate
+        real(c_double), intent(in), target :: a(nx*ny*nz)
+        real(c_double), intent(out) :: avg(nbins + 2, ny + 1, nv)
+        type(c_ptr) :: pg
+
+        pg = c_null_ptr
+        if (igate /= 0) pg = c_loc(gate)
+        call TLab_AMD_Check(tlab_cavg1v_n(nx, ny, nz, nv, nbins, ibc, umin, umax, u, int(igate, c_int), pg, c_loc(a), avg, c_null_ptr, c_null_ptr), &
+                            'tlab_cavg1v_n')
+    end subroutine TLab_AMD_CAVG1V_N
+
+    subroutine TLab_AMD_CAVG2V(nx, ny, nz, nbins, u, v, a, avg)
+        integer, intent(in) :: nx, ny, nz, nbins(2)
+        real(c_double), intent(in), target :: u(nx*ny*nz), v(nx*ny*nz), a(nx*ny*nz)
+        real(c_double), intent(out) :: avg(nbins(1)*nbins(2) + 2 + 2*nbins(1), ny + 1)
+
+        call TLab_AMD_Check(tlab_cavg2v(nx, ny, nz, nbins, c_loc(u), c_loc(v), c_loc(a), avg), 'tlab_cavg2v')
+    end subroutine TLab_AMD_CAVG2V
 
 #ifdef USE_MPI
     ! the reduction of PDF1V2D (utils/pdfs.f90:92-95) on np histograms: the counts are summed, the two centres behind them stay

@@ -621,6 +621,104 @@ def inter_n_xz(nx, ny, nz, np_, gate):
     return out
 
 
+# ---- conditional statistics: FI_GATE's partition, AVG_N_XZ with a gate, CAVG1V_N / CAVG2V (csrc/tlab_amd_conditional.h) ------------------------
+def _new_gate(a, gate):
+    """(n, gate): an int8 gate of the kind of a (a torch tensor or a numpy array), a new one unless handed in"""
+    if isinstance(a, np.ndarray):
+        return a.size, (np.empty(a.size, dtype=np.int8) if gate is None else gate)
+    import torch
+    return a.numel(), (torch.empty(a.numel(), dtype=torch.int8, device=a.device) if gate is None else gate)
+
+
+def gate_levels(a, thresholds, gate=None):
+    """The loop of FI_GATE (mappings/fi_gate.f90:85-90): the first n with a < thresholds[n - 1], else len(thresholds) + 1, as int8 of the kind
+    of a.  thresholds: ascending, absolute."""
+    keep = []
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    n, gate = _new_gate(a, gate)
+    _stream_if_device([a])
+    check(load().tlab_gate_levels(_field_ptr(a, n, "a", keep), n, thr.size + 1, c_vp(thr.ctypes.data if thr.size else 0), _gate_ptr(gate, n, keep)),
+          "tlab_gate_levels")
+    return gate
+
+
+def gate_flux(a, v, gate=None):
+    """The quadrant partition of FI_GATE (opt_cond = 7, fi_gate.f90:65-71) of the indicator a and the velocity v, as int8 of the kind of a."""
+    keep = []
+    n, gate = _new_gate(a, gate)
+    _stream_if_device([a, v])
+    check(load().tlab_gate_flux(_field_ptr(a, n, "a", keep), _field_ptr(v, n, "v", keep), n, _gate_ptr(gate, n, keep)), "tlab_gate_flux")
+    return gate
+
+
+def dns_gate(dns, opt_cond, thresholds, q, s, txc, relative=False, scal=1, gate=None):
+    """FI_GATE (mappings/fi_gate.f90) for opt_cond 2 .. 7 on the box of the driver dns: an int8 tensor.  q, s, txc: lists of device tensors; the
+    indicator goes into txc[0] (opt_cond 3: txc[1..6] are work arrays, 4: txc[1]); 2 and 5 read their field in place and need no txc."""
+    import torch
+    thr = np.ascontiguousarray(thresholds if thresholds is not None else [], dtype=np.float64).reshape(-1)
+    gate = torch.empty(dns.n, dtype=torch.int8, device="cuda") if gate is None else gate
+    arr = lambda ts: (c_vp * max(len(ts), 1))(*[_ptr(t, dns.n, "array %d" % i).value for i, t in enumerate(ts)])      # noqa: E731
+    _use_torch_stream()
+    check(load().tlab_dns_gate(dns._h, int(opt_cond), 1 if relative else 0, int(scal), thr.size + 1, c_vp(thr.ctypes.data if thr.size else 0),
+                               arr(list(q)), arr(list(s)), arr(list(txc)), _gate_ptr(gate, dns.n, [])), "tlab_dns_gate")
+    return gate
+
+
+def avg_n_xz(nx, ny, nz, fields, nm, np_=0, gate=None, raw=False):
+    """The calculation of AVG_N_XZ (statistics/avg_xz.f90:10) for the levels 1 .. np_ of an int8 gate in one pass (np_ = 0: ungated, one level):
+    numpy (L, nv, nm, ny) with L = max(np_, 1) -- the mean and the central moments 2 .. nm of every field, level and plane.  raw: (avg, sums,
+    nsample) with the undivided sums of a**m in the same shape and the counts (L, ny) as int64."""
+    fields = list(fields)
+    nv, n, keep, L = len(fields), nx * ny * nz, [], max(int(np_), 1)
+    shape = (L, max(nv, 1), max(int(nm), 1), ny)
+    avg, sums, ns = np.zeros(shape), np.zeros(shape), np.zeros((L, ny), dtype=np.int64)
+    _stream_if_device(fields + [gate])
+    check(load().tlab_avg_n_xz(nx, ny, nz, nv, int(nm), _field_ptrs(fields, n, keep), int(np_), _gate_ptr(gate, n, keep), c_vp(avg.ctypes.data),
+                               c_vp(sums.ctypes.data if raw else 0), c_vp(ns.ctypes.data if raw else 0)), "tlab_avg_n_xz")
+    return (avg, sums, ns) if raw else avg
+
+
+def raw_to_central(moments):
+    """RAW_TO_CENTRAL (statistics/avg_xz.f90:72): the raw moments 1 .. nm of one sample to its mean and central moments, a new numpy array."""
+    m = np.array(moments, dtype=np.float64).reshape(-1)
+    check(load().tlab_raw_to_central(m.size, c_vp(m.ctypes.data)), "tlab_raw_to_central")
+    return m
+
+
+def cavg1v_n(nx, ny, nz, fields, a, nbins, ibc=1, umin=None, umax=None, gate=None, igate=0, raw=False):
+    """The calculation of CAVG1V_N (statistics/cavg.f90:7): numpy (nv, ny + 1, nbins + 2) -- per plane the averages of a over the nbins bins of
+    every field, then the centres of the first and the last bin; the volume as the last plane (zero when ny == 1).  ibc: one value or one per
+    field, 0: the external interval umin, umax of the field, anything else: the local one.  raw: (avg, sum, pdf) with the undivided sums of a
+    and the counts in the same shape."""
+    fields = list(fields)
+    nv, n, keep = len(fields), nx * ny * nz, []
+    ibc_ = np.ascontiguousarray(np.broadcast_to(np.asarray(ibc, dtype=np.int32), (max(nv, 1),)))
+    lo = None if umin is None else np.ascontiguousarray(np.broadcast_to(np.asarray(umin, dtype=np.float64), (max(nv, 1),)))
+    hi = None if umax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(umax, dtype=np.float64), (max(nv, 1),)))
+    shape = (max(nv, 1), ny + 1, max(int(nbins), 0) + 2)
+    avg, sum_, pdf = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+    _stream_if_device(fields + [a, gate])
+    check(load().tlab_cavg1v_n(nx, ny, nz, nv, int(nbins), c_vp(ibc_.ctypes.data), c_vp(lo.ctypes.data if lo is not None else 0),
+                               c_vp(hi.ctypes.data if hi is not None else 0), _field_ptrs(fields, n, keep), int(igate), _gate_ptr(gate, n, keep),
+                               _field_ptr(a, n, "a", keep), c_vp(avg.ctypes.data), c_vp(sum_.ctypes.data if raw else 0),
+                               c_vp(pdf.ctypes.data if raw else 0)), "tlab_cavg1v_n")
+    return (avg[:nv], sum_[:nv], pdf[:nv]) if raw else avg[:nv]
+
+
+def cavg2v(nx, ny, nz, nbins, u, v, a):
+    """The calculation of CAVG2V (statistics/cavg.f90:93): numpy (ny + 1, nb1*nb2 + 2 + 2*nb1) in the layout of pdf2v, the first nb1*nb2 entries
+    of a plane the averages of a over the bins of (u, v)."""
+    keep, n = [], nx * ny * nz
+    nb = np.ascontiguousarray(nbins, dtype=np.int32)
+    if nb.shape != (2,):
+        raise TlabError("nbins must hold two values")
+    out = np.zeros((ny + 1, max(int(nb[0]) * int(nb[1]), 0) + 2 + 2 * max(int(nb[0]), 0)))
+    _stream_if_device([u, v, a])
+    check(load().tlab_cavg2v(nx, ny, nz, c_vp(nb.ctypes.data), _field_ptr(u, n, "u", keep), _field_ptr(v, n, "v", keep), _field_ptr(a, n, "a", keep),
+                             c_vp(out.ctypes.data)), "tlab_cavg2v")
+    return out
+
+
 # ---- spectra and correlations in horizontal planes: tools/statistics/spectra.f90 with module SpectraMod (include/tlab_amd.h) ------------------------
 # Arrays of a call are all torch CUDA tensors or all host arrays (numpy, or torch CPU tensors); the results are of the kind of the inputs, shaped
 # C-ordered: a Fortran out(i, j, k) is out[k, j, i].  Accumulators handed in through `out` are added to, as in the reference.
