@@ -2,7 +2,8 @@
 // statistics tlab_avg_gradients_flow, tlab_avg_ugradp, tlab_avg_gradients_scal, tlab_avg_gradients_pass (several programs one after the other:
 // the profiles of one pass are the means of the next).  Device arrays
 // take the kernels of averages.hip, host arrays the loop below in the reference's order; a host array never reaches a kernel, a device array is
-// never read by the host.  The programs (the terms of every output) are those of averages_host.hpp on both sides.
+// never read by the host.  The programs (the terms of every output) are those of averages_host.hpp on both sides.  From stats_common.hpp:
+// on_device and Scratch.
 #include "../../include/tlab_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include "averages_host.hpp"
 #include "driver_common.hpp"
 #include "kernels.hpp"
+#include "stats_common.hpp"
 
 #pragma clang fp contract(off)      // every multiply and add below stays as written
 
@@ -21,19 +23,7 @@ using namespace tlab;
 
 namespace {
 
-// partials, table of means and profile of one launch: one buffer for the process, grown on demand (the calls run on the library's stream one
-// after the other)
-double *g_buf = nullptr;
-size_t g_buf_n = 0;
-double *scratch(size_t n) {
-    if (g_buf_n < n) {
-        if (g_buf) hk(hipFree(g_buf), "hipFree");
-        g_buf = nullptr; g_buf_n = 0;
-        hk(hipMalloc((void **)&g_buf, n * sizeof(double)), "hipMalloc(plane statistics)");
-        g_buf_n = n;
-    }
-    return g_buf;
-}
+Scratch g_scratch("hipMalloc(plane statistics)");      // partials, table of means and profile of one launch
 
 // AVG_IK_V's loop nest for one plane (utils/averages.f90:311-320): k outer, i inner, one running sum per output, then the division
 template <class P>
@@ -54,19 +44,6 @@ void host_planes(int nx, int ny, int nz, const double *const *f, const double *c
     }
 }
 
-// 1: every array is device memory, 0: every array is host memory (or no tlab_init: no array is the library's); a mix is refused
-bool on_device(const char *who, int n, const double *const *f) {
-    int ndev = 0;
-    if (tlab_device_ready())
-        for (int i = 0; i < n; ++i) {
-            const int on = tlab_pointer_on_device(f[i]);
-            if (on < 0) throw Fail(on, std::string(who) + ": " + tlab_last_error());
-            ndev += on ? 1 : 0;
-        }
-    if (ndev != 0 && ndev != n) throw Fail(TLAB_EINVAL, std::string(who) + ": host and device arrays in one call");
-    return ndev != 0;
-}
-
 // one program on its fields: f[nfld], means[nmean] (host profiles), out: nout columns ldout apart
 void run(bool device, int prog, int param, int nx, int ny, int nz, const double *const *f, const double *const *means, double *out, int ldout) {
     const AvgInfo info = avg_info(prog, param);
@@ -76,7 +53,7 @@ void run(bool device, int prog, int param, int nx, int ny, int nz, const double 
     }
     hipStream_t st = tlab_current_stream();
     const size_t npart = (size_t)plane_moments_chunks(nz) * ny * info.nout, nmean = (size_t)info.nmean * ny, nprof = (size_t)info.nout * ny;
-    double *partial = scratch(npart + nmean + nprof), *dmeans = partial + npart, *prof = dmeans + nmean;
+    double *partial = g_scratch.doubles(npart + nmean + nprof), *dmeans = partial + npart, *prof = dmeans + nmean;
     std::vector<double> hm(nmean), hp(nprof);      // (both live until the stream is synchronised below)
     if (nmean) {
         for (int i = 0; i < info.nmean; ++i) std::copy(means[i], means[i] + ny, hm.begin() + (size_t)i * ny);
@@ -88,7 +65,7 @@ void run(bool device, int prog, int param, int nx, int ny, int nz, const double 
     for (int o = 0; o < info.nout; ++o) std::copy(hp.begin() + (size_t)o * ny, hp.begin() + (size_t)(o + 1) * ny, out + (size_t)o * ldout);
 }
 
-void check_box(const char *who, int nx, int ny, int nz, int ld) {
+void check_profiles(const char *who, int nx, int ny, int nz, int ld) {
     if (nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": nx, ny, nz must be at least 1");
     if (ld < ny) throw Fail(TLAB_EINVAL, std::string(who) + ": the leading dimension of the profiles is smaller than ny");
 }
@@ -101,10 +78,10 @@ int tlab_avg_ik_v(int nx, int ny, int nz, int nf, const double *const *a, double
     (void)tlab_internal_deferred_flush();
     return catch_fail([&] {
         if (nf < 1 || !a || !avg) throw Fail(TLAB_EINVAL, "tlab_avg_ik_v: nf < 1 or a null pointer");
-        check_box("tlab_avg_ik_v", nx, ny, nz, ldavg);
+        check_profiles("tlab_avg_ik_v", nx, ny, nz, ldavg);
         for (int f = 0; f < nf; ++f)
             if (!a[f]) throw Fail(TLAB_EINVAL, "tlab_avg_ik_v: a null array");
-        const bool dev = on_device("tlab_avg_ik_v", nf, a);
+        const bool dev = on_device("tlab_avg_ik_v", a, nf);
         for (int f0 = 0; f0 < nf; f0 += AVG_FIELDS_PER_LAUNCH) {
             const int n = std::min(AVG_FIELDS_PER_LAUNCH, nf - f0);
             run(dev, AVG_PROG_MEANS, n, nx, ny, nz, a + f0, nullptr, avg + (size_t)f0 * ldavg, ldavg);
@@ -117,8 +94,8 @@ int tlab_avg1v2d_v(int nx, int ny, int nz, int imom, const double *a, double *av
     return catch_fail([&] {
         if (!a || !avg) throw Fail(TLAB_EINVAL, "tlab_avg1v2d_v: a null pointer");
         if (imom < 1 || imom > 4) throw Fail(TLAB_EINVAL, "tlab_avg1v2d_v: imom must be 1 to 4");
-        check_box("tlab_avg1v2d_v", nx, ny, nz, ny);
-        run(on_device("tlab_avg1v2d_v", 1, &a), AVG_PROG_POWER, imom, nx, ny, nz, &a, nullptr, avg, ny);
+        check_profiles("tlab_avg1v2d_v", nx, ny, nz, ny);
+        run(on_device("tlab_avg1v2d_v", &a, 1), AVG_PROG_POWER, imom, nx, ny, nz, &a, nullptr, avg, ny);
     }, TLAB_EINVAL);
 }
 
@@ -126,9 +103,9 @@ int tlab_avg_cov2v(int nx, int ny, int nz, const double *a, const double *b, dou
     (void)tlab_internal_deferred_flush();
     return catch_fail([&] {
         if (!a || !b || !cov) throw Fail(TLAB_EINVAL, "tlab_avg_cov2v: a null pointer");
-        check_box("tlab_avg_cov2v", nx, ny, nz, ldcov);
+        check_profiles("tlab_avg_cov2v", nx, ny, nz, ldcov);
         const double *f[2] = {a, b};
-        run(on_device("tlab_avg_cov2v", 2, f), AVG_PROG_COV2, 0, nx, ny, nz, f, nullptr, cov, ldcov);
+        run(on_device("tlab_avg_cov2v", f, 2), AVG_PROG_COV2, 0, nx, ny, nz, f, nullptr, cov, ldcov);
     }, TLAB_EINVAL);
 }
 
@@ -138,9 +115,9 @@ int tlab_avg_moments_flow(int nx, int ny, int nz, const double *u, const double 
     return catch_fail([&] {
         if (!u || !v || !w || !fU || !fV || !fW || !out || (p == nullptr) != (rP == nullptr))
             throw Fail(TLAB_EINVAL, "tlab_avg_moments_flow: a null pointer (p and rP may be NULL, together)");
-        check_box("tlab_avg_moments_flow", nx, ny, nz, ldout);
+        check_profiles("tlab_avg_moments_flow", nx, ny, nz, ldout);
         const double *f[4] = {u, v, w, p}, *m[4] = {fU, fV, fW, rP};
-        run(on_device("tlab_avg_moments_flow", p ? 4 : 3, f), AVG_PROG_FLOW, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
+        run(on_device("tlab_avg_moments_flow", f, p ? 4 : 3), AVG_PROG_FLOW, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
     }, TLAB_EINVAL);
 }
 
@@ -150,9 +127,9 @@ int tlab_avg_moments_scal(int nx, int ny, int nz, const double *s, const double 
     return catch_fail([&] {
         if (!s || !u || !v || !w || !fS || !fU || !fV || !fW || !out || (p == nullptr) != (rP == nullptr))
             throw Fail(TLAB_EINVAL, "tlab_avg_moments_scal: a null pointer (p and rP may be NULL, together)");
-        check_box("tlab_avg_moments_scal", nx, ny, nz, ldout);
+        check_profiles("tlab_avg_moments_scal", nx, ny, nz, ldout);
         const double *f[5] = {s, u, v, w, p}, *m[5] = {fS, fU, fV, fW, rP};
-        run(on_device("tlab_avg_moments_scal", p ? 5 : 4, f), AVG_PROG_SCAL, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
+        run(on_device("tlab_avg_moments_scal", f, p ? 5 : 4), AVG_PROG_SCAL, p ? 1 : 0, nx, ny, nz, f, m, out, ldout);
     }, TLAB_EINVAL);
 }
 
@@ -167,12 +144,12 @@ int tlab_avg_gradients_pass(int pass, int with_p, int nx, int ny, int nz, const 
         if (pass < 1 || pass > 5) throw Fail(TLAB_EINVAL, std::string(who) + ": pass must be 1 to 5");
         const AvgInfo info = avg_info(progs[pass - 1], with_p ? 1 : 0);
         if (!fields || !out || (info.nmean > 0 && !means)) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
-        check_box(who, nx, ny, nz, ldout);
+        check_profiles(who, nx, ny, nz, ldout);
         for (int i = 0; i < info.nfld; ++i)
             if (!fields[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
         for (int i = 0; i < info.nmean; ++i)
             if (!means[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null profile");
-        run(on_device(who, info.nfld, fields), progs[pass - 1], with_p ? 1 : 0, nx, ny, nz, fields, means, out, ldout);
+        run(on_device(who, fields, info.nfld), progs[pass - 1], with_p ? 1 : 0, nx, ny, nz, fields, means, out, ldout);
     }, TLAB_EINVAL);
 }
 
@@ -184,13 +161,13 @@ int tlab_avg_gradients_flow(int nx, int ny, int nz, const double *const *grad, c
         const char *who = "tlab_avg_gradients_flow";
         if (!grad || !u || !v || !w || !fU || !fV || !fW || !rU_y || !rV_y || !rW_y || !out || (p == nullptr) != (rP == nullptr))
             throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer (p and rP may be NULL, together)");
-        check_box(who, nx, ny, nz, ldout);
+        check_profiles(who, nx, ny, nz, ldout);
         const double *f[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, u, v, w, p};
         for (int i = 0; i < 9; ++i) {
             if (!grad[i]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null gradient array");
             f[i] = grad[i];
         }
-        const bool dev = on_device(who, p ? 13 : 12, f);
+        const bool dev = on_device(who, f, p ? 13 : 12);
         auto col = [&](int c) { return out + (size_t)c * ldout; };
         run(dev, AVG_PROG_GRAD_FLOW1, 0, nx, ny, nz, f, nullptr, col(0), ldout);
         const double *m2[6] = {rU_y, rV_y, rW_y, col(0), col(1), col(2)};
@@ -205,9 +182,9 @@ int tlab_avg_ugradp(int nx, int ny, int nz, const double *u, const double *v, co
     (void)tlab_internal_deferred_flush();
     return catch_fail([&] {
         if (!u || !v || !w || !dpdx || !dpdy || !dpdz || !out) throw Fail(TLAB_EINVAL, "tlab_avg_ugradp: a null pointer");
-        check_box("tlab_avg_ugradp", nx, ny, nz, ny);
+        check_profiles("tlab_avg_ugradp", nx, ny, nz, ny);
         const double *f[6] = {u, v, w, dpdx, dpdy, dpdz};
-        run(on_device("tlab_avg_ugradp", 6, f), AVG_PROG_UGRADP, 0, nx, ny, nz, f, nullptr, out, ny);
+        run(on_device("tlab_avg_ugradp", f, 6), AVG_PROG_UGRADP, 0, nx, ny, nz, f, nullptr, out, ny);
     }, TLAB_EINVAL);
 }
 
@@ -220,9 +197,9 @@ int tlab_avg_gradients_scal(int nx, int ny, int nz, const double *const *grads, 
         if (!grads || !grads[0] || !grads[1] || !grads[2] || !s || !u || !v || !w || !fS || !fU || !fV || !fW || !rS_y || !out ||
             (p == nullptr) != (rP == nullptr) || (p && !fS_y))
             throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer (p and rP may be NULL, together; fS_y is needed with p)");
-        check_box(who, nx, ny, nz, ldout);
+        check_profiles(who, nx, ny, nz, ldout);
         const double *all[8] = {grads[0], grads[1], grads[2], s, u, v, w, p}, *f[8] = {grads[1], s, u, v, w, p, grads[0], grads[2]};
-        const bool dev = on_device(who, p ? 8 : 7, all);
+        const bool dev = on_device(who, all, p ? 8 : 7);
         auto col = [&](int c) { return out + (size_t)c * ldout; };
         run(dev, AVG_PROG_GRAD_SCAL1, 0, nx, ny, nz, grads, &rS_y, col(0), ldout);
         const double *m2[7] = {col(0), fS, fU, fV, fW, rP, fS_y};

@@ -3,7 +3,8 @@
 // conditional averages tlab_cavg1v_n, tlab_cavg2v (statistics/cavg.f90 over the a, avg arguments of module PDFS).  Device arrays take the kernels of
 // conditional.hip, host arrays the reference's loops below in the reference's order; a host array never reaches a kernel, a device array is never
 // read by the host.  The level and the bin of a point, the integer power and RAW_TO_CENTRAL are those of conditional_host.hpp / pdfs_host.hpp on
-// both sides; every interval bound and every division is computed HERE, on the host, for both kinds of array.
+// both sides; every interval bound and every division is computed HERE, on the host, for both kinds of array.  From stats_common.hpp: on_device,
+// Scratch with up16, Box, check_box, for_plane, group, minmax_pass (the intervals of tlab_cavg1v_n are those of tlab_pdf1v_n) and joint_intervals.
 #include "tlab_amd_conditional.h"
 
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "dns_state.hpp"
 #include "driver_common.hpp"
 #include "kernels.hpp"
+#include "stats_common.hpp"
 
 #pragma clang fp contract(off)      // every operation below stays as written
 
@@ -23,103 +25,8 @@ using namespace tlab;
 
 namespace {
 
-// device scratch of one pass: one buffer for the process, grown on demand (the calls run on the library's stream one after the other)
-char *g_buf = nullptr;
-size_t g_buf_n = 0;
-char *scratch(size_t bytes) {
-    if (g_buf_n < bytes) {
-        if (g_buf) hk(hipFree(g_buf), "hipFree");
-        g_buf = nullptr; g_buf_n = 0;
-        hk(hipMalloc((void **)&g_buf, bytes), "hipMalloc(conditional statistics)");
-        g_buf_n = bytes;
-    }
-    return g_buf;
-}
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+Scratch g_scratch("hipMalloc(conditional statistics)");      // the device scratch of one pass
 constexpr size_t PARTIAL_BYTES = (size_t)256 << 20;      // what the partial tables of one launch may take: fewer fields per launch above it
-
-// 1: every array is device memory, 0: every array is host memory (or no tlab_init: no array is the library's); a mix is refused
-bool on_device(const char *who, const std::vector<const void *> &p) {
-    size_t ndev = 0;
-    if (tlab_device_ready())
-        for (const void *x : p) {
-            const int on = tlab_pointer_on_device(x);
-            if (on < 0) throw Fail(on, std::string(who) + ": " + tlab_last_error());
-            ndev += on ? 1 : 0;
-        }
-    if (ndev != 0 && ndev != p.size()) throw Fail(TLAB_EINVAL, std::string(who) + ": host and device arrays in one call");
-    return ndev != 0;
-}
-
-struct Box {
-    bool dev;
-    int nx, ny, nz, igate;
-    const signed char *gate;
-};
-
-Box check_box(const char *who, int nx, int ny, int nz, int nv, const double *const *u, int igate, const signed char *gate, const double *a) {
-    if (nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": nx, ny, nz must be at least 1");
-    if (nv < 1 || !u) throw Fail(TLAB_EINVAL, std::string(who) + ": nv < 1 or a null pointer");
-    if (igate < -128 || igate > 127) throw Fail(TLAB_EINVAL, std::string(who) + ": igate is not a value of an int8 gate");
-    if (igate != 0 && !gate) throw Fail(TLAB_EINVAL, std::string(who) + ": igate != 0 needs a gate");
-    std::vector<const void *> all;
-    for (int v = 0; v < nv; ++v) {
-        if (!u[v]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
-        all.push_back(u[v]);
-    }
-    if (a) all.push_back(a);
-    if (igate != 0) all.push_back(gate);
-    return Box{on_device(who, all), nx, ny, nz, igate, igate != 0 ? gate : nullptr};
-}
-
-// plane j of u(nx, ny, nz) is u(:, j, :); the volume (j = ny) is the same loop over u(nx*ny, 1, nz), that is every point
-template <class F>
-void for_plane(const Box &B, int j, F &&fn) {
-    if (j < B.ny) {
-        for (int k = 0; k < B.nz; ++k)
-            for (int i = 0; i < B.nx; ++i) fn(((size_t)k * B.ny + j) * B.nx + i);
-    } else {
-        const size_t n = (size_t)B.nx * B.ny * B.nz;
-        for (size_t i = 0; i < n; ++i) fn(i);
-    }
-}
-
-PdfFields group(const Box &B, const double *const *u, size_t v0, size_t nv, size_t per) {
-    PdfFields F{};
-    F.nv = (int)std::min(per, nv - v0);
-    for (int i = 0; i < F.nv; ++i) F.f[i] = u[v0 + i];
-    F.gate = B.gate; F.igate = B.igate; F.nx = B.nx; F.ny = B.ny; F.nz = B.nz;
-    return F;
-}
-
-// utils/pdfs.f90:50-57 (from the first point) and :144-153 (gated: from big_wp) of the planes and of the volume: mm [nv][ny + 1][2]
-void minmax_pass(const Box &B, const double *const *u, size_t nv, std::vector<double> &mm) {
-    const size_t np = (size_t)B.ny + 1;
-    mm.assign(nv * np * 2, 0.0);
-    if (nv == 0) return;
-    if (!B.dev) {
-        for (size_t v = 0; v < nv; ++v)
-            for (int j = 0; j <= B.ny; ++j) {
-                double mn, mx;
-                if (B.gate) { mn = PDF_BIG; mx = -PDF_BIG; }
-                else mn = mx = u[v][j < B.ny ? (size_t)j * B.nx : 0];
-                for_plane(B, j, [&](size_t i) {
-                    if (B.gate && B.gate[i] != B.igate) return;
-                    mn = u[v][i] < mn ? u[v][i] : mn;
-                    mx = u[v][i] > mx ? u[v][i] : mx;
-                });
-                mm[(v * np + j) * 2] = mn; mm[(v * np + j) * 2 + 1] = mx;
-            }
-        return;
-    }
-    hipStream_t st = tlab_current_stream();
-    const size_t npart = (size_t)PDF_FIELDS_PER_LAUNCH * pdf_chunks(B.nz) * B.ny * 2;
-    double *dmm = (double *)scratch((nv * np * 2 + npart) * sizeof(double)), *partial = dmm + nv * np * 2;
-    for (size_t v0 = 0; v0 < nv; v0 += PDF_FIELDS_PER_LAUNCH)
-        hk(launch_pdf_minmax(group(B, u, v0, nv, PDF_FIELDS_PER_LAUNCH), partial, dmm + v0 * np * 2, st), "k_pdf_minmax");
-    hk(hipMemcpyAsync(mm.data(), dmm, mm.size() * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(min/max)");
-    hk(hipStreamSynchronize(st), "sync");
-}
 
 // The sums of a and the counts per bin of nv fields on the intervals iv [nv][ny + 1][2] = (umin, ustep) (nb2 == 0), or of the pair (u[0], v2) with
 // the v-intervals viv [ny + 1][nb1][2] of every u-bin (nb2 > 0): sum, cnt [nv][ny + 1][nbins], the volume as plane ny (zero when ny == 1)
@@ -154,7 +61,7 @@ void cavg_pass(const Box &B, const double *const *u, size_t nv, const double *v2
     const size_t o_viv = up16(iv.size() * 8), o_sum = o_viv + up16(viv.size() * 8), o_cnt = o_sum + up16(sum.size() * 8),
                  o_vs = o_cnt + up16(cnt.size() * 8), o_vc = o_vs + up16(per * B.ny * nb * 8), o_ps = o_vc + up16(per * B.ny * nb * 8),
                  o_pc = o_ps + up16(per * part1 * 8);
-    char *buf = scratch(o_pc + up16(per * part1 * 4));
+    char *buf = g_scratch.bytes(o_pc + up16(per * part1 * 4));
     double *div = (double *)buf, *dviv = (double *)(buf + o_viv), *dsum = (double *)(buf + o_sum), *dcnt = (double *)(buf + o_cnt);
     hk(hipMemcpyAsync(div, iv.data(), iv.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(intervals)");
     if (nb2 > 0) hk(hipMemcpyAsync(dviv, viv.data(), viv.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(v intervals)");
@@ -300,10 +207,10 @@ int tlab_avg_n_xz(int nx, int ny, int nz, int nv, int nm, const double *const *u
             const size_t npart = (size_t)PDF_FIELDS_PER_LAUNCH * pdf_chunks(nz) * ny * COND_LEVELS_PER_LAUNCH * gated_moments_width(nm),
                          ncnt = (size_t)pdf_chunks(nz) * ny * COND_LEVELS_PER_LAUNCH;
             const size_t o_n = up16(nout * 8), o_part = o_n + up16(N.size() * 8), o_cnt = o_part + up16(npart * 8);
-            char *buf = scratch(o_cnt + up16(ncnt * 4));
+            char *buf = g_scratch.bytes(o_cnt + up16(ncnt * 4));
             for (size_t v0 = 0; v0 < (size_t)nv; v0 += PDF_FIELDS_PER_LAUNCH)
                 for (size_t g0 = 1; g0 <= L; g0 += COND_LEVELS_PER_LAUNCH)
-                    hk(launch_gated_moments(group(B, u, v0, nv, PDF_FIELDS_PER_LAUNCH), nm, (int)g0, (int)L, (int)v0, nv, (double *)(buf + o_part),
+                    hk(launch_gated_moments(group(B, u, v0, nv), nm, (int)g0, (int)L, (int)v0, nv, (double *)(buf + o_part),
                                             (unsigned *)(buf + o_cnt), (double *)buf, (long long *)(buf + o_n), st), "k_gated_moments");
             hk(hipMemcpyAsync(S.data(), buf, nout * 8, hipMemcpyDeviceToHost, st), "hipMemcpy(sums)");
             hk(hipMemcpyAsync(N.data(), buf + o_n, N.size() * 8, hipMemcpyDeviceToHost, st), "hipMemcpy(counts)");
@@ -345,7 +252,7 @@ int tlab_cavg1v_n(int nx, int ny, int nz, int nv, int nbins, const int *ibc, con
             if (!ext[v]) local.push_back(u[v]);
         }
         std::vector<double> mm, iv((size_t)nv * np * 2, 1.0), S, C;
-        minmax_pass(B, local.data(), local.size(), mm);
+        minmax_pass(B, g_scratch, local.data(), local.size(), mm);
         for (double *out : {avg, sum, pdf})
             if (out) std::fill(out, out + (size_t)nv * ld, 0.0);
         for (size_t v = 0, l = 0; v < (size_t)nv; ++v) {
@@ -382,41 +289,8 @@ int tlab_cavg2v(int nx, int ny, int nz, const int *nbins, const double *u, const
         const Box B = check_box(who, nx, ny, nz, 2, f, 0, nullptr, a);
         const size_t np = (size_t)ny + 1, npl = ny > 1 ? np : 1, ld = (size_t)nb + 2 + 2 * nb1;
         std::fill(avg, avg + np * ld, 0.0);
-        // min / max of u (utils/pdfs.f90:241-252), then of v in every u-bin (:259-268)
-        std::vector<double> mm, iv(np * 2, 1.0), rng(np * nb1 * 2), viv(np * nb1 * 2, 1.0), S, C;
-        minmax_pass(B, f, 1, mm);
-        for (size_t j = 0; j < npl; ++j) {
-            iv[2 * j] = mm[2 * j];
-            iv[2 * j + 1] = pdf_step(mm[2 * j], mm[2 * j + 1], nb1, avg + j * ld + nb, avg + j * ld + nb + 1);
-        }
-        if (!B.dev) {
-            for (size_t j = 0; j < npl; ++j) {
-                for (int up = 0; up < nb1; ++up) { rng[(j * nb1 + up) * 2] = PDF_BIG; rng[(j * nb1 + up) * 2 + 1] = -PDF_BIG; }
-                for_plane(B, (int)j, [&](size_t i) {
-                    const int up = pdf_bin(u[i], iv[2 * j], iv[2 * j + 1], nb1, false);
-                    if (up < 0 || up >= nb1) return;
-                    double *r = &rng[(j * nb1 + up) * 2];
-                    r[0] = v[i] < r[0] ? v[i] : r[0];
-                    r[1] = v[i] > r[1] ? v[i] : r[1];
-                });
-            }
-        } else {
-            hipStream_t st = tlab_current_stream();
-            const size_t nchunks = pdf_chunks(nz);
-            const size_t o_rng = up16(iv.size() * 8), o_vp = o_rng + up16(rng.size() * 8), o_part = o_vp + up16((size_t)ny * nb1 * 2 * 8);
-            char *buf = scratch(o_part + up16(nchunks * ny * 2 * nb1 * 2 * 8));
-            hk(hipMemcpyAsync(buf, iv.data(), iv.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(intervals)");
-            hk(launch_pdf2v_range(group(B, f, 0, 2, 2), nb1, (double *)buf, (double *)(buf + o_part), (double *)(buf + o_vp), (double *)(buf + o_rng), st),
-               "k_pdf2v_range");
-            hk(hipMemcpyAsync(rng.data(), buf + o_rng, rng.size() * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(ranges)");
-            hk(hipStreamSynchronize(st), "sync");
-        }
-        for (size_t j = 0; j < npl; ++j)
-            for (int up = 0; up < nb1; ++up) {
-                const size_t e = (j * nb1 + up) * 2;
-                viv[e] = rng[e];
-                viv[e + 1] = pdf_step(rng[e], rng[e + 1], nb2, avg + j * ld + nb + 2 + up, avg + j * ld + nb + 2 + nb1 + up);
-            }
+        std::vector<double> iv, viv, S, C;
+        joint_intervals(B, g_scratch, f, nb1, nb2, avg, ld, iv, viv);
         cavg_pass(B, f, 1, v, a, nb1, nb2, std::vector<char>(1, 0), iv, viv, S, C);
         for (size_t j = 0; j < npl; ++j) divide(S.data() + j * nb, C.data() + j * nb, nb, avg + j * ld);
     }, TLAB_EINVAL);

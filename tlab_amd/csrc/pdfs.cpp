@@ -2,7 +2,8 @@
 // tlab_pdf_minmax_planes / tlab_pdf_histogram_planes, tlab_pdf_analize (PDF_ANALIZE, host arithmetic), tlab_pdf2v (PDF2V, :123-159) and
 // tlab_gate_threshold, and the intermittency factors of a gate, tlab_inter_n_xz (INTER_N_XZ, statistics/avg_xz.f90:109-153).  Device arrays take the kernels of pdfs.hip, host arrays the reference's loops below; a host array never reaches a kernel, a
 // device array is never read by the host.  The bin of a point, the step of an interval and PDF_ANALIZE are those of pdfs_host.hpp on both sides;
-// every interval bound is computed HERE, on the host, for both kinds of array.
+// every interval bound is computed HERE, on the host, for both kinds of array.  From stats_common.hpp: on_device, Scratch with up16, Box, check_box,
+// for_plane, group, minmax_pass and joint_intervals (the first two passes of tlab_pdf2v on device arrays).
 #include "../../include/tlab_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include "driver_common.hpp"
 #include "kernels.hpp"
 #include "pdfs_host.hpp"
+#include "stats_common.hpp"
 
 #pragma clang fp contract(off)      // every operation below stays as written
 
@@ -21,87 +23,13 @@ using namespace tlab;
 
 namespace {
 
-// device scratch of one pass: one buffer for the process, grown on demand (the calls run on the library's stream one after the other)
-char *g_buf = nullptr;
-size_t g_buf_n = 0;
-char *scratch(size_t bytes) {
-    if (g_buf_n < bytes) {
-        if (g_buf) hk(hipFree(g_buf), "hipFree");
-        g_buf = nullptr; g_buf_n = 0;
-        hk(hipMalloc((void **)&g_buf, bytes), "hipMalloc(plane PDFs)");
-        g_buf_n = bytes;
-    }
-    return g_buf;
-}
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-struct Box {
-    const char *who;
-    bool dev;
-    int nx, ny, nz, igate;
-    const signed char *gate;
-    size_t plane() const { return (size_t)nx * nz; }
-};
-
-// 1: every array is device memory, 0: every array is host memory (or no tlab_init: no array is the library's); a mix is refused
-bool on_device(const char *who, const std::vector<const void *> &p) {
-    size_t ndev = 0;
-    if (tlab_device_ready())
-        for (const void *x : p) {
-            const int on = tlab_pointer_on_device(x);
-            if (on < 0) throw Fail(on, std::string(who) + ": " + tlab_last_error());
-            ndev += on ? 1 : 0;
-        }
-    if (ndev != 0 && ndev != p.size()) throw Fail(TLAB_EINVAL, std::string(who) + ": host and device arrays in one call");
-    return ndev != 0;
-}
-
-Box check_box(const char *who, int nx, int ny, int nz, int nv, const double *const *u, int igate, const signed char *gate) {
-    if (nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": nx, ny, nz must be at least 1");
-    if (nv < 1 || !u) throw Fail(TLAB_EINVAL, std::string(who) + ": nv < 1 or a null pointer");
-    if (igate < -128 || igate > 127) throw Fail(TLAB_EINVAL, std::string(who) + ": igate is not a value of an int8 gate");
-    if (igate != 0 && !gate) throw Fail(TLAB_EINVAL, std::string(who) + ": igate != 0 needs a gate");
-    std::vector<const void *> all;
-    for (int v = 0; v < nv; ++v) {
-        if (!u[v]) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
-        all.push_back(u[v]);
-    }
-    if (igate != 0) all.push_back(gate);
-    return Box{who, on_device(who, all), nx, ny, nz, igate, igate != 0 ? gate : nullptr};
-}
+Scratch g_scratch("hipMalloc(plane PDFs)");      // the device scratch of one pass
 
 void check_bins(const char *who, long long nbins) {
     if (nbins < 1 || nbins > PDF_MAX_BINS) throw Fail(TLAB_EINVAL, std::string(who) + ": the number of bins must be 1 to " + std::to_string(PDF_MAX_BINS));
 }
 
 // ---- the reference's loops (host arrays) ---------------------------------------------------------------------------------------------------------
-// plane j of u(nx, ny, nz) is u(:, j, :); the volume is the same loop over u(nx*ny, 1, nz), that is every point (statistics/pdf.f90:74)
-template <class F>
-void for_plane(const Box &B, int j, F &&fn) {
-    if (j < B.ny) {
-        for (int k = 0; k < B.nz; ++k)
-            for (int i = 0; i < B.nx; ++i) fn(((size_t)k * B.ny + j) * B.nx + i);
-    } else {
-        const size_t n = (size_t)B.nx * B.ny * B.nz;
-        for (size_t i = 0; i < n; ++i) fn(i);
-    }
-}
-
-// utils/pdfs.f90:50-57 (from the first point) and :144-153 (gated: from big_wp); mm: [ny + 1][2]
-void host_minmax(const Box &B, const double *u, double *mm) {
-    for (int j = 0; j <= B.ny; ++j) {
-        double mn, mx;
-        if (B.gate) { mn = PDF_BIG; mx = -PDF_BIG; }
-        else mn = mx = u[j < B.ny ? (size_t)j * B.nx : 0];
-        for_plane(B, j, [&](size_t i) {
-            if (B.gate && B.gate[i] != B.igate) return;
-            mn = u[i] < mn ? u[i] : mn;
-            mx = u[i] > mx ? u[i] : mx;
-        });
-        mm[2 * j] = mn; mm[2 * j + 1] = mx;
-    }
-}
-
 // :76-90, :172-189; iv: [ny + 1][2] = (umin, ustep); cnt: [ny + 1][nbins]
 void host_hist(const Box &B, const double *u, int nbins, bool ext, const double *iv, double *cnt) {
     for (int j = 0; j < B.ny + (B.ny > 1 ? 1 : 0); ++j) {
@@ -116,35 +44,9 @@ void host_hist(const Box &B, const double *u, int nbins, bool ext, const double 
 }
 
 // ---- the passes ----------------------------------------------------------------------------------------------------------------------------------
-PdfFields group(const Box &B, const double *const *u, const std::vector<int> &idx, size_t v0) {
-    PdfFields F{};
-    F.nv = (int)std::min<size_t>(PDF_FIELDS_PER_LAUNCH, idx.size() - v0);
-    for (int i = 0; i < F.nv; ++i) F.f[i] = u[idx[v0 + i]];
-    F.gate = B.gate; F.igate = B.igate; F.nx = B.nx; F.ny = B.ny; F.nz = B.nz;
-    return F;
-}
-
-// min and max of the fields idx: mm [idx.size()][ny + 1][2], the volume as plane ny.  One synchronisation.
-void minmax_pass(const Box &B, const double *const *u, const std::vector<int> &idx, std::vector<double> &mm) {
-    const size_t ns = idx.size(), np = (size_t)B.ny + 1;
-    mm.assign(ns * np * 2, 0.0);
-    if (ns == 0) return;
-    if (!B.dev) {
-        for (size_t s = 0; s < ns; ++s) host_minmax(B, u[idx[s]], mm.data() + s * np * 2);
-        return;
-    }
-    hipStream_t st = tlab_current_stream();
-    const size_t npart = (size_t)PDF_FIELDS_PER_LAUNCH * pdf_chunks(B.nz) * B.ny * 2;
-    double *dmm = (double *)scratch((ns * np * 2 + npart) * sizeof(double)), *partial = dmm + ns * np * 2;
-    for (size_t v0 = 0; v0 < ns; v0 += PDF_FIELDS_PER_LAUNCH)
-        hk(launch_pdf_minmax(group(B, u, idx, v0), partial, dmm + v0 * np * 2, st), "k_pdf_minmax");
-    hk(hipMemcpyAsync(mm.data(), dmm, mm.size() * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(min/max)");
-    hk(hipStreamSynchronize(st), "sync");
-}
-
-// The histograms of the fields idx on the intervals lo, hi [idx.size()][ny + 1] (the volume's as plane ny), ext[s]: external (a point outside is
-// dropped).  Writes the whole of pdf(nbins + 2, ny + 1) of field idx[s] at pdf + idx[s] * ldf: counts and the two centres; with ny == 1 the last
-// plane is zero.  One synchronisation.
+// The histograms of the fields u[idx.size()] on the intervals lo, hi [idx.size()][ny + 1] (the volume's as plane ny), ext[s]: external (a point
+// outside is dropped).  Writes the whole of pdf(nbins + 2, ny + 1) of field u[s] at pdf + idx[s] * ldf: counts and the two centres; with ny == 1
+// the last plane is zero.  One synchronisation.
 void hist_pass(const Box &B, const double *const *u, const std::vector<int> &idx, int nbins, const std::vector<char> &ext, const std::vector<double> &lo,
                const std::vector<double> &hi, double *pdf, size_t ldf) {
     const size_t ns = idx.size(), np = (size_t)B.ny + 1, npl = B.ny > 1 ? np : 1;
@@ -164,16 +66,16 @@ void hist_pass(const Box &B, const double *const *u, const std::vector<int> &idx
             if (!(iv[(s * np + j) * 2] == iv[(s * np + B.ny) * 2] && iv[(s * np + j) * 2 + 1] == iv[(s * np + B.ny) * 2 + 1])) vol[s] = 1;
     }
     if (!B.dev) {
-        for (size_t s = 0; s < ns; ++s) host_hist(B, u[idx[s]], nbins, ext[s] != 0, iv.data() + s * np * 2, cnt.data() + s * np * nbins);
+        for (size_t s = 0; s < ns; ++s) host_hist(B, u[s], nbins, ext[s] != 0, iv.data() + s * np * 2, cnt.data() + s * np * nbins);
     } else {
         hipStream_t st = tlab_current_stream();
         const size_t ncnt = (size_t)PDF_FIELDS_PER_LAUNCH * pdf_chunks(B.nz) * B.ny * 2 * nbins, nvp = (size_t)PDF_FIELDS_PER_LAUNCH * B.ny * nbins;
         const size_t o_pdf = up16(iv.size() * 8), o_vp = o_pdf + up16(cnt.size() * 8), o_cnt = o_vp + up16(nvp * 8);
-        char *buf = scratch(o_cnt + up16(ncnt * 4));
+        char *buf = g_scratch.bytes(o_cnt + up16(ncnt * 4));
         double *div = (double *)buf, *dpdf = (double *)(buf + o_pdf);
         hk(hipMemcpyAsync(div, iv.data(), iv.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(intervals)");
         for (size_t v0 = 0; v0 < ns; v0 += PDF_FIELDS_PER_LAUNCH) {
-            const PdfFields F = group(B, u, idx, v0);
+            const PdfFields F = group(B, u, v0, ns);
             unsigned em = 0u, vm = 0u;
             for (int i = 0; i < F.nv; ++i) {
                 em |= ext[v0 + i] ? 1u << i : 0u;
@@ -224,10 +126,8 @@ int tlab_pdf_minmax_planes(int nx, int ny, int nz, int nv, const double *const *
         const char *who = "tlab_pdf_minmax_planes";
         const Box B = check_box(who, nx, ny, nz, nv, u, igate, gate);
         if (!umin || !umax) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
-        std::vector<int> idx(nv);
-        for (int v = 0; v < nv; ++v) idx[v] = v;
         std::vector<double> mm;
-        minmax_pass(B, u, idx, mm);
+        minmax_pass(B, g_scratch, u, nv, mm);
         for (size_t i = 0; i < (size_t)nv * (ny + 1); ++i) { umin[i] = mm[2 * i]; umax[i] = mm[2 * i + 1]; }
     }, TLAB_EINVAL);
 }
@@ -257,17 +157,18 @@ int tlab_pdf1v_n(int nx, int ny, int nz, int nv, int nbins, const int *ibc, cons
         const Box B = check_box(who, nx, ny, nz, nv, u, igate, gate);
         if (!ibc || !pdf) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
         const size_t np = (size_t)ny + 1, npl = ny > 1 ? np : 1, ldf = np * (nbins + 2);
-        std::vector<int> all(nv), local, analysed;
+        std::vector<int> all(nv), analysed;
+        std::vector<const double *> local, ua;      // the fields with a local interval, the fields of analysed
         for (int v = 0; v < nv; ++v) {
             if (ibc[v] < 0 || ibc[v] > 5) throw Fail(TLAB_EINVAL, std::string(who) + ": ibc must be 0 to 5");
             if (ibc[v] == 0 && (!umin || !umax)) throw Fail(TLAB_EINVAL, std::string(who) + ": ibc = 0 needs umin and umax");
             all[v] = v;
-            if (ibc[v] >= 1) local.push_back(v);
-            if (ibc[v] >= 2) analysed.push_back(v);
+            if (ibc[v] >= 1) local.push_back(u[v]);
+            if (ibc[v] >= 2) { analysed.push_back(v); ua.push_back(u[v]); }
         }
         // pass 1: the local intervals
         std::vector<double> mm;
-        minmax_pass(B, u, local, mm);
+        minmax_pass(B, g_scratch, local.data(), local.size(), mm);
         // pass 2: every field on its first interval
         std::vector<double> lo((size_t)nv * np), hi((size_t)nv * np);
         std::vector<char> ext(nv);
@@ -289,7 +190,7 @@ int tlab_pdf1v_n(int nx, int ny, int nz, int nv, int nbins, const int *ibc, cons
                 int nplim = 0;
                 pdf_analize(ibc[analysed[s]] - 2, nbins, pdf + analysed[s] * ldf + j * (nbins + 2), &lo[s * np + j], &hi[s * np + j], 1.0e-4, &nplim);
             }
-        hist_pass(B, u, analysed, nbins, std::vector<char>(na, 1), lo, hi, pdf, ldf);
+        hist_pass(B, ua.data(), analysed, nbins, std::vector<char>(na, 1), lo, hi, pdf, ldf);
     }, TLAB_EINVAL);
 }
 
@@ -317,35 +218,18 @@ int tlab_pdf2v(int nx, int ny, int nz, const int *nbins, const double *u, const 
             for (size_t j = 0; j < npl; ++j) host_pdf2v(B, (int)j, u, v, nb1, nb2, pdf + j * ld);
             return;
         }
-        // pass 1: min / max of u
-        std::vector<double> mm;
-        minmax_pass(B, f, std::vector<int>{0}, mm);
-        std::vector<double> iv(np * 2, 1.0), rng(np * nb1 * 2), viv(np * nb1 * 2, 1.0), cnt(np * nb, 0.0);
-        for (size_t j = 0; j < npl; ++j) {
-            iv[2 * j] = mm[2 * j];
-            iv[2 * j + 1] = pdf_step(mm[2 * j], mm[2 * j + 1], nb1, pdf + j * ld + nb, pdf + j * ld + nb + 1);
-        }
-        // pass 2: min / max of v in every u-bin
+        // passes 1 and 2: min / max of u, then of v in every u-bin
+        std::vector<double> iv, viv, cnt(np * nb, 0.0);
+        joint_intervals(B, g_scratch, f, nb1, nb2, pdf, ld, iv, viv);
+        // pass 3: the joint histogram (the u-intervals go to the device once more: the scratch of pass 2 is not kept)
         hipStream_t st = tlab_current_stream();
-        const PdfFields F = group(B, f, std::vector<int>{0, 1}, 0);
-        const size_t nchunks = pdf_chunks(nz);
-        const size_t o_viv = up16(iv.size() * 8), o_rng = o_viv + up16(viv.size() * 8), o_pdf = o_rng + up16(rng.size() * 8),
-                     o_vp = o_pdf + up16(cnt.size() * 8), o_part = o_vp + up16(std::max((size_t)ny * nb * 8, (size_t)ny * nb1 * 2 * 8));
-        char *buf = scratch(o_part + up16(std::max(nchunks * ny * 2 * nb1 * 2 * 8, nchunks * ny * 2 * nb * 4)));
-        double *div = (double *)buf, *dviv = (double *)(buf + o_viv), *drng = (double *)(buf + o_rng), *dpdf = (double *)(buf + o_pdf);
+        const size_t o_viv = up16(iv.size() * 8), o_pdf = o_viv + up16(viv.size() * 8), o_vp = o_pdf + up16(cnt.size() * 8),
+                     o_part = o_vp + up16((size_t)ny * nb * 8);
+        char *buf = g_scratch.bytes(o_part + up16((size_t)pdf_chunks(nz) * ny * 2 * nb * 4));
+        double *div = (double *)buf, *dviv = (double *)(buf + o_viv), *dpdf = (double *)(buf + o_pdf);
         hk(hipMemcpyAsync(div, iv.data(), iv.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(intervals)");
-        hk(launch_pdf2v_range(F, nb1, div, (double *)(buf + o_part), (double *)(buf + o_vp), drng, st), "k_pdf2v_range");
-        hk(hipMemcpyAsync(rng.data(), drng, rng.size() * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(ranges)");
-        hk(hipStreamSynchronize(st), "sync");
-        for (size_t j = 0; j < npl; ++j)
-            for (int up = 0; up < nb1; ++up) {
-                const size_t e = (j * nb1 + up) * 2;
-                viv[e] = rng[e];
-                viv[e + 1] = pdf_step(rng[e], rng[e + 1], nb2, pdf + j * ld + nb + 2 + up, pdf + j * ld + nb + 2 + nb1 + up);
-            }
-        // pass 3: the joint histogram
         hk(hipMemcpyAsync(dviv, viv.data(), viv.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(v intervals)");
-        hk(launch_pdf2v_hist(F, nb1, nb2, div, dviv, (unsigned *)(buf + o_part), (unsigned long long *)(buf + o_vp), dpdf, st), "k_pdf2v_hist");
+        hk(launch_pdf2v_hist(group(B, f, 0, 2), nb1, nb2, div, dviv, (unsigned *)(buf + o_part), (unsigned long long *)(buf + o_vp), dpdf, st), "k_pdf2v_hist");
         hk(hipMemcpyAsync(cnt.data(), dpdf, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(counts)");
         hk(hipStreamSynchronize(st), "sync");
         for (size_t j = 0; j < npl; ++j) std::copy(cnt.begin() + j * nb, cnt.begin() + (j + 1) * nb, pdf + j * ld);
@@ -371,7 +255,7 @@ int tlab_inter_n_xz(int nx, int ny, int nz, int np, const signed char *gate, dou
         if (nx < 1 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": nx, ny, nz must be at least 1");
         if (np < 1 || np > GATE_MAX_LEVELS) throw Fail(TLAB_EINVAL, std::string(who) + ": np must be 1 to " + std::to_string(GATE_MAX_LEVELS));
         if (!gate || !inter) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
-        const Box B{who, on_device(who, {gate}), nx, ny, nz, 0, gate};
+        const Box B{on_device(who, {gate}), nx, ny, nz, 0, gate};
         const double denom = (double)((long long)nx * nz);
         if (!B.dev) {
             for (int j = 0; j < ny; ++j)
@@ -384,7 +268,7 @@ int tlab_inter_n_xz(int nx, int ny, int nz, int np, const signed char *gate, dou
         }
         hipStream_t st = tlab_current_stream();
         const size_t nout = (size_t)ny * np, o_cnt = up16(nout * sizeof(double));
-        char *buf = scratch(o_cnt + up16((size_t)pdf_chunks(nz) * nout * sizeof(unsigned)));
+        char *buf = g_scratch.bytes(o_cnt + up16((size_t)pdf_chunks(nz) * nout * sizeof(unsigned)));
         hk(launch_gate_count(gate, nx, ny, nz, np, (unsigned *)(buf + o_cnt), (double *)buf, st), "k_gate_count");
         hk(hipMemcpyAsync(inter, buf, nout * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(intermittency)");
         hk(hipStreamSynchronize(st), "sync");

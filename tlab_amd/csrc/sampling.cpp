@@ -2,7 +2,7 @@
 // tlab_tower_*, the saved planes tlab_planes_gather with tlab_fi_gradient and tlab_log10_small, and tlab_dns_arm_pressure_sampling, whose samples
 // rhs.cpp takes between the pressure solve and the pressure gradient.  Device arrays take the kernels of sampling.hip, host arrays the loops below,
 // which are the reference's statements; a host array never reaches a kernel, a device array is never read by the host.  Nothing here synchronises
-// the stream: the accumulators are the caller's and stay where they are.
+// the stream: the accumulators are the caller's and stay where they are.  From stats_common.hpp: on_device and Scratch.
 #include "../../include/tlab_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 
 #include "averages_host.hpp"
 #include "dns_state.hpp"
+#include "stats_common.hpp"
 
 #pragma clang fp contract(off)      // every multiply, add and division below stays as written
 
@@ -36,31 +37,7 @@ struct tlab_tower {
 
 namespace {
 
-// partials and profile of the tower means: one buffer for the process, grown on demand (the calls run on the library's stream one after the other)
-double *g_buf = nullptr;
-size_t g_buf_n = 0;
-double *scratch(size_t n) {
-    if (g_buf_n < n) {
-        if (g_buf) hk(hipFree(g_buf), "hipFree");
-        g_buf = nullptr; g_buf_n = 0;
-        hk(hipMalloc((void **)&g_buf, n * sizeof(double)), "hipMalloc(tower means)");
-        g_buf_n = n;
-    }
-    return g_buf;
-}
-
-// 1: every array is device memory, 0: every array is host memory (or no tlab_init); a mix is refused
-bool on_device(const std::string &who, int n, const void *const *a) {
-    int ndev = 0;
-    if (tlab_device_ready())
-        for (int i = 0; i < n; ++i) {
-            const int on = tlab_pointer_on_device(a[i]);
-            if (on < 0) throw Fail(on, who + ": " + tlab_last_error());
-            ndev += on ? 1 : 0;
-        }
-    if (ndev != 0 && ndev != n) throw Fail(TLAB_EINVAL, who + ": host and device arrays in one call");
-    return ndev != 0;
-}
+Scratch g_scratch("hipMalloc(tower means)");      // partials and profile of the tower means
 
 // ---- phase averages ----
 // the planes of output o of an accumulator avg(nxy, avg_planes + 1, nout): this sample's (plane_id, 1-based) and the running mean (the last one)
@@ -153,7 +130,7 @@ void tower_accumulate(tlab_tower *t, bool dev, int index, const double *const *f
         const int *ipos = t->dpos, *jpos = ipos + ti, *kpos = jpos + tj;
         hk(launch_tower_gather(nf, f, dst, ipos, jpos, kpos, ti, tj, tk, t->nx, t->ny, t_slot, it_slot, rtime, itime, st), "k_tower_gather");
         const size_t npart = (size_t)plane_moments_chunks(t->nz) * t->ny * nf;
-        double *partial = scratch(npart + (size_t)nf * t->ny), *prof = partial + npart;
+        double *partial = g_scratch.doubles(npart + (size_t)nf * t->ny), *prof = partial + npart;
         hk(launch_plane_moments(AVG_PROG_MEANS, nf, t->nx, t->ny, t->nz, f, nullptr, partial, prof, st, (double)(float)((long long)t->nx * t->nz)),
            "k_plane_partial");
         hk(launch_tower_means(prof, t->ny, jpos, tj, nf, mean, st), "k_tower_means");
@@ -206,7 +183,7 @@ int tlab_avg_phase_space(int nx, int ny, int nz, int nz_total, int nf, const dou
         for (const void *p : all)
             if (!p) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
         all.push_back(avg);
-        phase_space(on_device(who, nf + 1, all.data()), nx, ny, nz, nz_total, nf, fields, avg_planes, plane_id, avg);
+        phase_space(on_device(who, all), nx, ny, nz, nz_total, nf, fields, avg_planes, plane_id, avg);
     }, TLAB_EINVAL);
 }
 
@@ -217,7 +194,6 @@ int tlab_avg_phase_flow(int nx, int ny, int nz, int nz_total, const double *u, c
         const char *who = "tlab_avg_phase_flow";
         if (!u || !v || !w || !avg_flow || !avg_stress) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
         check_phase(who, nx, ny, nz, nz_total, avg_planes, plane_id);
-        const void *all[5] = {u, v, w, avg_flow, avg_stress};
         const double *f[3] = {u, v, w};
         const long long nxy = (long long)nx * ny;
         double *out[9], *last[9];
@@ -225,7 +201,7 @@ int tlab_avg_phase_flow(int nx, int ny, int nz, int nz_total, const double *u, c
             out[o] = phase_plane(o < 3 ? avg_flow : avg_stress, nxy, avg_planes, o < 3 ? o : o - 3, plane_id - 1);
             last[o] = phase_plane(o < 3 ? avg_flow : avg_stress, nxy, avg_planes, o < 3 ? o : o - 3, avg_planes);
         }
-        if (on_device(who, 5, all)) {
+        if (on_device(who, {u, v, w, avg_flow, avg_stress})) {
             hk(launch_phase_space(3, true, f, out, last, nxy, nz, nz_total, avg_planes, tlab_current_stream()), "k_phase_space");
             return;
         }
@@ -295,7 +271,7 @@ int tlab_tower_accumulate(tlab_tower_t t, int index, const double *const *fields
         const void *all[4] = {tower_buf, nullptr, nullptr, nullptr};
         for (int i = 0; i < nf; ++i)
             if (!(all[1 + i] = fields[i])) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
-        tower_accumulate(t, on_device(who, nf + 1, all), index, fields, itime, rtime, tower_buf);
+        tower_accumulate(t, on_device(who, all, (size_t)nf + 1), index, fields, itime, rtime, tower_buf);
     }, TLAB_EINVAL);
 }
 
@@ -313,7 +289,7 @@ int tlab_planes_gather(int nx, int ny, int nz, int nvars, const double *const *f
         for (const void *p : all)
             if (!p) throw Fail(TLAB_EINVAL, std::string(who) + ": a null field");
         all.push_back(out);
-        if (on_device(who, nvars + 1, all.data())) {
+        if (on_device(who, all)) {
             hk(launch_planes_gather(nx, ny, nz, nvars, fields, dir, n, nodes, out, single != 0, tlab_current_stream()), "k_planes_gather");
             return;
         }
@@ -359,8 +335,7 @@ int tlab_log10_small(long long n, double *a) {
     (void)tlab_internal_deferred_flush();
     return catch_fail([&] {
         if (n < 1 || !a) throw Fail(TLAB_EINVAL, "tlab_log10_small: n < 1 or a null pointer");
-        const void *all[1] = {a};
-        if (on_device("tlab_log10_small", 1, all)) hk(launch_log10_small(a, n, tlab_current_stream()), "k_log10_small");
+        if (on_device("tlab_log10_small", {a})) hk(launch_log10_small(a, n, tlab_current_stream()), "k_log10_small");
         else
             for (long long i = 0; i < n; ++i) a[i] = std::log10(a[i] + 1.0e-20);
     }, TLAB_EINVAL);

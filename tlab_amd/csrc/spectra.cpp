@@ -3,7 +3,8 @@
 // tlab_cross_product, tlab_fluctuation, and the composed operators tlab_spectra_pair (the loop body of tools/statistics/spectra.f90:620-671 for one pair,
 // on a Poisson plan's transforms) and tlab_dns_spectra (its pair list, :482-522, on the driver's arrays).  Device arrays take the kernels of
 // spectra.hip, host arrays the reference's loops below; a host array never reaches a kernel, a device array is never read by the host.  The
-// index maps are those of spectra_host.hpp on both sides.  Profiles (ny values) are host memory, as in averages.cpp.
+// index maps are those of spectra_host.hpp on both sides.  Profiles (ny values) are host memory, as in averages.cpp.  From stats_common.hpp:
+// on_device and Scratch.
 #include "../../include/tlab_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "driver_common.hpp"
 #include "kernels.hpp"
 #include "spectra_host.hpp"
+#include "stats_common.hpp"
 
 #pragma clang fp contract(off)      // every operation below stays as written
 
@@ -24,22 +26,10 @@ using namespace tlab;
 
 namespace {
 
-// device scratch of one call: one buffer for the process, grown on demand (the calls run on the library's stream one after the other)
-double *g_buf = nullptr;
-size_t g_buf_n = 0;
-double *scratch(size_t n) {
-    if (g_buf_n < n) {
-        if (g_buf) hk(hipFree(g_buf), "hipFree");
-        g_buf = nullptr; g_buf_n = 0;
-        hk(hipMalloc((void **)&g_buf, n * sizeof(double)), "hipMalloc(spectra)");
-        g_buf_n = n;
-    }
-    return g_buf;
-}
+Scratch g_scratch("hipMalloc(spectra)");      // the device scratch of one call
 
 // the ring lists of one (kind, line length, nz, number of rings) on the device; the last few are kept
-// (like the scratch above and the buffers of pdfs.cpp and averages.cpp they are the process's: nothing is freed at exit, when the runtime may
-// be gone; a list that leaves the cache is freed then)
+// (like the scratch they are the process's: nothing is freed at exit, when the runtime may be gone; a list that leaves the cache is freed then)
 struct DevRings {
     int kind, n1, nz, nr;
     int *off = nullptr, *mode = nullptr;
@@ -64,20 +54,7 @@ const DevRings &rings(int kind, int n1, int nz, int nr) {
     return *g_rings.back();
 }
 
-// 1: every array is device memory, 0: every array is host memory (or no tlab_init: no array is the library's); a mix is refused
-bool on_device(const char *who, const std::vector<const void *> &p) {
-    size_t ndev = 0;
-    if (tlab_device_ready())
-        for (const void *x : p) {
-            const int on = tlab_pointer_on_device(x);
-            if (on < 0) throw Fail(on, std::string(who) + ": " + tlab_last_error());
-            ndev += on ? 1 : 0;
-        }
-    if (ndev != 0 && ndev != p.size()) throw Fail(TLAB_EINVAL, std::string(who) + ": host and device arrays in one call");
-    return ndev != 0;
-}
-
-void check_box(const std::string &who, int nx, int ny, int nz, int nblock) {
+void check_spectra_box(const std::string &who, int nx, int ny, int nz, int nblock) {
     if (nx < 2 || ny < 1 || nz < 1) throw Fail(TLAB_EINVAL, who + ": nx must be at least 2, ny and nz at least 1");
     if (nx % 2) throw Fail(TLAB_EINVAL, who + ": nx must be even");
     if (nblock < 1 || nblock > ny) throw Fail(TLAB_EINVAL, who + ": nblock must be 1 to ny");
@@ -187,7 +164,7 @@ void spectrum_reduce(const char *who, bool dev, int nx, int ny, int nz, int nblo
     const int nkx = nx / 2, nyo = ny / nblock;
     const size_t nS = (size_t)nkx * nyo * nz, nrow = (size_t)ny * nz;
     const DevRings &R = rings(0, nkx, nz, kr_total);
-    double *S = scratch(nS + nrow + ny), *rowv = S + nS, *dvar = rowv + nrow;
+    double *S = g_scratch.doubles(nS + nrow + ny), *rowv = S + nS, *dvar = rowv + nrow;
     hk(launch_spectrum_reduce(nx, ny, nz, nblock, kr_total, a, b, S, rowv, R.off, R.mode, out2d, outx, outz, outr, dvar, st), who);
     hk(hipMemcpyAsync(variance, dvar, (size_t)ny * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(variance)");
     hk(hipStreamSynchronize(st), "sync");
@@ -203,7 +180,7 @@ void correlation_reduce(const char *who, bool dev, int nx, int ny, int nz, int n
     }
     hipStream_t st = tlab_current_stream();
     const DevRings *R = outr ? &rings(1, nx, nz, nr_total) : nullptr;
-    double *dnorm = scratch(2 * (size_t)ny), *dvar = dnorm + ny;
+    double *dnorm = g_scratch.doubles(2 * (size_t)ny), *dvar = dnorm + ny;
     hk(hipMemcpyAsync(dnorm, normj.data(), (size_t)ny * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(norms)");
     hk(launch_correlation_reduce(nx, ny, nz, nblock, nr_total, in, dnorm, R ? R->off : nullptr, R ? R->mode : nullptr, out2d, outx, outz, outr, dvar, st),
        who);
@@ -250,7 +227,7 @@ int tlab_spectrum_reduce(int nx, int ny, int nz, int nblock, int kr_total, const
     (void)tlab_internal_deferred_flush();
     return catch_fail([&] {
         const char *who = "tlab_spectrum_reduce";
-        check_box(who, nx, ny, nz, nblock);
+        check_spectra_box(who, nx, ny, nz, nblock);
         if (kr_total < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": kr_total must be at least 1");
         if (!a_hat || !outx || !outz || !outr || !variance) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
         std::vector<const void *> all{a_hat, outx, outz, outr};
@@ -265,7 +242,7 @@ int tlab_correlation_reduce(int nx, int ny, int nz, int nblock, int nr_total, co
     (void)tlab_internal_deferred_flush();
     return catch_fail([&] {
         const char *who = "tlab_correlation_reduce";
-        check_box(who, nx, ny, nz, nblock);
+        check_spectra_box(who, nx, ny, nz, nblock);
         if (!in || !var1 || !var2 || !outx || !outz || !variance2) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
         if (icalc_radial == 1 && (!outr || nr_total < 1)) throw Fail(TLAB_EINVAL, std::string(who) + ": icalc_radial = 1 needs outr and nr_total >= 1");
         double *r = icalc_radial == 1 ? outr : nullptr;
@@ -321,7 +298,7 @@ int tlab_fluctuation(int nx, int ny, int nz, const double *in, const double *mea
             return;
         }
         hipStream_t st = tlab_current_stream();
-        double *dm = scratch(ny);
+        double *dm = g_scratch.doubles(ny);
         hk(hipMemcpyAsync(dm, mean, (size_t)ny * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(means)");
         hk(launch_fluctuation(nx, ny, nz, in, dm, out, st), "k_fluctuation");
         hk(hipStreamSynchronize(st), "sync");      // (the caller's means may go, and the scratch may be taken again)
@@ -336,7 +313,7 @@ int tlab_spectra_pair(tlab_poisson_plan_t plan, int mode, int nblock, int kr_tot
         int n[3];
         if (!plan) throw Fail(TLAB_EINVAL, std::string(who) + ": null plan");
         if (!tlab_internal_poisson_box(plan, n)) throw Fail(TLAB_EUNSUPPORTED, std::string(who) + ": needs a single-device plan (no slab or pencil plan)");
-        check_box(who, n[0], n[1], n[2], nblock);
+        check_spectra_box(who, n[0], n[1], n[2], nblock);
         if (kr_total < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": kr_total must be at least 1");
         if (!cov || !variance) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
         std::vector<const void *> all{a, tmp1, tmp2, tmp3, outx, outz, outr};
@@ -359,7 +336,7 @@ int tlab_dns_spectra(tlab_dns_t h, int mode, int cross, int nblock, int kr_total
         tlab_internal_dns_grid(h, &G);
         const int nx = G.nx, ny = G.ny, nz = G.nz, nscal = tlab_internal_dns_nscal(h);
         tlab_poisson_plan_t plan = tlab_internal_dns_poisson(h);
-        check_box(who, nx, ny, nz, nblock);
+        check_spectra_box(who, nx, ny, nz, nblock);
         if (kr_total < 1) throw Fail(TLAB_EINVAL, std::string(who) + ": kr_total must be at least 1");
         if (!q || !txc || (nscal > 0 && !s) || !outx || !outz || !outr || !cov || !variance) throw Fail(TLAB_EINVAL, std::string(who) + ": a null pointer");
         std::vector<const double *> var{q[0], q[1], q[2]};      // vars(:), spectra.f90:454-474
