@@ -17,4 +17,6 @@ from .operators import (  # noqa: F401
     pdf1v_n, pdf_minmax_planes, pdf_histogram_planes, pdf_analize, pdf2v, gate_threshold,
     fi_vorticity, vorticity_from_gradients, inter_n_xz,
     avg_phase_space, avg_phase_flow, avg_phase_plane_id, Tower, planes_gather, fi_gradient, log10_small,
+    MAPS, FI_DIFFUSION_KINDS, gradient_maps, velocity_gradients, scalar_gradient, fi_maps, fi_diffusion, fi_strain, fi_strain_tensor, fi_curl,
+    fi_invariant_q, fi_invariant_r, fi_vorticity_production, fi_strain_production, fi_gradient_production, fi_strain_a,
 )

@@ -742,6 +742,64 @@ class Dns:
         out = cavg1v_n(self.nx, self.ny, self.nz, list(fields.values()), a, nbins, ibc, umin, umax, gate, igate)
         return dict(zip(fields, out))
 
+    # ---- the variables of tools/statistics/averages.f90, opt_main 5 .. 8 (:661-762): what the reference puts into vars(:) before AVG_N_XZ ----
+    def _new_fields(self, k):
+        import torch
+        return [torch.empty(self.n, dtype=torch.float64, device=self.q[0].device) for _ in range(k)]
+
+    def invariants(self):
+        """opt_main = 8 (averages.f90:756-762): {"InvariantP", "InvariantQ", "InvariantR"} as device tensors, from nine derivatives into
+        self.txc[0..8] and one pass over them (the reference: 23 OPR_Partial calls).  q, s, hq, hs and the state of the driver are unchanged."""
+        from .operators import fi_maps
+        r = fi_maps(self, self.q, None, ["P", "Q", "R"], self.txc[:9], out=self._new_fields(3))
+        return {"InvariantP": r["P"], "InvariantQ": r["Q"], "InvariantR": r["R"]}
+
+    def enstrophy_equation(self):
+        """opt_main = 5 (averages.f90:661-685), incompressible, without the Baroclinic entry (FI_VORTICITY_BAROCLINIC is not built): a dict keyed
+        by the reference's tags with device tensors -- EnstrophyW_iW_i, LnEnstrophyW_iW_i, ProductionW_iW_jS_ij, DiffusionNuW_iLapW_i (visc x
+        FI_VORTICITY_DIFFUSION), DilatationMsW_iW_iDivU (P x enstrophy) and RateAN_iN_jS_ij (production / enstrophy).  The nine gradients are
+        taken ONCE for the enstrophy, its production and the dilatation (self.txc[0..8]); the diffusion term then makes the reference's calls
+        with self.txc[0..5] as its work space.  q, s, hq, hs and the state of the driver are unchanged."""
+        import torch
+        from .operators import fi_diffusion, fi_maps
+        r = fi_maps(self, self.q, None, ["VORTICITY", "VORTICITY_PRODUCTION", "P"], self.txc[:9], out=self._new_fields(3))
+        ens, prod = r["VORTICITY"], r["VORTICITY_PRODUCTION"]
+        dif = fi_diffusion(self, "VORTICITY_DIFFUSION", self.q, None, self._new_fields(1)[0], self.txc[:6])
+        return {"EnstrophyW_iW_i": ens, "LnEnstrophyW_iW_i": torch.log(ens), "ProductionW_iW_jS_ij": prod, "DiffusionNuW_iLapW_i": self.visc * dif,
+                "DilatationMsW_iW_iDivU": r["P"] * ens, "RateAN_iN_jS_ij": prod / ens}
+
+    def strain_equation(self, p=None):
+        """opt_main = 6 (averages.f90:696-721): Strain2S_ijS_i (2 x FI_STRAIN), LnStrain2S_ijS_i, ProductionMs2S_ijS_jkS_ki (2 x
+        FI_STRAIN_PRODUCTION), DiffusionNuS_ijLapS_ij ((2 visc) x FI_STRAIN_DIFFUSION) and Pressure2S_ijP_ij (2 x FI_STRAIN_PRESSURE) as device
+        tensors.  p: the pressure; None takes FI_PRESSURE_BOUSSINESQ first, into an array of the method's.  Strain and production share one
+        pass over the nine gradients (self.txc[0..8]); the two composed terms use self.txc[0..5].  q, s, hq, hs are unchanged."""
+        import torch
+        from .operators import fi_diffusion, fi_maps
+        if p is None:
+            p = self.FI_PRESSURE_BOUSSINESQ(torch.empty(self.isize_txc_field, dtype=torch.float64, device=self.q[0].device))
+        prs = fi_diffusion(self, "STRAIN_PRESSURE", self.q, p, self._new_fields(1)[0], self.txc[:6])
+        r = fi_maps(self, self.q, None, ["STRAIN", "STRAIN_PRODUCTION"], self.txc[:9], out=self._new_fields(2))
+        dif = fi_diffusion(self, "STRAIN_DIFFUSION", self.q, None, self._new_fields(1)[0], self.txc[:6])
+        strain2 = 2.0 * r["STRAIN"]
+        return {"Strain2S_ijS_i": strain2, "LnStrain2S_ijS_i": torch.log(strain2), "ProductionMs2S_ijS_jkS_ki": 2.0 * r["STRAIN_PRODUCTION"],
+                "DiffusionNuS_ijLapS_ij": (2.0 * self.visc) * dif, "Pressure2S_ijP_ij": 2.0 * prs}
+
+    def scalar_gradient_equation(self, iscal=0):
+        """opt_main = 7 (averages.f90:731-746) for scalar iscal (0-based): GradientG_iG_i, LnGradientG_iG_i, ProductionMsG_iG_jS_ij,
+        DiffusionNuG_iLapG_i (FI_GRADIENT_DIFFUSION x visc / schmidt[iscal]) and StrainAMsN_iN_jS_ij (production / gradient, as the reference
+        computes that entry) as device tensors.  Gradient and production share one pass over twelve derivatives (self.txc[0..8] and three
+        arrays of the method's).  q, s, hq, hs are unchanged."""
+        import torch
+        from .operators import fi_diffusion, fi_maps
+        s = self.s[iscal]
+        r = fi_maps(self, self.q, s, ["GRADIENT", "GRADIENT_PRODUCTION"], self.txc[:9], self._new_fields(3), self._new_fields(2))
+        grad, prod = r["GRADIENT"], r["GRADIENT_PRODUCTION"]
+        dif = fi_diffusion(self, "GRADIENT_DIFFUSION", None, s, self._new_fields(1)[0], self.txc[:6])
+        # (a device operand: torch divides by a host number through its reciprocal, which is not the reference's division)
+        schmidt = torch.tensor(float(self.schmidt[iscal]), dtype=torch.float64, device=dif.device)
+        return {"GradientG_iG_i": grad, "LnGradientG_iG_i": torch.log(grad), "ProductionMsG_iG_jS_ij": prod,
+                "DiffusionNuG_iLapG_i": torch.div(dif * self.visc, schmidt), "StrainAMsN_iN_jS_ij": prod / grad}
+
     def spectra(self, mode="spectra", cross=False, nblock=1, p=None, out2d=False):
         """tools/statistics/spectra.f90, opt_main 1-4, for the fields of the driver, without its files: mode "spectra" (power and co-spectra)
         or "correlations", cross False (every variable with itself: u, v, w, (p,) and the scalars) or True (uv, uw, vw and us, vs, ws per

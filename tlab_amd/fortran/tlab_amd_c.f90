@@ -737,6 +737,40 @@ module TLab_AMD_C
             type(c_ptr), value :: u, v, a
             real(c_double), intent(out) :: avg(*)
         end function
+        ! field mappings (declared in tlab_amd/csrc/tlab_amd_mappings.h; wrappers in tlab_amd_mappings.f90): the maps TLAB_MAP_* of the nine velocity
+        ! gradients (and the scalar gradient) in one pass, the derivatives that feed it on the driver's plans, and the diffusion / pressure terms
+        ! TLAB_FI_* composed from OPR_Partial.  du9, ds3, maps, out, q, txc9, work6: host arrays (of addresses); ds3 may be c_null_ptr
+        integer(c_int) function tlab_gradient_maps(n, du9, ds3, maps, nmaps, out) bind(C, name='tlab_gradient_maps')
+            import :: c_int, c_ptr, c_long_long
+            integer(c_long_long), value :: n
+            type(c_ptr), intent(in) :: du9(9), out(*)
+            type(c_ptr), value :: ds3
+            integer(c_int), intent(in) :: maps(*)
+            integer(c_int), value :: nmaps
+        end function
+        integer(c_int) function tlab_dns_velocity_gradients(dns, q, txc9) bind(C, name='tlab_dns_velocity_gradients')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns
+            type(c_ptr), intent(in) :: q(3), txc9(9)
+        end function
+        integer(c_int) function tlab_dns_scalar_gradient(dns, s, ds3) bind(C, name='tlab_dns_scalar_gradient')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, s
+            type(c_ptr), intent(in) :: ds3(3)
+        end function
+        integer(c_int) function tlab_dns_fi_maps(dns, q, s, maps, nmaps, txc9, ds3, out) bind(C, name='tlab_dns_fi_maps')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, s, ds3
+            type(c_ptr), intent(in) :: q(3), txc9(9), out(*)
+            integer(c_int), intent(in) :: maps(*)
+            integer(c_int), value :: nmaps
+        end function
+        integer(c_int) function tlab_dns_fi_diffusion(dns, kind, q, f, result, work6) bind(C, name='tlab_dns_fi_diffusion')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: dns, q, f, result
+            integer(c_int), value :: kind
+            type(c_ptr), intent(in) :: work6(6)
+        end function
         ! plane spectra and correlations (tlab_amd_spectra.f90); a_hat .. outr: device or host arrays of one kind, the profiles host memory
         integer(c_int) function tlab_spectrum_reduce(nx, ny, nz, nblock, kr_total, a_hat, b_hat, out2d, outx, outz, outr, variance) &
             bind(C, name='tlab_spectrum_reduce')

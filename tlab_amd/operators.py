@@ -978,3 +978,127 @@ def log10_small(a):
     _stream_if_device([a])
     check(load().tlab_log10_small(n, _field_ptr(a, n, "a", keep)), "tlab_log10_small")
     return a
+
+
+# ---- field mappings: the first-derivative maps in one pass over the gradients, the diffusion and pressure terms (csrc/tlab_amd_mappings.h) ------
+# name -> (TLAB_MAP_* code, outputs, reads the scalar gradient)
+MAPS = {
+    "P": (0, 1, False), "Q": (1, 1, False), "R": (2, 1, False), "STRAIN": (3, 1, False), "STRAIN_TENSOR": (4, 6, False), "CURL": (5, 4, False),
+    "VORTICITY": (6, 1, False), "VORTICITY_PRODUCTION": (7, 1, False), "STRAIN_PRODUCTION": (8, 1, False), "GRADIENT": (9, 1, True),
+    "GRADIENT_PRODUCTION": (10, 1, True), "STRAIN_A": (11, 3, True),
+}
+FI_DIFFUSION_KINDS = {"VORTICITY_DIFFUSION": 0, "STRAIN_DIFFUSION": 1, "GRADIENT_DIFFUSION": 2, "STRAIN_PRESSURE": 3}
+
+
+def _map_call(maps, like, n, out, keep):
+    """(codes, output pointers, the dict handed back) of a call that names `maps`; out: a flat list of the outputs, new arrays like `like` if None"""
+    maps = [maps] if isinstance(maps, str) else list(maps)
+    unknown = [m for m in maps if m not in MAPS]
+    if unknown or not maps:
+        raise TlabError("maps: names of %s, got %r" % (", ".join(MAPS), unknown or maps))
+    nout = sum(MAPS[m][1] for m in maps)
+    if out is None:
+        if isinstance(like, np.ndarray):
+            out = [np.empty(n) for _ in range(nout)]
+        else:
+            import torch
+            out = [torch.empty(n, dtype=torch.float64, device=like.device) for _ in range(nout)]
+    out = list(out)
+    if len(out) != nout:
+        raise TlabError("out must hold %d arrays, one per output of the maps" % nout)
+    codes = (ctypes.c_int * len(maps))(*[MAPS[m][0] for m in maps])
+    ptrs = (c_vp * nout)(*[_field_ptr(o, n, "out[%d]" % i, keep).value for i, o in enumerate(out)])
+    res, k = {}, 0
+    for m in maps:
+        res[m] = out[k] if MAPS[m][1] == 1 else tuple(out[k:k + MAPS[m][1]])
+        k += MAPS[m][1]
+    return codes, ptrs, res
+
+
+def gradient_maps(du9, ds3, maps, out=None):
+    """The maps `maps` (names of MAPS, or one name) of the velocity gradients du9 = [u,x u,y u,z v,x v,y v,z w,x w,y w,z] and, for GRADIENT,
+    GRADIENT_PRODUCTION and STRAIN_A, of the scalar gradient ds3 = [s,x s,y s,z] (else None), in one pass that reads each gradient once: torch
+    tensors (k_gradient_maps) or numpy arrays (the host loop), not a mix.  An entry of du9 / ds3 that no requested map reads may be None.
+    A dict name -> array, or a tuple of arrays for STRAIN_TENSOR (Sxx Syy Szz Sxy Sxz Syz), CURL (wx wy wz, their squared magnitude) and
+    STRAIN_A (strain1, strain2, G.G); out: the output arrays in that order, new ones if None.  Every operation is the reference's."""
+    keep, du9 = [], list(du9)
+    ds3 = [None] * 3 if ds3 is None else list(ds3)
+    if len(du9) != 9 or len(ds3) != 3:
+        raise TlabError("du9 must hold nine arrays and ds3 three")
+    given = [a for a in du9 + ds3 if a is not None]
+    if not given:
+        raise TlabError("no gradient given")
+    n = given[0].size if isinstance(given[0], np.ndarray) else given[0].numel()
+    codes, optrs, res = _map_call(maps, given[0], n, out, keep)
+    _stream_if_device(given)
+    dptr = (c_vp * 9)(*[_field_ptr(a, n, "du9[%d]" % i, keep).value for i, a in enumerate(du9)])
+    sptr = (c_vp * 3)(*[_field_ptr(a, n, "ds3[%d]" % i, keep).value for i, a in enumerate(ds3)]) if any(a is not None for a in ds3) else None
+    check(load().tlab_gradient_maps(n, dptr, sptr, codes, len(codes), optrs), "tlab_gradient_maps")
+    return res
+
+
+def _dev_ptrs(arrays, n, name):
+    return (c_vp * len(arrays))(*[_ptr(a, n, "%s[%d]" % (name, i)).value for i, a in enumerate(arrays)])
+
+
+def velocity_gradients(dns, q, txc9):
+    """OPR_Partial_X/Y/Z(OPR_P1) of q[0..2] by the plans of the driver dns, bcs = 0, into txc9 = [u,x u,y u,z v,x v,y v,z w,x w,y w,z]."""
+    _use_torch_stream()
+    check(load().tlab_dns_velocity_gradients(dns._h, _dev_ptrs(list(q)[:3], dns.n, "q"), _dev_ptrs(list(txc9), dns.n, "txc9")),
+          "tlab_dns_velocity_gradients")
+    return txc9
+
+
+def scalar_gradient(dns, s, ds3):
+    """The same of one scalar into ds3 = [s,x s,y s,z]."""
+    _use_torch_stream()
+    check(load().tlab_dns_scalar_gradient(dns._h, _ptr(s, dns.n, "s"), _dev_ptrs(list(ds3), dns.n, "ds3")), "tlab_dns_scalar_gradient")
+    return ds3
+
+
+def fi_maps(dns, q, s, maps, txc9, ds3=None, out=None):
+    """velocity_gradients(q) into txc9, scalar_gradient(s) into ds3 where a map reads it, then gradient_maps: any set of FI_INVARIANT_P/Q/R,
+    FI_STRAIN, FI_STRAIN_TENSOR, FI_CURL, FI_VORTICITY, FI_VORTICITY_PRODUCTION, FI_STRAIN_PRODUCTION, FI_GRADIENT, FI_GRADIENT_PRODUCTION and
+    FI_STRAIN_A on the box of the driver dns from nine (twelve) derivatives, which stay in txc9 / ds3.  Device tensors; a dict as gradient_maps."""
+    txc9 = list(txc9)
+    if len(txc9) != 9:
+        raise TlabError("txc9 must hold nine arrays")
+    codes, optrs, res = _map_call(maps, txc9[0], dns.n, out, [])
+    _use_torch_stream()
+    check(load().tlab_dns_fi_maps(dns._h, _dev_ptrs(list(q)[:3], dns.n, "q"), _ptr(s, dns.n, "s"), codes, len(codes), _dev_ptrs(txc9, dns.n, "txc9"),
+                                  _dev_ptrs(list(ds3), dns.n, "ds3") if ds3 is not None else None, optrs), "tlab_dns_fi_maps")
+    return res
+
+
+def fi_diffusion(dns, kind, q, f, result, work6):
+    """FI_VORTICITY_DIFFUSION, FI_STRAIN_DIFFUSION, FI_GRADIENT_DIFFUSION (f: the scalar) or FI_STRAIN_PRESSURE (f: the pressure) -- kind: a key
+    of FI_DIFFUSION_KINDS -- into result, the reference's OPR_Partial calls in the reference's order on the plans of the driver dns; no
+    viscosity is multiplied.  work6: six work tensors ([0]: vort / strain / grad, [1..4]: tmp1 .. tmp4).  Returns result."""
+    code = FI_DIFFUSION_KINDS.get(kind) if isinstance(kind, str) else int(kind)
+    if code is None:
+        raise TlabError("kind: one of %s" % ", ".join(FI_DIFFUSION_KINDS))
+    work6 = list(work6)
+    if len(work6) != 6:
+        raise TlabError("work6 must hold six work arrays")
+    _use_torch_stream()
+    check(load().tlab_dns_fi_diffusion(dns._h, code, _dev_ptrs(list(q)[:3], dns.n, "q") if q is not None else None, _ptr(f, dns.n, "f"),
+                                       _ptr(result, dns.n, "result"), _dev_ptrs(work6, dns.n, "work6")), "tlab_dns_fi_diffusion")
+    return result
+
+
+# the reference's routines by name: the map on the driver's box, its gradients left in txc9 (and ds3)
+def _named(name, scalar):
+    if scalar:
+        def f(dns, q, s, txc9, ds3, out=None):
+            return fi_maps(dns, q, s, name, txc9, ds3, out)[name]
+    else:
+        def f(dns, q, txc9, out=None):
+            return fi_maps(dns, q, None, name, txc9, out=out)[name]
+    f.__doc__ = "FI_%s of the reference on the driver dns: fi_maps with the one map %s." % (name if len(name) > 1 else "INVARIANT_" + name, name)
+    return f
+
+
+fi_strain, fi_strain_tensor, fi_curl = _named("STRAIN", False), _named("STRAIN_TENSOR", False), _named("CURL", False)
+fi_invariant_q, fi_invariant_r = _named("Q", False), _named("R", False)
+fi_vorticity_production, fi_strain_production = _named("VORTICITY_PRODUCTION", False), _named("STRAIN_PRODUCTION", False)
+fi_gradient_production, fi_strain_a = _named("GRADIENT_PRODUCTION", True), _named("STRAIN_A", True)
